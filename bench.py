@@ -21,9 +21,12 @@ Either way the bands are gathered on rank 0 inside the timed step.  The frame is
 grows -> "scaling": "strong".  The line also carries "config4": BASELINE configs[3], the 4K
 scene of config 3 partitioned over the same N GPUs, timed the same way.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
-"roofline" for the dominant kernel (the blend) and "cpu_baseline" (the C oracle
-timed on this host's cores, rank 0 at N=1 only).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps frames, writes
+the last frame with --dump-outputs, and prints the headline ("value", "ms_per_step") with the
+blend "roofline" derived from the timed frames.  --full adds everything that takes runs of its
+own: the per-stage breakdown, "roofline_frame", the moving-camera and two-in-flight legs, parity
+against the oracle, "cpu_baseline" (the C oracle timed on this host's cores, rank 0 at N=1 only),
+the virtual-rank frame of config 4 and, at N>1, "config4"; each leg keeps its own switch there.
 """
 from __future__ import annotations
 
@@ -93,6 +96,12 @@ def parse():
     p.add_argument("--steps", type=int, default=50)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--config", default="cfg2_1m_sh3_1080p_f16")
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beyond the headline figure (stage breakdown, orbit, in-flight, parity, "
+                        "CPU baseline, virtual ranks, N>1: config 4); without it those legs and their switches are off")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the last timed frame (what a caller of the timed path receives) as DIR/<name>.npy, "
+                        "float32, at most 64 MB in all (a fixed seeded sample of a larger frame)")
     p.add_argument("--cpu-baseline", type=int, default=1, help="time the C oracle (rank 0, N=1)")
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="oracle threads of cpu_baseline (0: every CPU of this process's affinity mask)")
@@ -123,9 +132,36 @@ def parse():
                    help="N>1: also time this config's frame on the N GPUs (BASELINE config 4: the 4K scene), "
                         "reported under 'config4'; 'none' = off")
     a = p.parse_args()
+    if not a.full:  # a plain run: the headline figure only
+        a.cpu_baseline = a.cpu_one_thread = a.parity = a.orbit_steps = a.inflight_steps = a.virtual_ranks = 0
+        a.multi_extra_config = "none"
     if a.traffic_json is None:
         a.traffic_json = os.path.join(ROOT, "profiles", f"{a.pmc_tag}_pmc_blend_{a.config.split('_')[0]}.json")
     return a
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array of the last timed frame as path/<name>.npy in float32.  A frame larger
+    than the budget is sampled: the same seeded element indices (sorted, row-major) of every array on every
+    run, so two builds are compared element for element."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.size * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).astype(np.float32)
+        if total > DUMP_BUDGET_BYTES:
+            keep = int(a.size * (DUMP_BUDGET_BYTES / total))
+            idx = np.sort(np.random.default_rng(1234).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def half_frame(t):
+    """A float16 device tensor as a host float16 array (bit copy)."""
+    import torch
+    return t.contiguous().view(torch.int16).cpu().numpy().view(np.float16)
 
 
 def launch_ranks(args) -> int:
@@ -322,13 +358,21 @@ def main():
     # stream -- two events on every BLEND_EVENT_PERIOD-th frame (each bracketed frame costs ~10 us
     # of event overhead, tools/exp_events.py); the per-stage breakdown comes from a separate pass below
     elapsed, blend_ms_timed = timed_loop(args.steps, step, renderer, world_size, dev, backend)
-    # per-stage breakdown: 10 more frames with every stage bracketed (not part of `value`)
-    renderer.set_profiling(stage_events=True)
-    for _ in range(10):
-        step()
-    torch.cuda.synchronize()
-    stage_ms = renderer.stage_times_ms()
-    stage_ms["blend_timed_region"] = blend_ms_timed
+    if args.dump_outputs and rank == 0:  # the last timed frame, before any other leg renders
+        if native_multi:  # the gathered N-GPU frame
+            dump_outputs(args.dump_outputs, {"color": mg.copy_frame(W, H).view(np.float16),
+                                             "depth": mg.copy_depth(W, H).view(np.float16)})
+        else:  # the whole frame (N = 1) or rank 0's band of it (N > 1 without the native frame)
+            dump_outputs(args.dump_outputs, {"color": half_frame(color[:H]), "depth": half_frame(depth[:H])})
+    stage_ms = {"blend_timed_region": blend_ms_timed}
+    if args.full:
+        # per-stage breakdown: 10 more frames with every stage bracketed (not part of `value`)
+        renderer.set_profiling(stage_events=True)
+        for _ in range(10):
+            step()
+        torch.cuda.synchronize()
+        stage_ms = renderer.stage_times_ms()
+        stage_ms["blend_timed_region"] = blend_ms_timed
     counters = renderer.counters()
     # the blend kernel the library launched for this frame (not re-derived here, so a
     # GSM_BLEND_WAVES / GSM_BLEND_PAIRS override is attributed to the kernel that actually ran)
@@ -454,8 +498,8 @@ def main():
                         f"upper bound if every gather segment were 128 B: {int(2 * raw_fetch + write)} B")
         valu_insts = tj.get("valu_insts_per_launch")
         valu_mix = tj.get("valu_mix_per_launch")
-    stage_sum = sum(v for k, v in stage_ms.items() if k != "blend_timed_region")
-    sort_gkeys = A / (stage_ms["sort"] * 1e-3) / 1e9 if stage_ms["sort"] > 0 else 0.0
+    stage_sum = sum(v for k, v in stage_ms.items() if k != "blend_timed_region") if args.full else None
+    sort_gkeys = (A / (stage_ms["sort"] * 1e-3) / 1e9 if stage_ms["sort"] > 0 else 0.0) if args.full else None
 
     parity = None
     cpu = None
@@ -503,14 +547,17 @@ def main():
     # SURVEY.md 8(d) B_frame: the minimal dataflow of one frame (inputs of all N, SH of the visible
     # V, render data, assignment write, K = 4 sort passes of key + value read and write, blend reads,
     # targets, headers), against the whole frame's time
-    V = visible_count(renderer, gsm_amd)
-    s_w = 32 if prec else 48
-    s_sh = 3 * sh * (2 if prec else 4)
-    b_frame = n * s_w + V * s_sh + V * 16 + A * 8 + 4 * A * 16 + A * 20 + P * 10 + T * 8
+    V = b_frame = None
+    if args.full:
+        V = visible_count(renderer, gsm_amd)
+        s_w = 32 if prec else 48
+        s_sh = 3 * sh * (2 if prec else 4)
+        b_frame = n * s_w + V * s_sh + V * 16 + A * 8 + 4 * A * 16 + A * 20 + P * 10 + T * 8
     out = {
         "metric": "frames/sec @ N Gaussians × W×H (1/2/4/8 GPU); sort Gkeys/s; blend HBM GB/s",
         "value": fps,
         "unit": "frames/s",
+        "full": bool(args.full),
         "n_gpus": world_size,
         "steps": args.steps,
         "warmup": args.warmup,
@@ -541,7 +588,8 @@ def main():
         "roofline_frame": {"bound": "hbm", "achieved": b_frame / (ms_per_step * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
                            "unit": "GB/s", "frac": b_frame / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
                            "algorithmic_bytes": b_frame,
-                           "formula": "N*S_w + V*S_sh + V*16 + A*8 + 4*A*16 + A*20 + P*10 + T*8 (SURVEY.md 8d)"},
+                           "formula": "N*S_w + V*S_sh + V*16 + A*8 + 4*A*16 + A*20 + P*10 + T*8 (SURVEY.md 8d)"}
+        if args.full else None,
         "cpu_baseline": cpu,
         "stages_ms": stage_ms,
         "stages_sum_ms": stage_sum,
@@ -800,16 +848,21 @@ def run_depthfirst(args, c, world_np, harm_np, world, harm, dev):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     blend_ms_timed = renderer.stage_times_ms()["blend"]
-    renderer.set_profiling(stage_events=True)
-    for _ in range(10):
+    if args.dump_outputs:  # the last timed frame, before any other leg renders
+        dump_outputs(args.dump_outputs, {"color": half_frame(color)})
+    stage_ms = {"blend_timed_region": blend_ms_timed}
+    walk = None
+    if args.full:
+        renderer.set_profiling(stage_events=True)
+        for _ in range(10):
+            step()
+        torch.cuda.synchronize()
+        stage_ms = renderer.stage_times_ms()
+        stage_ms["blend_timed_region"] = blend_ms_timed
+        renderer.set_profiling(stage_events=False, blend_stats=True)  # one more frame: walk statistics
         step()
-    torch.cuda.synchronize()
-    stage_ms = renderer.stage_times_ms()
-    stage_ms["blend_timed_region"] = blend_ms_timed
-    renderer.set_profiling(stage_events=False, blend_stats=True)  # one more frame: walk statistics
-    step()
-    torch.cuda.synchronize()
-    walk = [int(x) for x in renderer.copy_buffer(gsm_amd.DepthFirstBuffer.BLEND_STATS)]
+        torch.cuda.synchronize()
+        walk = [int(x) for x in renderer.copy_buffer(gsm_amd.DepthFirstBuffer.BLEND_STATS)]
     cnt = renderer.counters()
     ms_per_step = elapsed / args.steps * 1e3
     A, T, P = cnt["total_instances"], cnt["tile_count"], 2 * W * H
@@ -848,7 +901,7 @@ def run_depthfirst(args, c, world_np, harm_np, world, harm, dev):
                                      ref["times"], per_threads)
     out = {
         "metric": "frames/sec @ N Gaussians × W×H (1/2/4/8 GPU); sort Gkeys/s; blend HBM GB/s",
-        "value": 1e3 / ms_per_step, "unit": "frames/s", "n_gpus": 1, "steps": args.steps,
+        "value": 1e3 / ms_per_step, "unit": "frames/s", "full": bool(args.full), "n_gpus": 1, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong",
         "vs_baseline": None, "dtype": "fp16", "data": "synthetic",
         "config": {"workload": f"{args.config}: {n} gaussians SH{ {1: 0, 4: 1, 9: 2, 16: 3}[sh] } 2x{W}x{H} "
@@ -863,7 +916,8 @@ def run_depthfirst(args, c, world_np, harm_np, world, harm, dev):
                      "algorithmic_bytes": b_blend, "launch_timing": f"HIP events around the blend on every {BLEND_EVENT_PERIOD}th frame of the timed region", "avg_launch_ms": blend_ms_timed,
                      "note": "blend is bound by packed-fp16 VALU issue (fp16 math per pixel per (tile, eye) unit)"},
         "roofline_valu": valu_roofline("k_df_blend_eye", valu_insts, valu_mix, t_blend),
-        "blend_walk": {"walked": walk[0], "with_mean": walk[1], "blended": walk[2], "list_entries": walk[3]},
+        "blend_walk": {"walked": walk[0], "with_mean": walk[1], "blended": walk[2], "list_entries": walk[3]}
+        if walk else None,
         "cpu_baseline": cpu, "stages_ms": stage_ms, "blend_gb_per_s": achieved, "parity_vs_oracle": parity,
     }
     print(json.dumps(out))

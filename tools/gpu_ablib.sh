@@ -32,7 +32,7 @@ print(sys.argv[2])
 for r in sorted(rows, key=lambda r: -float(r["TotalDurationNs"]))[:12]:
     print(f"  {r['Name'].split('(')[0][:52]:52s} calls={int(r['Calls']):5d} avg_us={float(r['AverageNs'])/1e3:8.1f}")
 PY
-    timeout -k 10 300 python bench.py --config $cfg --steps 50 --warmup 5 --cpu-baseline 0 --orbit-steps ${ORBIT:-0} --virtual-ranks 0 \
+    timeout -k 10 300 python bench.py --full --config $cfg --steps 50 --warmup 5 --cpu-baseline 0 --orbit-steps ${ORBIT:-0} --virtual-ranks 0 \
       --traffic-json /dev/null > $OUT/bench_${v}_$cfg.log 2>&1 || { echo "bench failed: $v $cfg"; tail -n 5 $OUT/bench_${v}_$cfg.log; use A; exit 1; }
     grep '"metric"' $OUT/bench_${v}_$cfg.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('  bench', '$v', round(d['value'],1), 'parity', d.get('parity_vs_oracle'), 'inflight2', (d.get('inflight2') or {}).get('value'), (d.get('inflight2') or {}).get('parity_both_targets'), {k: round(x*1e3,1) for k,x in d['stages_ms'].items()})"
   done

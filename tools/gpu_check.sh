@@ -16,7 +16,7 @@ step() {  # name timeout cmd...
 }
 step pytest_gpu 1100 python -m pytest tests -m gpu -q -rf ${PYTEST_ARGS:-}
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 600 python bench.py --steps ${BENCH_STEPS:-50} --warmup 5
+step bench 600 python bench.py --full --steps ${BENCH_STEPS:-50} --warmup 5
 if [ "${PROFILE:-1}" = "1" ]; then
   step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o run -- \
        python bench.py --steps 20 --warmup 3 --cpu-baseline 0 --parity 0 --orbit-steps 0 --inflight-steps 0 --virtual-ranks 0

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/dfpmc
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python bench.py --config cfg5_1m_sh2_stereo_2x1440x1600_f16 --steps 5 --warmup 2 --cpu-baseline 0 --parity 0"
+CMD="python bench.py --full --config cfg5_1m_sh2_stereo_2x1440x1600_f16 --steps 5 --warmup 2 --cpu-baseline 0 --parity 0"
 i=0
 for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE" \
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM SQ_WAIT_INST_LDS"; do

@@ -15,7 +15,7 @@ CTR="SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_INSTS_VALU SQ_WAVES 
 for v in ${VARIANTS:-A}; do
   use $v
   for cfg in ${CFGS:-cfg2_1m_sh3_1080p_f16}; do
-    CMD="python bench.py --config $cfg --steps 5 --warmup 2 --cpu-baseline 0 --parity 0 --orbit-steps ${PMC_ORBIT:-0} --inflight-steps 0 --virtual-ranks 0"
+    CMD="python bench.py --full --config $cfg --steps 5 --warmup 2 --cpu-baseline 0 --parity 0 --orbit-steps ${PMC_ORBIT:-0} --inflight-steps 0 --virtual-ranks 0"
     rm -rf $OUT/pmc_${v}_$cfg
     timeout -s KILL 120 rocprofv3 --pmc $CTR --output-format csv -d $OUT/pmc_${v}_$cfg -o p -- $CMD > $OUT/pmc_${v}_$cfg.log 2>&1 \
       || { echo "pmc failed: $v $cfg"; tail -n 5 $OUT/pmc_${v}_$cfg.log; use A; exit 1; }
@@ -34,7 +34,7 @@ for k, cs in acc.items():
     print(f"  {sys.argv[2]} {k[:40]}: conflict {bc/1e6:.2f}M / active {act/1e6:.2f}M = {bc/act:.3f}; "
           f"LDS insts {m.get('SQ_INSTS_LDS',0)/1e6:.2f}M VALU {m.get('SQ_INSTS_VALU',0)/1e6:.2f}M waves {m.get('SQ_WAVES',0):.0f}")
 PY
-    timeout -k 10 300 python bench.py --config $cfg --steps 50 --warmup 5 --cpu-baseline 0 --cpu-threads 16 --orbit-steps ${ORBIT:-50} \
+    timeout -k 10 300 python bench.py --full --config $cfg --steps 50 --warmup 5 --cpu-baseline 0 --cpu-threads 16 --orbit-steps ${ORBIT:-50} \
       --inflight-steps 0 --virtual-ranks 0 --traffic-json /dev/null > $OUT/bench_${v}_$cfg.log 2>&1 \
       || { echo "bench failed: $v $cfg"; tail -n 5 $OUT/bench_${v}_$cfg.log; use A; exit 1; }
     grep '"metric"' $OUT/bench_${v}_$cfg.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); o=d.get('orbit') or {}; print('  bench', '$v', '$cfg', round(d['value'],1), 'parity', d.get('parity_vs_oracle'), 'blend_us', round(d['stages_ms']['blend_timed_region']*1e3,1), 'orbit', round(o.get('value',0),1), o.get('blend_ms'), o.get('parity_last_frame'))"

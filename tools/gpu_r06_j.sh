@@ -12,7 +12,7 @@ for rep in 1 2; do
     for cfg in cfg2_1m_sh3_1080p_f16 cfg3_5m_sh3_4k_f16; do
       label=${cl}_${cfg%%_*}_r$rep
       GSM_BLEND_CLAIM=$cl timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$label -o run -- \
-        python bench.py --config $cfg --steps 20 --warmup 3 --cpu-baseline 0 --parity 1 --orbit-steps 20 --inflight-steps 0 \
+        python bench.py --full --config $cfg --steps 20 --warmup 3 --cpu-baseline 0 --parity 1 --orbit-steps 20 --inflight-steps 0 \
         --virtual-ranks 0 > $OUT/$label.log 2>&1 || { echo "run $label failed"; tail -5 $OUT/$label.log; exit 1; }
       f=$(find $OUT/$label -name '*kernel_stats.csv' | head -1)
       python3 - "$f" "$label" "$OUT/$label.log" <<'PY' | tee -a $OUT/summary.txt

@@ -42,8 +42,8 @@ if [ "${PMC:-1}" = 1 ]; then
 fi
 for cfg in $CFGS; do
   c=${cfg%%_*}
-  step bench_$c 600 python bench.py --config $cfg --traffic-json $OUT/pmc_blend_$c.json
-  [ $c = cfg5 ] && step bench_${c}_global 600 python bench.py --config $cfg --stereo-path global --cpu-baseline 0 \
+  step bench_$c 600 python bench.py --full --config $cfg --traffic-json $OUT/pmc_blend_$c.json
+  [ $c = cfg5 ] && step bench_${c}_global 600 python bench.py --full --config $cfg --stereo-path global --cpu-baseline 0 \
        --traffic-json /dev/null
   step kt_$c 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$c -o run -- \
        python bench.py --config $cfg --steps 50 --warmup 5 --cpu-baseline 0 --parity 0 --orbit-steps 0 --inflight-steps 0 --virtual-ranks 0

@@ -5,7 +5,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 O=gpurun_out/scanab; mkdir -p $O; export TMPDIR=/tmp
 b() {  # label cfg mode
-  GSM_SCAN=$3 timeout -k 10 300 python bench.py --config $2 --steps 100 --warmup 5 --cpu-baseline 0 --orbit-steps 0 \
+  GSM_SCAN=$3 timeout -k 10 300 python bench.py --full --config $2 --steps 100 --warmup 5 --cpu-baseline 0 --orbit-steps 0 \
     --inflight-steps 0 --virtual-ranks 0 --traffic-json /dev/null > $O/bench_$1.log 2>&1 || { echo "bench $1 failed"; tail -5 $O/bench_$1.log; exit 1; }
   grep '"metric"' $O/bench_$1.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$1', round(d['value'],1), 'parity', d.get('parity_vs_oracle'), {k: round(x*1e3,1) for k, x in d['stages_ms'].items()})"
 }

@@ -12,7 +12,7 @@ if [ "${TESTS:-1}" = 1 ]; then
 fi
 b() {  # label cfg env...
   local label=$1 cfg=$2; shift 2
-  env "$@" timeout -k 10 300 python bench.py --config $cfg --steps ${STEPS:-100} --warmup 5 --cpu-baseline 0 \
+  env "$@" timeout -k 10 300 python bench.py --full --config $cfg --steps ${STEPS:-100} --warmup 5 --cpu-baseline 0 \
     --orbit-steps ${ORBIT:-50} --inflight-steps 0 --virtual-ranks 0 --traffic-json /dev/null > $O/bench_$label.log 2>&1
   local rc=$?
   [ $rc -eq 0 ] || { echo "bench $label rc=$rc"; tail -n 5 $O/bench_$label.log; exit $rc; }
