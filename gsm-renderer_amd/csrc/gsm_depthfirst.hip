@@ -6,6 +6,8 @@
 // 469-512, 595-831) over the DepthFirstResources scratch set (DepthFirstResources.swift:380-470).
 // One HIP stream replaces the command buffer; grids are capacity-sized and data-dependent
 // counts are read on the device, so a frame is enqueue-only.
+// The mono frame, DepthFirstRenderer.render -> encodeRender (:166-203, 237-465), runs on the same
+// handle and arena (renderMono).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -28,6 +30,8 @@ class DepthFirstRenderer {
     gsm_status renderStereoSbs(hipStream_t s, const gsm_gaussian_input& in, const gsm_camera_params& left,
                                const gsm_camera_params& right, const float* scene, uint32_t width, uint32_t height,
                                void* color, size_t pitch);
+    gsm_status renderMono(hipStream_t s, const gsm_gaussian_input& in, const gsm_camera_params& cam, uint32_t width,
+                          uint32_t height, void* color, size_t pitch, void* depth, size_t depthPitch);
     gsm_status counters(gsm_depthfirst_counters* out);
     gsm_status debugCopy(int which, void* dst, size_t bytes, size_t* needed);
     gsm_status setProfiling(int flags);
@@ -48,6 +52,7 @@ class DepthFirstRenderer {
     std::vector<void*> allocations_;
     // last frame
     uint32_t lastCount_ = 0, lastTilesX_ = 0, lastTilesY_ = 0;
+    bool lastMono_ = false;  // the last frame was a mono frame (16-byte records)
     uint64_t schedKey_ = ~0ull;  // geometry the unit costs belong to
     unsigned long long* statsBuf_ = nullptr;  // blend walk statistics (profiling bit 1)
     const uint32_t* depthOrder_ = nullptr;
@@ -153,6 +158,8 @@ gsm_status DepthFirstRenderer::create(const gsm_renderer_config& cfg, int hipDev
     GSM_DF_ALLOC(A.unitCost, (size_t)r->maxTiles_ * 2 * sizeof(uint16_t));
     GSM_DF_ALLOC(A.unitOrder, (size_t)r->maxTiles_ * 2 * sizeof(uint32_t));
     GSM_DF_ALLOC(A.costMax, kCostMaxSlots * sizeof(uint32_t));
+    GSM_DF_ALLOC(A.sincos, 65536 * sizeof(float2));
+    GSM_DF_ALLOC(A.expTableMono, 65536 * 2);
 #undef GSM_DF_ALLOC
     if (st != GSM_OK) {
         delete r;
@@ -160,7 +167,16 @@ gsm_status DepthFirstRenderer::create(const gsm_renderer_config& cfg, int hipDev
     }
     std::vector<uint16_t> expt(65536);
     for (uint32_t i = 0; i < 65536; ++i) expt[i] = stereo_exp_table_entry((uint16_t)i);
-    if (hipMemcpy(A.expTable, expt.data(), 65536 * 2, hipMemcpyHostToDevice) != hipSuccess ||
+    // the mono frame's tables: the Global blend's alpha table and the sin/cos of the quantised angles
+    std::vector<uint16_t> exptMono(65536);
+    std::vector<float2> sc(65536);
+    for (uint32_t i = 0; i < 65536; ++i) {
+        exptMono[i] = blend_exp_table_entry((uint16_t)i);
+        det_sincos_table_entry(i, &sc[i].x, &sc[i].y);
+    }
+    if (hipMemcpy(A.expTableMono, exptMono.data(), 65536 * 2, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(A.sincos, sc.data(), 65536 * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(A.expTable, expt.data(), 65536 * 2, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(A.visHdr, 0, sizeof(TileAssignmentHeader)) != hipSuccess ||
         hipMemset(A.instHdr, 0, sizeof(TileAssignmentHeader)) != hipSuccess ||
         hipMemset(A.costMax, 0, kCostMaxSlots * sizeof(uint32_t)) != hipSuccess ||
@@ -290,6 +306,95 @@ gsm_status DepthFirstRenderer::renderStereoSbs(hipStream_t s, const gsm_gaussian
     lastCount_ = a.count;
     lastTilesX_ = a.tilesX;
     lastTilesY_ = a.tilesY;
+    lastMono_ = false;
+    depthOrder_ = A_.dvals[dc];
+    instTiles_ = A_.ikeys[ic];
+    instGids_ = A_.ivals[ic];
+    if (hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;
+    return GSM_OK;
+}
+
+// DepthFirstRenderer.render -> encodeRender (DepthFirstRenderer.swift:166-203, 237-465) on the same
+// arena as the stereo frame: the 16-byte GaussianRenderData records alias the stereo renderData, the
+// compaction, both sorts and the scans are the stereo frame's, and the stage events map onto the same
+// GSM_DF_STAGE_* slots.  Nothing of a frame outlives it except the stereo blend's unit costs, which
+// this path neither reads nor writes.
+gsm_status DepthFirstRenderer::renderMono(hipStream_t s, const gsm_gaussian_input& in, const gsm_camera_params& cam,
+                                          uint32_t width, uint32_t height, void* color, size_t pitch, void* depth,
+                                          size_t depthPitch) {
+    (void)hipGetLastError();
+    // encodeRender's guard (:249) and the texture sizes -- errors, not a silent return
+    if (in.gaussian_count == 0 || in.gaussian_count > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
+    if (width == 0 || height == 0 || width > maxWidth_ || height > maxHeight_) return GSM_ERR_INVALID_DIMENSIONS;
+    if (!color || !in.gaussians || !in.harmonics) return GSM_ERR_MISSING_REQUIRED_BUFFER;
+    const int fmt = (int)config_.color_format;
+    const size_t bpp = fmt == GSM_COLOR_FORMAT_RGBA16F ? 8 : (fmt == GSM_COLOR_FORMAT_RGBA32F ? 16 : 4);
+    if (pitch < (size_t)width * bpp) return GSM_ERR_INVALID_BUFFER_SIZE;
+    if ((((uintptr_t)color) & 3u) || (pitch & 3u)) return GSM_ERR_INVALID_BUFFER_SIZE;
+    if (depth && (depthPitch < (size_t)width * 2 || (depthPitch & 1u) || (((uintptr_t)depth) & 1u)))
+        return GSM_ERR_INVALID_BUFFER_SIZE;
+    if (hipSetDevice(device_) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
+
+    DfArgs a;
+    std::memset(&a, 0, sizeof(a));
+    const float W = (float)width, H = (float)height;
+    // CameraUniforms(from: camera, ...) (KernelTypes.swift:107-123)
+    eye_const(cam, W, H, &a.eye[0]);
+    a.width = W;
+    a.height = H;
+    a.nearPlane = cam.near_plane;
+    a.farPlane = cam.far_plane;
+    const float maxDim = std::fmax(W, H);
+    const float maxEig = (maxDim * 2.0f) / 3.0f;
+    a.maxEig = maxEig * maxEig;
+    a.adjFar = a.farPlane * 0.02f;
+    a.adjDen = a.adjFar - a.nearPlane;
+    for (int i = 0; i < 3; ++i) a.mid[i] = cam.position[i];
+    a.inputIsSRGB = config_.gaussian_color_space == GSM_COLOR_SPACE_SRGB ? 1.0f : 0.0f;
+    a.shComponents = in.sh_components;
+    a.count = in.gaussian_count;
+    // buildBinningParams(gaussianCount:width:height:) on 16x16 tiles (GlobalRenderer.swift:54-70)
+    a.tilesX = (width + kDfTile - 1) / kDfTile;
+    a.tilesY = (height + kDfTile - 1) / kDfTile;
+    a.tileCount = a.tilesX * a.tilesY;
+    a.maxInstances = maxInstances_;
+    const uint32_t k = in.sh_components;
+    const uint32_t deg = k <= 1 ? 0u : (k <= 4 ? 1u : (k <= 9 ? 2u : 3u));
+    const bool half = config_.precision == GSM_PRECISION_FLOAT16;
+    const uint32_t nb = (a.count + kDfBlock - 1) / kDfBlock;
+
+    const bool prof = (profiling_ & 1) != 0;
+    const uint32_t period = ((uint32_t)profiling_ >> 8) & 0xFFu;
+    const bool blendOnly = !prof && (profiling_ & 8) != 0 && (period <= 1 || (sampleFrame_++ % period) == 0);
+    hipEvent_t* ev = (prof || blendOnly) ? frameEvents(profFrames_) : nullptr;
+    if (prof) hipEventRecord(ev[0], s);
+    df_launch_project_mono(half, deg, in.gaussians, in.harmonics, a, A_, s);
+    launch_scan_sums(A_.blockSums, nb, maxGaussians_, A_.visHdr, A_.queue, s);
+    df_launch_compact(a, A_, s);
+    if (prof) hipEventRecord(ev[1], s);
+    const int dc = radix_sort_bits(A_.dkeys, A_.dvals, &A_.visHdr->totalAssignments, maxGaussians_, 0, 32,
+                                   sort_space(A_), s, tuning_.ballotRank, tuning_.wideSort,
+                                   tuning_.sortScanless);
+    if (dc == kSortNoSpace) return GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;
+    if (prof) hipEventRecord(ev[2], s);
+    df_launch_instance_counts(A_.dvals[dc], a, A_, s);
+    launch_scan_sums(A_.instSums, nb, maxInstances_, A_.instHdr, A_.queue, s);
+    df_launch_instances_mono(A_.dvals[dc], a, A_, s);
+    if (prof) hipEventRecord(ev[3], s);
+    const int ic = radix_sort_tiles(A_.ikeys, A_.ivals, &A_.instHdr->totalAssignments, maxInstances_, 0, sort_space(A_),
+                                    A_.starts, 0u, a.tileCount, a.tileCount, s, tuning_.ballotRank,
+                                    tuning_.wideSort, tuning_.sortScanless);
+    if (ic == kSortNoSpace) return GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;
+    if (prof || blendOnly) hipEventRecord(ev[4], s);
+    df_launch_blend_mono(A_.ivals[ic], a, A_, color, pitch, fmt, depth, depthPitch, numCUs_, s);
+    if (prof || blendOnly) {
+        hipEventRecord(ev[5], s);
+        profFrames_++;
+    }
+    lastCount_ = a.count;
+    lastTilesX_ = a.tilesX;
+    lastTilesY_ = a.tilesY;
+    lastMono_ = true;
     depthOrder_ = A_.dvals[dc];
     instTiles_ = A_.ikeys[ic];
     instGids_ = A_.ivals[ic];
@@ -322,7 +427,7 @@ gsm_status DepthFirstRenderer::debugCopy(int which, void* dst, size_t bytes, siz
     const void* src = nullptr;
     size_t full = 0;
     switch (which) {
-        case GSM_DF_BUF_RENDER_DATA: src = A_.renderData; full = n * 32; break;
+        case GSM_DF_BUF_RENDER_DATA: src = A_.renderData; full = n * (lastMono_ ? 16 : 32); break;
         case GSM_DF_BUF_BOUNDS: full = n * 16; break;
         case GSM_DF_BUF_TOUCHED: src = A_.touched; full = n * 4; break;
         case GSM_DF_BUF_DEPTH_KEYS: src = A_.depthKeys; full = n * 4; break;
@@ -460,6 +565,14 @@ gsm_status gsm_depthfirst_render_stereo_sbs(gsm_depthfirst* r, void* stream, con
     if (!r || !input || !left || !right) return GSM_ERR_INVALID_ARGUMENT;
     return r->impl->renderStereoSbs((hipStream_t)stream, *input, *left, *right, scene_transform, width, height,
                                     color, color_pitch_bytes);
+}
+
+gsm_status gsm_depthfirst_render(gsm_depthfirst* r, void* stream, const gsm_gaussian_input* input,
+                                 const gsm_camera_params* camera, uint32_t width, uint32_t height, void* color,
+                                 size_t color_pitch_bytes, void* depth_r16f, size_t depth_pitch_bytes) {
+    if (!r || !input || !camera) return GSM_ERR_INVALID_ARGUMENT;
+    return r->impl->renderMono((hipStream_t)stream, *input, *camera, width, height, color, color_pitch_bytes,
+                               depth_r16f, depth_pitch_bytes);
 }
 
 gsm_status gsm_depthfirst_debug_counters(gsm_depthfirst* r, gsm_depthfirst_counters* out) {

@@ -604,6 +604,125 @@ __device__ __forceinline__ BandSkip band_skip_setup(uint32_t meanW, uint32_t ccW
     b.valid = __builtin_isfinite(b.ex);
     return b;
 }
+// ---------------------------------------------------------------------------
+// DepthFirst mono per-tile test (depthFirstProjectCullKernel, DepthFirstShaders.metal:166-205, and
+// createInstancesKernel, :667-715): tile (tx, ty) of 16x16 pixels counts for a gaussian when
+// minQuadRect(tile - mean) <= computeD2Cutoff(opacity_q, tau) (GaussianShared.h:517-593), all of it
+// evaluated on the QUANTISED GaussianRenderData words.  The projection's count and the expansion's
+// writes both call mono_tile_setup + mono_tile_pass on the same 16 bytes, so they agree tile by tile.
+// Numeric contract ("DepthFirst mono"): sin/cos of the quantised angle from the sincos
+// table, log(x) = ln2 * det_log2f(x), IEEE division, no contraction, min/max/clamp as
+// fminf/fmaxf (a NaN operand yields the other one).
+// ---------------------------------------------------------------------------
+constexpr float kMonoAlphaThreshold = 0.005f;  // TileBinningParams.alphaThreshold (GlobalRenderer.swift:54-69)
+struct MonoTileTest {
+    float mx, my;      // fp16 mean
+    float a, b2, c;    // conicFromSigmaTheta: a, 2 b, c
+    float nbc, nba;    // -(b * invC), -(b * invA) of minQuadRect
+    float d2;          // computeD2Cutoff; < 0: no tile passes
+};
+__device__ __forceinline__ MonoTileTest mono_tile_setup(const float2* __restrict__ sincos, uint4 rd) {
+#pragma clang fp contract(off)
+    MonoTileTest T;
+    T.mx = hbits_to_f((uint16_t)(rd.x & 0xFFFFu));
+    T.my = hbits_to_f((uint16_t)(rd.x >> 16));
+    const float2 sc = sincos[rd.y & 0xFFFFu];  // unpackThetaPi + fast::sincos: the table of the contract
+    const float s = sc.x, c = sc.y;
+    const float sigma1 = hbits_to_f((uint16_t)(rd.y >> 16)), sigma2 = hbits_to_f((uint16_t)(rd.z & 0xFFFFu));
+    const float opacity = (float)(rd.w >> 24) * (1.0f / 255.0f);
+    // conicFromSigmaTheta (GaussianShared.h:569-585)
+    const float invS1 = 1.0f / __builtin_fmaxf(sigma1 * sigma1, 1e-12f);
+    const float invS2 = 1.0f / __builtin_fmaxf(sigma2 * sigma2, 1e-12f);
+    const float cc = c * c, ss = s * s, cs = c * s;
+    T.a = cc * invS1 + ss * invS2;
+    T.c = ss * invS1 + cc * invS2;
+    const float b = cs * (invS1 - invS2);
+    T.b2 = 2.0f * b;
+    // computeD2Cutoff (GaussianShared.h:590-593), tau = max(alphaThreshold, 1e-12)
+    const float tau = __builtin_fmaxf(kMonoAlphaThreshold, 1e-12f);
+    const float LN2 = 0.693147180559945f;
+    T.d2 = opacity < tau ? -1.0f : -2.0f * (LN2 * det_log2f(tau / opacity));
+    // minQuadRect's invA, invC (GaussianShared.h:533-534)
+    const float invA = 1.0f / __builtin_fmaxf(T.a, 1e-20f);
+    const float invC = 1.0f / __builtin_fmaxf(T.c, 1e-20f);
+    T.nbc = -(b * invC);
+    T.nba = -(b * invA);
+    return T;
+}
+// evalQuad (GaussianShared.h:518-520): a*x*x + 2.0f*b*x*y + c*y*y, left to right
+__device__ __forceinline__ float mono_eval_quad(const MonoTileTest& T, float x, float y) {
+#pragma clang fp contract(off)
+    return ((T.a * x) * x + (T.b2 * x) * y) + (T.c * y) * y;
+}
+__device__ __forceinline__ bool mono_tile_pass(const MonoTileTest& T, int tx, int ty) {
+#pragma clang fp contract(off)
+    if (!(T.d2 >= 0.0f)) return false;
+    const float tileMinX = (float)tx * 16.0f, tileMaxX = tileMinX + 16.0f;
+    const float tileMinY = (float)ty * 16.0f, tileMaxY = tileMinY + 16.0f;
+    const float xmin = tileMinX - T.mx, xmax = tileMaxX - T.mx;
+    const float ymin = tileMinY - T.my, ymax = tileMaxY - T.my;
+    // minQuadRect (GaussianShared.h:525-564)
+    if (xmin <= 0.0f && 0.0f <= xmax && ymin <= 0.0f && 0.0f <= ymax) return 0.0f <= T.d2;
+    float qmin = __builtin_inff();
+    qmin = __builtin_fminf(qmin, mono_eval_quad(T, xmin, clampf(T.nbc * xmin, ymin, ymax)));
+    qmin = __builtin_fminf(qmin, mono_eval_quad(T, xmax, clampf(T.nbc * xmax, ymin, ymax)));
+    qmin = __builtin_fminf(qmin, mono_eval_quad(T, clampf(T.nba * ymin, xmin, xmax), ymin));
+    qmin = __builtin_fminf(qmin, mono_eval_quad(T, clampf(T.nba * ymax, xmin, xmax), ymax));
+    return qmin <= T.d2;
+}
+// The same test for one gaussian's whole tile rect, spread over the wave: a lane walks its own rect
+// when it has at most kMonoSmallRect tiles; larger rects (up to the whole grid for a screen-filling
+// splat) are taken one after the other by all 64 lanes, 64 tiles per step in ty-major, tx-minor
+// order.  hit(tx, ty, k) is called by the lane that tested the k-th passing tile of the rect (the
+// wave's ballot and popcount give k, so passing tiles keep the reference's order).  Returns the
+// number of passing tiles of this lane's own rect.  Every lane of the wave must call it.
+constexpr uint32_t kMonoSmallRect = 8;
+template <class Hit>
+__device__ __forceinline__ uint32_t mono_rect_tiles(const MonoTileTest& T, short4 r, bool valid, Hit&& hit) {
+    const uint32_t w = valid ? (uint32_t)max(r.y - r.x + 1, 0) : 0u;
+    const uint32_t h = valid ? (uint32_t)max(r.w - r.z + 1, 0) : 0u;
+    const uint32_t area = w * h;
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t n = 0;
+    if (area > 0 && area <= kMonoSmallRect) {
+        for (int ty = r.z; ty <= r.w; ++ty)
+            for (int tx = r.x; tx <= r.y; ++tx)
+                if (mono_tile_pass(T, tx, ty)) {
+                    hit(tx, ty, n, lane);
+                    n++;
+                }
+    }
+    uint64_t big = __builtin_amdgcn_ballot_w64(area > kMonoSmallRect);
+    while (big != 0) {
+        const int src = __builtin_ctzll(big);
+        big &= big - 1;
+        auto bc = [&](float v) {
+            return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src));
+        };
+        MonoTileTest S;
+        S.mx = bc(T.mx); S.my = bc(T.my); S.a = bc(T.a); S.b2 = bc(T.b2); S.c = bc(T.c);
+        S.nbc = bc(T.nbc); S.nba = bc(T.nba); S.d2 = bc(T.d2);
+        const int x0 = __builtin_amdgcn_readlane((int)r.x, src), y0 = __builtin_amdgcn_readlane((int)r.z, src);
+        const uint32_t sw = (uint32_t)__builtin_amdgcn_readlane((int)w, src);
+        const uint32_t sa = (uint32_t)__builtin_amdgcn_readlane((int)area, src);
+        uint32_t cnt = 0;
+        for (uint32_t base = 0; base < sa; base += 64u) {
+            const uint32_t idx = base + lane;
+            const uint32_t dy = idx / sw, dx = idx - dy * sw;
+            const bool p = idx < sa && mono_tile_pass(S, x0 + (int)dx, y0 + (int)dy);
+            const uint64_t pm = __builtin_amdgcn_ballot_w64(p);
+            if (p) {
+                const uint32_t k = cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32),
+                                                                   __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0u));
+                hit(x0 + (int)dx, y0 + (int)dy, k, (uint32_t)src);
+            }
+            cnt += (uint32_t)__builtin_popcountll(pm);
+        }
+        if (lane == (uint32_t)src) n = cnt;
+    }
+    return n;
+}
+
 // Colour target store of one rgba16f pixel in config.color_format (include/gsm_renderer.h
 // conversion rules; oracle og_convert_color): rgba32f widens, the 8-bit formats clamp to
 // [0, 1], sRGB-encode rgb and round to nearest.

@@ -59,6 +59,9 @@ struct DfArena {
     uint32_t* costMax = nullptr;                  // [kCostMaxSlots] longest walk of the last blend
     unsigned long long* blendStats = nullptr;     // [4] profiling bit 1: entries walked / with a real
                                                   // mean / blended, list entries (null: not counted)
+    // mono frame (gsm_depthfirst_render): its 16-byte GaussianRenderData[maxG] alias renderData
+    float2* sincos = nullptr;                     // [65536] sin/cos of the quantised angles
+    uint16_t* expTableMono = nullptr;             // [65536] Global alpha table (blend_exp_table_entry)
 };
 inline SortSpace sort_space(const DfArena& A) { return SortSpace{A.radixHist, A.radixHistBytes, A.radixBinTotals, kSortTotalsWords}; }
 
@@ -85,5 +88,16 @@ void df_launch_instances(const uint32_t* order, const DfArgs& a, const DfArena& 
 // and each wave's longest into A.costMax
 void df_launch_blend(const uint32_t* sortedGids, const DfArgs& a, const DfArena& A, void* color, size_t pitch,
                      int colorFormat, int numCUs, bool costOrder, hipStream_t stream);
+
+// ---- mono frame (DepthFirstRenderer.render, DepthFirstRenderer.swift:237-465) ----
+// a.eye[0] is the camera, a.mid its centre; a.scene / a.sceneScale / a.schedUnits are not used.
+// depthFirstProjectCullKernel (DepthFirstShaders.metal:46-219) + per-block visible counts
+void df_launch_project_mono(bool halfInput, uint32_t shDegree, const void* world, const void* harmonics,
+                            const DfArgs& a, const DfArena& A, hipStream_t stream);
+// createInstancesKernel (:642-716): only the tiles that pass the per-tile test (mono_tile_pass)
+void df_launch_instances_mono(const uint32_t* order, const DfArgs& a, const DfArena& A, hipStream_t stream);
+// clear + depthFirstRender (:2020-2034, :1703-1811) in one persistent kernel; depth may be null
+void df_launch_blend_mono(const uint32_t* sortedGids, const DfArgs& a, const DfArena& A, void* color, size_t pitch,
+                          int colorFormat, void* depth, size_t depthPitch, int numCUs, hipStream_t stream);
 
 }  // namespace gsm

@@ -11,6 +11,8 @@
 // side by side with the copy pass's row flip (k_df_blend_eye).
 // Numeric contract: DESIGN.md (built with -ffp-contract=off, IEEE div/sqrt); bit-exact with
 // oracle/gsm_oracle.c og_df_render_stereo.
+// The mono frame's three kernels (k_df_project_mono, k_df_expand_mono, k_df_blend_mono) follow the
+// stereo ones below; bit-exact with tests/df_mono/df_mono_ref.c.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -696,9 +698,391 @@ __global__ __launch_bounds__(NW * 64) void k_df_blend_eye(const uint32_t* __rest
     if (unitCost && lane == 0 && waveMax) atomicMax(&costMax[(blockIdx.x * NW + wave) % kCostMaxSlots], waveMax);
 }
 
+// ===========================================================================
+// DepthFirst mono frame (DepthFirstRenderer.render, DepthFirstRenderer.swift:166-203, 237-465):
+// k_df_project_mono -> k_df_compact -> depth sort -> k_df_icount, scan, k_df_expand_mono -> tile
+// sort with tile starts -> k_df_blend_mono.  DESIGN.md "DepthFirst mono".
+// ===========================================================================
+
+// ---------------------------------------------------------------------------
+// M1. depthFirstProjectCullKernel (DepthFirstShaders.metal:46-219) + per-block visible counts.
+// The Global projection (project_gaussian, gsm_kernels.hip) with the far-plane cull, ndcToScreen
+// without the half-pixel centring, 16x16 tile bounds and the per-tile touched count.  P.eye[0]
+// holds the camera, P.mid its centre; the scene transform is not part of this path.
+// ---------------------------------------------------------------------------
+template <bool HALF, int DEG>
+__global__ __launch_bounds__(kDfBlock) void k_df_project_mono(const void* __restrict__ world,
+                                                              const void* __restrict__ harm, DfArgs P,
+                                                              const float2* __restrict__ sincos,
+                                                              uint4* __restrict__ outRD,
+                                                              short4* __restrict__ outBounds,
+                                                              uint32_t* __restrict__ touchedOut,
+                                                              uint32_t* __restrict__ depthKeys,
+                                                              uint32_t* __restrict__ blockSums) {
+    __shared__ uint32_t lds[kDfBlock / 64];
+    const uint32_t gid = blockIdx.x * kDfBlock + threadIdx.x;
+    const DfEyeConst& E = P.eye[0];
+    bool ok = gid < P.count;
+    uint4 rdw = make_uint4(0u, 0u, 0u, 0u);
+    short4 tb = make_short4(0, -1, 0, -1);
+    float depth = 0.0f;
+    if (ok) {
+        float pos[3], scale[3], rot[4], opacity;
+        if constexpr (HALF) {
+            const uint4* wq = (const uint4*)((const PackedWorldGaussianHalf*)world + gid);
+            const uint4 w0 = wq[0], w1 = wq[1];
+            pos[0] = __builtin_bit_cast(float, w0.x);
+            pos[1] = __builtin_bit_cast(float, w0.y);
+            pos[2] = __builtin_bit_cast(float, w0.z);
+            opacity = hbits_to_f((uint16_t)(w0.w & 0xFFFFu));
+            scale[0] = hbits_to_f((uint16_t)(w0.w >> 16));
+            scale[1] = hbits_to_f((uint16_t)(w1.x & 0xFFFFu));
+            scale[2] = hbits_to_f((uint16_t)(w1.x >> 16));
+            rot[0] = hbits_to_f((uint16_t)(w1.y & 0xFFFFu));
+            rot[1] = hbits_to_f((uint16_t)(w1.y >> 16));
+            rot[2] = hbits_to_f((uint16_t)(w1.z & 0xFFFFu));
+            rot[3] = hbits_to_f((uint16_t)(w1.z >> 16));
+        } else {
+            const float4* wq = (const float4*)((const PackedWorldGaussian*)world + gid);
+            const float4 w0 = wq[0], w1 = wq[1], w2 = wq[2];
+            pos[0] = w0.x; pos[1] = w0.y; pos[2] = w0.z; opacity = w0.w;
+            scale[0] = w1.x; scale[1] = w1.y; scale[2] = w1.z;
+            rot[0] = w2.x; rot[1] = w2.y; rot[2] = w2.z; rot[3] = w2.w;
+        }
+        // cullByScale (GaussianShared.h:719-722), alpha threshold (:94)
+        ok = !(__builtin_fmaxf(scale[0], __builtin_fmaxf(scale[1], scale[2])) < 0.0005f) &&
+             !(opacity < kMonoAlphaThreshold);
+        float vp[4], clip[4];
+        float sx = 0.0f, sy = 0.0f;
+        if (ok) {
+            const float p4[4] = {pos[0], pos[1], pos[2], 1.0f};
+            m4_mul_v(E.view, p4, vp);
+            m4_mul_v(E.proj, vp, clip);
+            depth = clip[3];
+            if (!(clip[3] > P.nearPlane)) ok = false;  // isInFrontOfCameraClipW
+            if (depth > P.farPlane) ok = false;        // cullByFarPlane (GaussianShared.h:732-734)
+        }
+        Cov2 cov;
+        float theta = 0.0f, s1 = 0.0f, s2 = 0.0f;
+        if (ok) {
+            float ndc[2] = {clip[0], clip[1]};
+            div_many(ndc, clip[3]);  // clip / w, each correctly rounded (w > near > 0)
+            sx = (ndc[0] + 1.0f) * 0.5f * P.width;  // ndcToScreen (GaussianShared.h:150-155)
+            sy = (ndc[1] + 1.0f) * 0.5f * P.height;
+            const M3 C3 = build_cov3d(scale, rot);
+            cov = project_cov2d(C3, vp, E.view, E.limX, E.limY, E.focalX, E.focalY);
+            cov = stabilize_cov2d(cov, P.maxEig);
+            if (!theta_sigmas(cov, &theta, &s1, &s2)) ok = false;
+        }
+        if (ok && 3.0f * __builtin_fmaxf(s1, s2) < 0.5f) ok = false;  // cullByRadius
+        if (ok) {  // cullByTotalInkFromCov (GaussianShared.h:753-768), threshold 2.0
+            const float a = cov.a, b = 0.5f * (cov.b + cov.c), d = cov.d;
+            const float ink = opacity * 6.283185f * sqrt_cr(__builtin_fmaxf(a * d - b * b, 1e-12f));
+            const float s = clampf((P.adjFar - depth) / P.adjDen, 0.0f, 1.0f);
+            const float depthFactor = 1.0f - s * s;
+            if (ink < depthFactor * 2.0f) ok = false;
+        }
+        float ex = 0.0f, ey = 0.0f;
+        if (ok) {
+            obb_extents(cov, &ex, &ey);
+            // cullByScreenBounds (GaussianShared.h:771-781)
+            if (sx + ex < 0.0f || sx - ex > P.width || sy + ey < 0.0f || sy - ey > P.height) ok = false;
+        }
+        if (ok) {
+            float col[3];
+            sh_color<HALF, DEG>(harm, gid, pos, P.mid, P.shComponents, col);
+            col[0] = __builtin_fmaxf(col[0] + 0.5f, 0.0f);
+            col[1] = __builtin_fmaxf(col[1] + 0.5f, 0.0f);
+            col[2] = __builtin_fmaxf(col[2] + 0.5f, 0.0f);
+            if (P.inputIsSRGB > 0.5f) {
+                col[0] = srgb_to_linear(col[0]);
+                col[1] = srgb_to_linear(col[1]);
+                col[2] = srgb_to_linear(col[2]);
+            }
+            // GaussianRenderData (:143-154), packThetaPi (GaussianShared.h:434-440)
+            float th = fmod_pi(theta);
+            if (th < 0.0f) th = th + kPiF;
+            const uint16_t thq = (uint16_t)clampf(th * (65535.0f / kPiF) + 0.5f, 0.0f, 65535.0f);
+            const uint32_t cR = (uint32_t)(uint8_t)clampf(col[0] * 255.0f, 0.0f, 255.0f);
+            const uint32_t cG = (uint32_t)(uint8_t)clampf(col[1] * 255.0f, 0.0f, 255.0f);
+            const uint32_t cB = (uint32_t)(uint8_t)clampf(col[2] * 255.0f, 0.0f, 255.0f);
+            const uint32_t cO = (uint32_t)(uint8_t)clampf(opacity * 255.0f, 0.0f, 255.0f);
+            rdw.x = (uint32_t)f_to_hbits(sx) | ((uint32_t)f_to_hbits(sy) << 16);
+            rdw.y = (uint32_t)thq | ((uint32_t)f_to_hbits(s1) << 16);
+            rdw.z = (uint32_t)f_to_hbits(s2) | ((uint32_t)f_to_hbits(depth) << 16);
+            rdw.w = cR | (cG << 8) | (cB << 16) | (cO << 24);
+            // computeTileBounds (GaussianShared.h:791-828) on 16x16 tiles
+            const float maxW = P.width - 1.0f, maxH = P.height - 1.0f;
+            const float xmin = clampf(sx - ex, 0.0f, maxW), xmax = clampf(sx + ex, 0.0f, maxW);
+            const float ymin = clampf(sy - ey, 0.0f, maxH), ymax = clampf(sy + ey, 0.0f, maxH);
+            const int minTX = (int)__builtin_floorf(xmin * (1.0f / 16.0f));
+            const int maxTX = (int)__builtin_ceilf(xmax * (1.0f / 16.0f)) - 1;
+            const int minTY = (int)__builtin_floorf(ymin * (1.0f / 16.0f));
+            const int maxTY = (int)__builtin_ceilf(ymax * (1.0f / 16.0f)) - 1;
+            tb = make_short4((short)max(minTX, 0), (short)min(maxTX, (int)P.tilesX - 1), (short)max(minTY, 0),
+                             (short)min(maxTY, (int)P.tilesY - 1));
+        }
+    }
+    // the per-tile test on the quantised record (:166-205), large rects spread over the wave
+    MonoTileTest T = {};
+    if (ok) T = mono_tile_setup(sincos, rdw);
+    const uint32_t touched = mono_rect_tiles(T, tb, ok, [](int, int, uint32_t, uint32_t) {});
+    if (gid < P.count) {
+        if (touched > 0) {
+            outRD[gid] = rdw;
+            outBounds[gid] = tb;
+            touchedOut[gid] = touched;
+            depthKeys[gid] = df_sortable(depth);
+        } else {
+            // (the reference leaves preDepthKeys unwritten on three of its early returns, :111-122
+            // and :133-137; they are 0xFFFFFFFF here, include/gsm_depthfirst.h)
+            outBounds[gid] = make_short4(0, -1, 0, -1);
+            touchedOut[gid] = 0;
+            depthKeys[gid] = 0xFFFFFFFFu;
+        }
+    }
+    const uint32_t s = block_reduce_add<kDfBlock>(touched > 0 ? 1u : 0u, lds);
+    if (threadIdx.x == 0) blockSums[blockIdx.x] = s;
+}
+
+// ---------------------------------------------------------------------------
+// M2. createInstancesKernel (DepthFirstShaders.metal:642-716): gaussian i of the depth order writes
+// its passing tiles, ty-major and tx-minor, from its exclusive offset while below maxInstances.
+// The offset of a tile inside its gaussian is the number of passing tiles before it: a lane's own
+// counter for small rects, the wave's ballot and popcount for large ones (mono_rect_tiles).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kDfBlock) void k_df_expand_mono(const TileAssignmentHeader* __restrict__ visHdr,
+                                                             const uint32_t* __restrict__ order,
+                                                             const uint32_t* __restrict__ touched,
+                                                             const short4* __restrict__ bounds,
+                                                             const uint32_t* __restrict__ blockOffsets,
+                                                             const uint4* __restrict__ rd,
+                                                             const float2* __restrict__ sincos,
+                                                             uint32_t maxInstances, uint32_t tilesX,
+                                                             uint32_t* __restrict__ tiles, uint32_t* __restrict__ gids) {
+    __shared__ uint32_t lds[kDfBlock / 64];
+    __shared__ uint32_t sOff[kDfBlock];
+    __shared__ uint32_t sG[kDfBlock];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t i = blockIdx.x * kDfBlock + tid;
+    const uint32_t V = visHdr->totalAssignments;
+    const bool valid = i < V;
+    const uint32_t g = valid ? order[i] : 0u;
+    const uint32_t c = valid ? touched[g] : 0u;
+    uint32_t total;
+    const uint32_t off = block_exclusive_scan<kDfBlock>(c, lds, &total);
+    sOff[tid] = off;
+    sG[tid] = g;
+    __syncthreads();
+    if (total == 0) return;  // (block-uniform)
+    const uint64_t base = (uint64_t)blockOffsets[blockIdx.x];
+    if (base >= maxInstances) return;  // every instance of this block is past the capacity
+    short4 r = make_short4(0, -1, 0, -1);
+    MonoTileTest T = {};
+    if (c > 0) {
+        r = bounds[g];
+        T = mono_tile_setup(sincos, rd[g]);
+    }
+    const uint32_t waveBase = tid & ~63u;
+    mono_rect_tiles(T, r, c > 0, [&](int tx, int ty, uint32_t k, uint32_t owner) {
+        const uint64_t wp = base + sOff[waveBase + owner] + k;
+        if (wp < maxInstances) {
+            tiles[wp] = (uint32_t)(ty * (int)tilesX + tx) & 0xFFFFu;  // ushort tile id
+            gids[wp] = sG[waveBase + owner];
+        }
+    });
+}
+
+// ---------------------------------------------------------------------------
+// M3. clear (DepthFirstShaders.metal:2020-2034) + depthFirstRender (:1703-1811)
+//
+// Persistent workgroups, one per CU: the 128 KiB Global alpha table (blend_exp_table_entry, no r^2
+// cutoff) sits in LDS and the waves pull tiles from a device counter.  One wave per 16x16 tile; a
+// lane is one reference thread, a 2x2 pixel group held as packed fp16 pairs (row 0 = {x, x+1},
+// row 1).  Lane l stages record l of the 64-entry batch -- the per-entry values of :1753-1764 (conic
+// of the quantised angle, fp16 c/255 colour and opacity) computed once per (tile, entry) -- and
+// every entry is read back as a uniform-address broadcast.  The reference's control flow is applied
+// as data, as in k_df_blend_eye: a lane whose max transmittance fell below 1/255 (the break, :1746)
+// or whose four alphas are all zero (:1781) keeps C, D and T (alpha 0 would leave the same bits:
+// C + c * (0 * T) = C, T * (1 - 0) = T; the update is masked so a non-finite depth cannot turn
+// 0 * depth into NaN where the reference skipped), a dead lane stays dead (T never grows), and the
+// wave leaves the list once every lane is dead.  `idx < 0` (:1750) cannot occur: ids are < 2^30.
+// A tile without instances is not an active tile and gets the clear value: colour (0, 0, 0, 1),
+// depth 0.  Writes are direct (no row flip), bounds-checked for ragged sizes.
+// ---------------------------------------------------------------------------
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void k_df_blend_mono(const uint32_t* __restrict__ starts,
+                                                           const uint32_t* __restrict__ gids,
+                                                           const uint4* __restrict__ rd,
+                                                           const float2* __restrict__ sincos,
+                                                           const uint16_t* __restrict__ expTable,
+                                                           uint32_t* __restrict__ queue, uint32_t tilesX,
+                                                           uint32_t tileCount, uint32_t W, uint32_t H,
+                                                           uint8_t* __restrict__ color, size_t pitch, int fmt,
+                                                           uint8_t* __restrict__ depthOut, size_t depthPitch) {
+    __shared__ __attribute__((aligned(16))) uint16_t tbl[65536];
+    __shared__ __attribute__((aligned(16))) uint4 stageA[NW][kDfEyeBatch];
+    __shared__ __attribute__((aligned(16))) uint32_t stageB[NW][kDfEyeBatch];
+    __shared__ uint16_t div255[256];
+    {
+        const uint4* src = (const uint4*)expTable;
+        uint4* dst = (uint4*)tbl;
+        for (int i = threadIdx.x; i < 65536 * 2 / 16; i += NW * 64) dst[i] = src[i];
+        if (threadIdx.x < 256) div255[threadIdx.x] = f_to_hbits((float)threadIdx.x / 255.0f);  // getColor
+    }
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t thrBits = (uint32_t)f_to_hbits(1.0f / 255.0f);  // half(1.0h / 255.0h)
+    const uint32_t bpp = fmt == GSM_COLOR_FORMAT_RGBA16F ? 8u : (fmt == GSM_COLOR_FORMAT_RGBA32F ? 16u : 4u);
+    const h2 ONE = {(h1)1.0f, (h1)1.0f};
+    const h1 c099 = (h1)0.99;
+    const h2 C099 = {c099, c099};
+    uint4* sA = stageA[wave];
+    uint32_t* sB = stageB[wave];
+    const uint32_t stripes = (gridDim.x % kQueueStripes) == 0 ? kQueueStripes : 1u;
+    const uint32_t stripe = blockIdx.x % stripes;
+    uint32_t qi = blockIdx.x * NW + wave;  // first tile static, then the queue
+    while (qi < tileCount) {
+        const uint32_t t = qi;
+        const uint32_t st0 = starts[t];
+        const uint32_t cnt = starts[t + 1] - st0;
+        const uint32_t tileX = t % tilesX, tileY = t / tilesX;
+        const uint32_t bx = tileX * kDfTile + (lane & 7u) * 2u, by = tileY * kDfTile + (lane >> 3) * 2u;
+        const h2 PX = {(h1)(float)bx, (h1)(float)(bx + 1u)};
+        const h2 PY = {(h1)(float)by, (h1)(float)(by + 1u)};
+        DfEyeState E;
+        E.T[0] = E.T[1] = ONE;
+        E.Cr[0] = E.Cr[1] = E.Cg[0] = E.Cg[1] = E.Cb[0] = E.Cb[1] = df_h2(0u);
+        h2 D[2] = {df_h2(0u), df_h2(0u)};
+        bool alive = true;  // the lane's max T >= 1/255
+        bool done = false;
+        const uint32_t* lst = gids + st0;
+        for (uint32_t b0 = 0; b0 < cnt && !done; b0 += kDfEyeBatch) {
+            const uint32_t n = min(kDfEyeBatch, cnt - b0);
+            if (lane < n) {
+                const uint4 r = rd[lst[b0 + lane] & kDfGidMask];
+                // conicFromThetaSigmas of the unpacked angle, half(cxx), half(cyy), half(2 cxy) (:1753-1759)
+                const Conic k = conic_from_quant(sincos, (uint16_t)(r.y & 0xFFFFu), hbits_to_f((uint16_t)(r.y >> 16)),
+                                                 hbits_to_f((uint16_t)(r.z & 0xFFFFu)));
+                const uint32_t cw = r.w;  // colorR, G, B, opacity
+                sA[lane] = make_uint4(r.x, (uint32_t)f_to_hbits(k.A) | ((uint32_t)f_to_hbits(k.C) << 16),
+                                      (uint32_t)f_to_hbits(2.0f * k.B) | ((uint32_t)div255[cw >> 24] << 16),
+                                      (uint32_t)div255[cw & 0xFFu] | ((uint32_t)div255[(cw >> 8) & 0xFFu] << 16));
+                sB[lane] = (uint32_t)div255[(cw >> 16) & 0xFFu] | (r.z & 0xFFFF0000u);  // b, depth
+            }
+            df_wave_sync();
+            for (uint32_t j = 0; j < n; ++j) {
+                const uint4 ra = sA[j];
+                const uint32_t rb = sB[j];
+                h2 p0, p1;
+                df_quadform(df_h2(ra.x), df_h2(ra.y), df_h2(ra.z), PX, PY, p0, p1);
+                const uint32_t b0w = df_u32(p0), b1w = df_u32(p1);
+                df_u16x2 e0, e1;
+                e0.x = tbl[b0w & 0xFFFFu];
+                e0.y = tbl[b0w >> 16];
+                e1.x = tbl[b1w & 0xFFFFu];
+                e1.y = tbl[b1w >> 16];
+                const h2 op = df_hi(df_h2(ra.z));
+                const h2 a0 = __builtin_elementwise_min(op * __builtin_bit_cast(h2, e0), C099);
+                const h2 a1 = __builtin_elementwise_min(op * __builtin_bit_cast(h2, e1), C099);
+                // all(alphas == 0.0h) (:1781): +0 or -0 in every half
+                const bool anyAlpha = ((df_u32(a0) | df_u32(a1)) & 0x7FFF7FFFu) != 0u;
+                if (alive && anyAlpha) {
+                    const h2 w0 = a0 * E.T[0], w1 = a1 * E.T[1];
+                    const h2 cr = df_lo(df_h2(ra.w)), cg = df_hi(df_h2(ra.w)), cb = df_lo(df_h2(rb));
+                    const h2 dep = df_hi(df_h2(rb));
+                    E.Cr[0] = df_acc(E.Cr[0], cr, w0);
+                    E.Cr[1] = df_acc(E.Cr[1], cr, w1);
+                    E.Cg[0] = df_acc(E.Cg[0], cg, w0);
+                    E.Cg[1] = df_acc(E.Cg[1], cg, w1);
+                    E.Cb[0] = df_acc(E.Cb[0], cb, w0);
+                    E.Cb[1] = df_acc(E.Cb[1], cb, w1);
+                    D[0] = df_acc(D[0], dep, w0);
+                    D[1] = df_acc(D[1], dep, w1);
+                    E.T[0] = E.T[0] * (ONE - a0);
+                    E.T[1] = E.T[1] * (ONE - a1);
+                    alive = df_alive(E, thrBits);
+                }
+                if (__builtin_amdgcn_ballot_w64(alive) == 0) {
+                    done = true;
+                    break;
+                }
+            }
+            df_wave_sync();  // the stage is rewritten by the next batch
+        }
+        uint32_t nq = 0;
+        if (lane == 0) nq = atomicAdd(queue + stripe * kQueueStride, 1u);
+        qi = gridDim.x * NW + stripe + stripes * __builtin_amdgcn_readfirstlane(nq);
+        const uint32_t clearA = cnt == 0 ? 0x3C003C00u : 0u;
+#pragma unroll
+        for (int row = 0; row < 2; ++row) {
+            const uint32_t y = by + (uint32_t)row;
+            if (y >= H) continue;
+            uint8_t* trow = color + (size_t)y * pitch;
+            const uint32_t ur = df_u32(E.Cr[row]), ug = df_u32(E.Cg[row]);
+            const uint32_t ub = df_u32(E.Cb[row]), ua = df_u32(ONE - E.T[row]) | clearA;
+            const uint32_t ud = df_u32(D[row]);
+            if (bx < W) {
+                store_color_px(fmt, (char*)(trow + (size_t)bx * bpp), (ur & 0xFFFFu) | (ug << 16),
+                               (ub & 0xFFFFu) | (ua << 16));
+                if (depthOut) *(uint16_t*)(depthOut + (size_t)y * depthPitch + (size_t)bx * 2u) = (uint16_t)(ud & 0xFFFFu);
+            }
+            if (bx + 1u < W) {
+                store_color_px(fmt, (char*)(trow + (size_t)(bx + 1u) * bpp), (ur >> 16) | (ug & 0xFFFF0000u),
+                               (ub >> 16) | (ua & 0xFFFF0000u));
+                if (depthOut) *(uint16_t*)(depthOut + (size_t)y * depthPitch + (size_t)(bx + 1u) * 2u) = (uint16_t)(ud >> 16);
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
+template <bool HALF>
+static void df_launch_project_mono_t(uint32_t deg, const void* world, const void* harm, const DfArgs& a,
+                                     const DfArena& A, hipStream_t s) {
+    const uint32_t blocks = (a.count + kDfBlock - 1) / kDfBlock;
+    if (blocks == 0) return;
+#define GSM_DF_PROJ_MONO(D)                                                                               \
+    hipLaunchKernelGGL((k_df_project_mono<HALF, D>), dim3(blocks), dim3(kDfBlock), 0, s, world, harm, a,  \
+                       A.sincos, (uint4*)A.renderData, A.bounds, A.touched, A.depthKeys, A.blockSums)
+    switch (deg) {
+        case 0: GSM_DF_PROJ_MONO(0); break;
+        case 1: GSM_DF_PROJ_MONO(1); break;
+        case 2: GSM_DF_PROJ_MONO(2); break;
+        default: GSM_DF_PROJ_MONO(3); break;
+    }
+#undef GSM_DF_PROJ_MONO
+}
+
+void df_launch_project_mono(bool halfInput, uint32_t deg, const void* world, const void* harm, const DfArgs& a,
+                            const DfArena& A, hipStream_t s) {
+    if (halfInput) df_launch_project_mono_t<true>(deg, world, harm, a, A, s);
+    else df_launch_project_mono_t<false>(deg, world, harm, a, A, s);
+}
+
+void df_launch_instances_mono(const uint32_t* order, const DfArgs& a, const DfArena& A, hipStream_t s) {
+    const uint32_t blocks = (a.count + kDfBlock - 1) / kDfBlock;
+    if (blocks == 0) return;
+    hipLaunchKernelGGL(k_df_expand_mono, dim3(blocks), dim3(kDfBlock), 0, s, A.visHdr, order, A.touched, A.bounds,
+                       A.instSums, (const uint4*)A.renderData, A.sincos, a.maxInstances, a.tilesX, A.ikeys[0],
+                       A.ivals[0]);
+}
+
+constexpr int kDfMonoBlendWaves = 16;
+void df_launch_blend_mono(const uint32_t* sortedGids, const DfArgs& a, const DfArena& A, void* color, size_t pitch,
+                          int colorFormat, void* depth, size_t depthPitch, int numCUs, hipStream_t s) {
+    uint32_t grid = (uint32_t)(numCUs > 0 ? numCUs : 256);
+    const uint32_t need = (a.tileCount + kDfMonoBlendWaves - 1) / kDfMonoBlendWaves;
+    if (grid > need) grid = need;
+    if (grid == 0) return;
+    hipLaunchKernelGGL((k_df_blend_mono<kDfMonoBlendWaves>), dim3(grid), dim3(kDfMonoBlendWaves * 64), 0, s,
+                       A.starts, sortedGids, (const uint4*)A.renderData, A.sincos, A.expTableMono, A.queue,
+                       a.tilesX, a.tileCount, (uint32_t)a.width, (uint32_t)a.height, (uint8_t*)color, pitch,
+                       colorFormat, (uint8_t*)depth, depthPitch);
+}
+
 template <bool HALF>
 static void df_launch_project_t(uint32_t deg, const void* world, const void* harm, const DfArgs& a,
                                 const DfArena& A, hipStream_t s) {

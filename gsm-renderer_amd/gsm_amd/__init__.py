@@ -229,6 +229,8 @@ _SIGNATURES = {
     "gsm_depthfirst_render_stereo_sbs": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera),
                                           C.POINTER(_Camera), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                           C.c_size_t], C.c_int),
+    "gsm_depthfirst_render": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera), C.c_uint32,
+                               C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t], C.c_int),
     "gsm_depthfirst_debug_counters": ([C.c_void_p, C.POINTER(_DfCounters)], C.c_int),
     "gsm_depthfirst_debug_copy": ([C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
                                   C.c_int),
@@ -541,9 +543,9 @@ STEREO_RENDER_DATA = np.dtype([(f, "<u2") for f in (
 
 
 class DepthFirstRenderer:
-    """DepthFirstRenderer (DepthFirstRenderer.swift:11-831) on one HIP device: the stereo
-    side-by-side path (renderStereo(target: .sideBySide), :205-223, 469-512).  The mono
-    render/renderStereo(.foveated) entry points of the reference are out of scope."""
+    """DepthFirstRenderer (DepthFirstRenderer.swift:11-831) on one HIP device: the mono frame
+    (render, :166-203, 237-465) and the stereo side-by-side path (renderStereo(target:
+    .sideBySide), :205-223, 469-512).  renderStereo(.foveated) is out of scope."""
 
     def __init__(self, device: Optional[int] = None, config: RendererConfig = RendererConfig()):
         L = _lib()
@@ -557,11 +559,29 @@ class DepthFirstRenderer:
         self._h = h
         self.device = dev
         self._bpp = ColorFormat(int(config.color_format)).bytes_per_pixel
+        self._last_mono = False  # the last frame was a mono frame (copy_buffer's record dtype)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             _lib().gsm_depthfirst_destroy(self._h)
             self._h = C.c_void_p()
+
+    # -- DepthFirstRenderer.render (DepthFirstRenderer.swift:166-203) --
+    def render(self, color_texture, depth_texture, input: GaussianInput, camera: CameraParams,
+               width: int, height: int, stream=None, color_pitch: Optional[int] = None,
+               depth_pitch: Optional[int] = None):
+        """The mono frame into color_texture ([height, width] of the config's colour format) and
+        depth_texture ([height, width] fp16, or None: no depth is written)."""
+        inp = _Input(_ptr(input.gaussians), _ptr(input.harmonics), int(input.gaussian_count),
+                     int(input.sh_components))
+        cam = _camera_struct(camera)
+        cp = color_pitch if color_pitch is not None else int(width) * self._bpp
+        dp = depth_pitch if depth_pitch is not None else int(width) * 2
+        st = _lib().gsm_depthfirst_render(self._h, _stream_handle(stream), C.byref(inp), C.byref(cam),
+                                          int(width), int(height), _ptr(color_texture), cp,
+                                          _ptr(depth_texture), dp)
+        _check(st, "gsm_depthfirst_render")
+        self._last_mono = True
 
     def __del__(self):  # pragma: no cover
         try:
@@ -585,6 +605,7 @@ class DepthFirstRenderer:
                                                      C.byref(cr), st_arr, int(width_per_eye), int(height),
                                                      _ptr(color_texture), cp)
         _check(st, "gsm_depthfirst_render_stereo_sbs")
+        self._last_mono = False
 
     @property
     def last_gpu_time(self) -> Optional[float]:
@@ -617,8 +638,8 @@ class DepthFirstRenderer:
         if n:
             _check(L.gsm_depthfirst_debug_copy(self._h, int(which), raw.ctypes.data, n, None), "debug_copy")
         raw = raw[:n]
-        if which == DepthFirstBuffer.RENDER_DATA:
-            return raw.view(STEREO_RENDER_DATA)
+        if which == DepthFirstBuffer.RENDER_DATA:  # 16-byte records after a mono frame
+            return raw.view(RENDER_DATA if self._last_mono else STEREO_RENDER_DATA)
         if which == DepthFirstBuffer.BOUNDS:
             return raw.view(np.int32).reshape(-1, 4)
         if which == DepthFirstBuffer.HEADERS:

@@ -52,7 +52,36 @@ gsm_status gsm_depthfirst_render_stereo_sbs(gsm_depthfirst *renderer, void *stre
                                             const float *scene_transform, uint32_t width, uint32_t height,
                                             void *color, size_t color_pitch_bytes);
 
-/* DepthFirstHeader (BridgingTypes.h:209-219) + frame counters of the last frame. */
+/* render(commandBuffer:colorTexture:depthTexture:input:camera:width:height:)
+ * (DepthFirstRenderer.swift:166-203, 237-465): the mono frame, the only DepthFirst path that writes a
+ * depth target.  Enqueue-only on `stream`, on the same handle as the stereo entry; either may be
+ * called on any frame.  It is not "stereo with two equal eyes":
+ *   - the projection writes the 16-byte GaussianRenderData (depthFirstProjectCullKernel,
+ *     DepthFirstShaders.metal:46-219): ndcToScreen without the half-pixel shift, far-plane cull,
+ *     SH colour from camera->position;
+ *   - a tile of the gaussian's 16x16-tile rect counts only when minQuadRect(tile) <=
+ *     computeD2Cutoff(opacity, 0.005) on the quantised record (:166-216, GaussianShared.h:525-593),
+ *     and the instance expansion writes only those tiles (:642-716);
+ *   - one wave per 16x16 tile blends 2x2 pixels per lane with the Global blend's per-entry
+ *     arithmetic, no r^2 cutoff, and accumulates depth (:1703-1811); no row flip;
+ *   - tiles without instances get the clear value: colour (0, 0, 0, 1), depth 0 (:2020-2034).
+ * Binning parameters are the reference's (GlobalRenderer.swift:54-69): alpha threshold 0.005,
+ * total-ink threshold 2.0, 16x16 tiles; capacity 4 * max_gaussians instances, instances past it are
+ * dropped from the tail of the depth order and `overflow` is set, as in the stereo frame.
+ * color: width x height pixels of config.color_format, rows color_pitch_bytes apart (4-byte
+ * aligned).  depth_r16f: width x height fp16, rows depth_pitch_bytes apart (2-byte aligned), or
+ * NULL: then no depth is written.
+ * Returns an error where the reference silently returns (:249): gaussian_count 0 or above
+ * max_gaussians -> GSM_ERR_INVALID_GAUSSIAN_COUNT; width or height 0 or above the configured maximum
+ * -> GSM_ERR_INVALID_DIMENSIONS; null colour (or input buffers) -> GSM_ERR_MISSING_REQUIRED_BUFFER;
+ * a pitch below a row or misaligned -> GSM_ERR_INVALID_BUFFER_SIZE. */
+gsm_status gsm_depthfirst_render(gsm_depthfirst *renderer, void *stream,
+                                 const gsm_gaussian_input *input, const gsm_camera_params *camera,
+                                 uint32_t width, uint32_t height,
+                                 void *color, size_t color_pitch_bytes,
+                                 void *depth_r16f, size_t depth_pitch_bytes);
+
+/* DepthFirstHeader (BridgingTypes.h:209-219) + frame counters of the last frame, whichever kind. */
 typedef struct {
     uint32_t gaussian_count;
     uint32_t visible;         /* visibleCount after compaction */
@@ -62,7 +91,15 @@ typedef struct {
     uint32_t tiles_x, tiles_y, tile_count;
 } gsm_depthfirst_counters;
 
-/* Buffers of the last frame that can be copied back (reference resource in brackets). */
+/* Buffers of the last frame that can be copied back (reference resource in brackets).  The
+ * comments describe a stereo frame.  After a mono frame (gsm_depthfirst_render):
+ *   RENDER_DATA is GaussianRenderData[count], 16 B (BridgingTypes.h:75-84); culled entries undefined;
+ *   BOUNDS is the mono tile rect, (0, -1, 0, -1) for a gaussian with no passing tile;
+ *   TOUCHED is the number of tiles of that rect that passed the per-tile test;
+ *   DEPTH_KEYS is float_to_sortable_uint(clip w); the reference leaves preDepthKeys unwritten on three
+ *     of its early returns (DepthFirstShaders.metal:111-122, :133-137) -- every gaussian without a
+ *     passing tile has 0xFFFFFFFF here;
+ *   the others are as for a stereo frame. */
 typedef enum {
     GSM_DF_BUF_RENDER_DATA = 0,      /* StereoTiledRenderData[count], 32 B [renderData]; culled entries undefined */
     GSM_DF_BUF_BOUNDS = 1,           /* int32[count][4] union tile rect [bounds] */

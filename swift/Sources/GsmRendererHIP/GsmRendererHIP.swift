@@ -297,7 +297,7 @@ public final class GlobalRenderer: GaussianRenderer {
     public func debugReadTotalAssignments() -> Int { Int(gsm_global_debug_read_total_assignments(handle)) }
 }
 
-/// DepthFirstRenderer's side-by-side stereo path (DepthFirstRenderer.swift:205-223).
+/// DepthFirstRenderer's mono frame (DepthFirstRenderer.swift:166-203) and side-by-side stereo path (:205-223).
 public final class DepthFirstRenderer: GaussianRenderer {
     private var handle: OpaquePointer?
     public let device: Int32
@@ -318,10 +318,15 @@ public final class DepthFirstRenderer: GaussianRenderer {
         return gsm_depthfirst_last_gpu_time(handle, &s) == GSM_OK ? s : nil
     }
 
-    /// Mono rendering of the DepthFirst renderer is outside this build's scope (DESIGN.md 9).
+    /// The mono frame (DepthFirstRenderer.swift:166-203), gsm_depthfirst_render; a nil depth texture
+    /// writes no depth.  Where the reference silently returns (:249) the status is kept in `lastError`.
     public func render(commandBuffer: HIPStream, colorTexture: HIPTexture, depthTexture: HIPTexture?,
                        input: GaussianInput, camera: CameraParams, width: Int, height: Int) {
-        lastError = .unsupported
+        var inp = inputStruct(input)
+        var cam = camera.c
+        lastError = RendererError(status: gsm_depthfirst_render(
+            handle, commandBuffer.handle, &inp, &cam, UInt32(width), UInt32(height), colorTexture.pointer,
+            colorTexture.pitch, depthTexture?.pointer, depthTexture?.pitch ?? 0))
     }
 
     public func renderStereo(commandBuffer: HIPStream, target: StereoRenderTarget, input: GaussianInput,
