@@ -23,7 +23,7 @@ try:  # load torch's HIP runtime first so libgsm_amd.so binds to the same one
 except Exception:  # pragma: no cover - torch is always present in this image
     torch = None
 
-from .types import RENDER_DATA, WORLD16, WORLD32  # noqa: F401
+from .types import PROJECTED, RENDER_DATA, WORLD16, WORLD32  # noqa: F401
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # GSM_AMD_LIB: another in-tree build of the same library (A/B experiments, tools/); default lib/
@@ -185,6 +185,13 @@ class _DfCounters(C.Structure):
                 ("tiles_y", C.c_uint32), ("tile_count", C.c_uint32)]
 
 
+class _LocalCounters(C.Structure):
+    _fields_ = [("gaussian_count", C.c_uint32), ("visible", C.c_uint32), ("tiles_x", C.c_uint32),
+                ("tiles_y", C.c_uint32), ("tile_count", C.c_uint32), ("active_tiles", C.c_uint32),
+                ("total_entries", C.c_uint32), ("max_tile_count", C.c_uint32), ("max_per_tile", C.c_uint32),
+                ("overflow", C.c_uint32)]
+
+
 _LIB = None
 
 # every function include/gsm_renderer.h and include/gsm_debug.h declare, with ctypes signature
@@ -275,6 +282,21 @@ _SIGNATURES = {
     "gsm_multigpu_debug_set_epoch": ([C.c_void_p, C.c_uint32], C.c_int),
 }
 
+# every function include/gsm_local.h declares (the LocalRenderer frame)
+_LOCAL_SIGNATURES = {
+    "gsm_local_create": ([C.POINTER(_Config), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
+    "gsm_local_destroy": ([C.c_void_p], None),
+    "gsm_local_render": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera), C.c_uint32,
+                          C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t], C.c_int),
+    "gsm_local_debug_counters": ([C.c_void_p, C.POINTER(_LocalCounters)], C.c_int),
+    "gsm_local_debug_copy": ([C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)], C.c_int),
+    "gsm_local_debug_sort_tiles": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                    C.c_void_p], C.c_int),
+    "gsm_local_set_profiling": ([C.c_void_p, C.c_int], C.c_int),
+    "gsm_local_stage_times": ([C.c_void_p, C.POINTER(C.c_float), C.c_int], C.c_int),
+    "gsm_local_last_gpu_time": ([C.c_void_p, C.POINTER(C.c_double)], C.c_int),
+}
+
 SPLAT_RECORD_BYTES = 48  # include/gsm_multigpu.h GSM_SPLAT_RECORD_BYTES
 MAX_SLABS = 16
 MULTIGPU_HANDLE_BYTES = 256  # GSM_MULTIGPU_HANDLE_BYTES
@@ -288,7 +310,7 @@ def _lib():
         if not os.path.exists(LIB_PATH):
             raise ImportError(f"libgsm_amd.so not built: {LIB_PATH} (run `make -C gsm-renderer_amd`)")
         L = C.CDLL(LIB_PATH)
-        for name, (args, res) in _SIGNATURES.items():
+        for name, (args, res) in list(_SIGNATURES.items()) + list(_LOCAL_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.argtypes = args
             fn.restype = res
@@ -649,6 +671,103 @@ class DepthFirstRenderer:
         if which == DepthFirstBuffer.BLEND_STATS:
             return raw.view(np.uint64)
         return raw.view(np.uint32)
+
+
+class LocalBuffer(enum.IntEnum):  # include/gsm_local.h gsm_local_buffer
+    PROJECTED = 0
+    TILE_COUNTS = 1
+    TILE_LISTS = 2
+
+
+LOCAL_STAGES = ("project", "scatter", "sort", "blend")  # gsm_local_stage
+LOCAL_MAX_PER_TILE = 2048  # GSM_LOCAL_MAX_PER_TILE
+
+
+class LocalRenderer:
+    """LocalRenderer (LocalRenderer.swift:6-257) on one HIP device: per-tile slot lists sorted by a 16-bit
+    depth key, no global sort (include/gsm_local.h).  renderStereo is a fatalError in the reference."""
+
+    def __init__(self, device: Optional[int] = None, config: RendererConfig = RendererConfig()):
+        L = _lib()
+        self.config = config
+        cfg = _Config(int(config.max_gaussians), int(config.max_width), int(config.max_height),
+                      int(config.precision), int(config.color_format),
+                      int(config.gaussian_color_space), int(bool(config.back_to_front)))
+        h = C.c_void_p()
+        dev = -1 if device is None else int(device)
+        _check(L.gsm_local_create(C.byref(cfg), dev, C.byref(h)), "gsm_local_create")
+        self._h = h
+        self.device = dev
+        self._bpp = ColorFormat(int(config.color_format)).bytes_per_pixel
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            _lib().gsm_local_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # -- LocalRenderer.render (LocalRenderer.swift:83-106) --
+    def render(self, color_texture, depth_texture, input: GaussianInput, camera: CameraParams,
+               width: int, height: int, stream=None, color_pitch: Optional[int] = None,
+               depth_pitch: Optional[int] = None):
+        """One frame into color_texture ([height, width] of the config's colour format) and
+        depth_texture ([height, width] fp16, or None: no depth is written)."""
+        inp = _Input(_ptr(input.gaussians), _ptr(input.harmonics), int(input.gaussian_count),
+                     int(input.sh_components))
+        cam = _camera_struct(camera)
+        cp = color_pitch if color_pitch is not None else int(width) * self._bpp
+        dp = depth_pitch if depth_pitch is not None else int(width) * 2
+        st = _lib().gsm_local_render(self._h, _stream_handle(stream), C.byref(inp), C.byref(cam),
+                                     int(width), int(height), _ptr(color_texture), cp, _ptr(depth_texture), dp)
+        _check(st, "gsm_local_render")
+
+    @property
+    def last_gpu_time(self) -> Optional[float]:
+        s = C.c_double()
+        st = _lib().gsm_local_last_gpu_time(self._h, C.byref(s))
+        return float(s.value) if st == 0 else None
+
+    def set_profiling(self, stage_events: bool = True):
+        _check(_lib().gsm_local_set_profiling(self._h, 1 if stage_events else 0), "set_profiling")
+
+    def stage_times_ms(self) -> dict:
+        arr = (C.c_float * len(LOCAL_STAGES))()
+        _check(_lib().gsm_local_stage_times(self._h, arr, len(LOCAL_STAGES)), "gsm_local_stage_times")
+        return {k: float(v) for k, v in zip(LOCAL_STAGES, arr)}
+
+    def counters(self) -> dict:
+        c = _LocalCounters()
+        _check(_lib().gsm_local_debug_counters(self._h, C.byref(c)), "gsm_local_debug_counters")
+        return {name: int(getattr(c, name)) for name, _ in _LocalCounters._fields_}
+
+    def copy_buffer(self, which: LocalBuffer) -> np.ndarray:
+        L = _lib()
+        need = C.c_size_t()
+        _check(L.gsm_local_debug_copy(self._h, int(which), None, 0, C.byref(need)), "debug_copy")
+        n = int(need.value)
+        raw = np.zeros(max(n, 1), np.uint8)
+        if n:
+            _check(L.gsm_local_debug_copy(self._h, int(which), raw.ctypes.data, n, None), "debug_copy")
+        raw = raw[:n]
+        if which == LocalBuffer.PROJECTED:
+            return raw.view(PROJECTED)
+        if which == LocalBuffer.TILE_LISTS:
+            return raw.view(np.uint32).reshape(-1, LOCAL_MAX_PER_TILE)
+        return raw.view(np.uint32)
+
+    @staticmethod
+    def sort_tiles(keys16, indices, counts, max_per_tile: int, out_local_idx, stream=None):
+        """The per-tile sort stage alone on device buffers (torch int16 keys and output, int32 indices and
+        counts; tile t owns slots [t * max_per_tile, (t + 1) * max_per_tile)): out_local_idx receives each
+        tile's slots ascending by (key, index, slot)."""
+        _check(_lib().gsm_local_debug_sort_tiles(_stream_handle(stream), _ptr(keys16), _ptr(indices), _ptr(counts),
+                                                 int(counts.numel()), int(max_per_tile), _ptr(out_local_idx)),
+               "gsm_local_debug_sort_tiles")
 
 
 def sort_pairs_u32(keys, values, key_bits: int = 32, stream=None):

@@ -13,4 +13,11 @@ WORLD16 = np.dtype([("px", "<f4"), ("py", "<f4"), ("pz", "<f4"), ("opacity", "<u
 RENDER_DATA = np.dtype([("meanX", "<u2"), ("meanY", "<u2"), ("theta", "<u2"), ("sigma1", "<u2"),
                         ("sigma2", "<u2"), ("depth", "<u2"), ("colorR", "u1"), ("colorG", "u1"),
                         ("colorB", "u1"), ("opacity", "u1")])
+# BridgingTypes.h:106-114 ProjectedGaussian, 32 B (LocalRenderer; fp16 fields as raw bits; minTile
+# inclusive, maxTile exclusive)
+PROJECTED = np.dtype([(f, "<u2") for f in ("posX", "posY", "conicA", "conicB", "conicC", "depth", "colorR",
+                                            "colorG", "colorB", "opacity")] +
+                     [("minTile", "<u2", (2,)), ("maxTile", "<u2", (2,)), ("obbExtentX", "<u2"),
+                      ("obbExtentY", "<u2")])
 assert WORLD32.itemsize == 48 and WORLD16.itemsize == 32 and RENDER_DATA.itemsize == 16
+assert PROJECTED.itemsize == 32

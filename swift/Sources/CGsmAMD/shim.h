@@ -2,6 +2,7 @@
  * the few HIP runtime entry points the wrapper uses for device buffers and streams. */
 #include "../../../include/gsm_renderer.h"
 #include "../../../include/gsm_depthfirst.h"
+#include "../../../include/gsm_local.h"
 #include "../../../include/gsm_debug.h"
 #include "../../../include/gsm_multigpu.h"
 

@@ -4,7 +4,7 @@
 // GaussianInput :9-26, CameraParams :28-54, StereoCameraParams :56-66, RendererConfig :195-228,
 // StereoRenderTarget :233-239, protocol GaussianRenderer :243-272, RendererError :274-324) and the
 // classes GlobalRenderer (Sources/Renderer/GlobalRenderer/GlobalRenderer.swift:72-572) and
-// DepthFirstRenderer's side-by-side stereo path (DepthFirstRenderer.swift:205-223).  Metal types
+// DepthFirstRenderer's side-by-side stereo path (DepthFirstRenderer.swift:205-223), LocalRenderer (LocalRenderer.swift:83-106).  Metal types
 // become HIP ones: MTLBuffer -> HIPBuffer (device pointer + length), MTLTexture -> HIPTexture
 // (device pointer + pitch + pixel format), MTLCommandBuffer -> HIPStream (frames are enqueued on
 // the stream; the caller synchronises, as it commits a command buffer).  `simd_float4x4` (Apple
@@ -337,5 +337,44 @@ public final class DepthFirstRenderer: GaussianRenderer {
         lastError = RendererError(status: gsm_depthfirst_render_stereo_sbs(
             handle, commandBuffer.handle, &inp, &l, &r, nil, UInt32(width), UInt32(height), color.pointer,
             color.pitch))
+    }
+}
+
+/// LocalRenderer (LocalRenderer.swift:6-257): per-tile slot lists sorted by a 16-bit depth key, gsm_local_render.
+public final class LocalRenderer: GaussianRenderer {
+    private var handle: OpaquePointer?
+    public let device: Int32
+    public private(set) var lastError: RendererError?
+
+    public init(device: Int32 = -1, config: RendererConfig = RendererConfig()) throws {
+        var cfg = config.c
+        var h: OpaquePointer?
+        if let err = RendererError(status: gsm_local_create(&cfg, device, &h)) { throw err }
+        handle = h
+        self.device = device
+    }
+
+    deinit { gsm_local_destroy(handle) }
+
+    public var lastGPUTime: Double? {
+        var s = 0.0
+        return gsm_local_last_gpu_time(handle, &s) == GSM_OK ? s : nil
+    }
+
+    /// A nil depth texture writes no depth.  Where the reference silently returns (:139-141) the status is
+    /// kept in `lastError`.
+    public func render(commandBuffer: HIPStream, colorTexture: HIPTexture, depthTexture: HIPTexture?,
+                       input: GaussianInput, camera: CameraParams, width: Int, height: Int) {
+        var inp = inputStruct(input)
+        var cam = camera.c
+        lastError = RendererError(status: gsm_local_render(
+            handle, commandBuffer.handle, &inp, &cam, UInt32(width), UInt32(height), colorTexture.pointer,
+            colorTexture.pitch, depthTexture?.pointer, depthTexture?.pitch ?? 0))
+    }
+
+    /// LocalRenderer.renderStereo is a fatalError in the reference (:108-123); here it records UNSUPPORTED.
+    public func renderStereo(commandBuffer: HIPStream, target: StereoRenderTarget, input: GaussianInput,
+                             camera: StereoCameraParams, width: Int, height: Int) {
+        lastError = RendererError(status: GSM_ERR_UNSUPPORTED)
     }
 }
