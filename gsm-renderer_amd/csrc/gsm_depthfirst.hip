@@ -25,7 +25,9 @@ namespace gsm {
 
 class DepthFirstRenderer {
    public:
-    static gsm_status create(const gsm_renderer_config& cfg, int hipDevice, DepthFirstRenderer** out);
+    static gsm_status create(const gsm_renderer_config& cfg, int hipDevice, const gsm_depthfirst_options& opt,
+                             DepthFirstRenderer** out);
+    const gsm_depthfirst_options& options() const { return options_; }
     ~DepthFirstRenderer() { release(); }
     gsm_status renderStereoSbs(hipStream_t s, const gsm_gaussian_input& in, const gsm_camera_params& left,
                                const gsm_camera_params& right, const float* scene, uint32_t width, uint32_t height,
@@ -48,6 +50,11 @@ class DepthFirstRenderer {
     Tuning tuning_{};  // A/B switches, read once at create
     uint32_t maxGaussians_ = 1, maxWidth_ = 1, maxHeight_ = 1, maxInstances_ = 4;
     uint32_t maxTiles_ = 1;
+    gsm_depthfirst_options options_{};  // fixed at create
+    bool key16_ = false, tile32_ = false;
+    const uint32_t* sortedDepthKeys_ = nullptr;
+    int sortDepth(hipStream_t s);
+    int sortTiles(const DfArgs& a, hipStream_t s);
     DfArena A_;
     std::vector<void*> allocations_;
     // last frame
@@ -89,7 +96,8 @@ gsm_status DepthFirstRenderer::alloc(void** p, size_t bytes) {
     return GSM_OK;
 }
 
-gsm_status DepthFirstRenderer::create(const gsm_renderer_config& cfg, int hipDevice, DepthFirstRenderer** out) {
+gsm_status DepthFirstRenderer::create(const gsm_renderer_config& cfg, int hipDevice,
+                                      const gsm_depthfirst_options& opt, DepthFirstRenderer** out) {
     *out = nullptr;
     // DepthFirstRenderer.init guard (DepthFirstRenderer.swift:51-56)
     if (cfg.max_gaussians > kMaxSupportedGaussians) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
@@ -98,7 +106,15 @@ gsm_status DepthFirstRenderer::create(const gsm_renderer_config& cfg, int hipDev
     if (cfg.color_format > GSM_COLOR_FORMAT_BGRA8_UNORM_SRGB) return GSM_ERR_INVALID_ARGUMENT;
     const uint32_t maxW = cfg.max_width ? cfg.max_width : 1u, maxH = cfg.max_height ? cfg.max_height : 1u;
     const uint64_t tiles = (uint64_t)((maxW + kDfTile - 1) / kDfTile) * ((maxH + kDfTile - 1) / kDfTile);
-    if (tiles > 65535u) return GSM_ERR_INVALID_TILE_COUNT;  // 16-bit tile ids (DepthFirstResources.swift)
+    const bool tile32 = opt.tile_id_bits == 32u;
+    // 16-bit tile ids (DepthFirstResources.swift); 32-bit: the tile sort's two passes (radix_sort_tiles_wide)
+    static_assert((1u << kTilesWideMaxBits) == GSM_DF_MAX_TILES_32, "the header's limit is the tile sort's");
+    if (tiles > (tile32 ? (uint64_t)GSM_DF_MAX_TILES_32 : 65535u)) return GSM_ERR_INVALID_TILE_COUNT;
+    // tile rects are short4 (DfArena::bounds): a 32-bit grid may not exceed GSM_DF_MAX_TILES_AXIS per axis
+    // (with 16-bit ids the grid check is the reference's, unchanged)
+    if (tile32 && ((maxW + kDfTile - 1) / kDfTile > GSM_DF_MAX_TILES_AXIS ||
+                   (maxH + kDfTile - 1) / kDfTile > GSM_DF_MAX_TILES_AXIS))
+        return GSM_ERR_INVALID_TILE_COUNT;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         (void)hipGetLastError();
@@ -115,6 +131,9 @@ gsm_status DepthFirstRenderer::create(const gsm_renderer_config& cfg, int hipDev
     r->maxWidth_ = maxW;
     r->maxHeight_ = maxH;
     r->maxTiles_ = (uint32_t)tiles;
+    r->options_ = opt;
+    r->key16_ = opt.depth_key_bits == 16u;
+    r->tile32_ = tile32;
     const uint64_t cap64 = 4ull * r->maxGaussians_;  // DepthFirstResources.swift:399
     r->maxInstances_ = (uint32_t)(cap64 > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : cap64);
     hipDeviceProp_t prop;
@@ -160,7 +179,13 @@ gsm_status DepthFirstRenderer::create(const gsm_renderer_config& cfg, int hipDev
     GSM_DF_ALLOC(A.costMax, kCostMaxSlots * sizeof(uint32_t));
     GSM_DF_ALLOC(A.sincos, 65536 * sizeof(float2));
     GSM_DF_ALLOC(A.expTableMono, 65536 * 2);
+    if (tiles > 65536u) GSM_DF_ALLOC(A.tileBuckets, ((size_t)kWideBins + 1) * sizeof(uint32_t));
 #undef GSM_DF_ALLOC
+    // the sort plans the options add must fit the workspace now, not at the first frame
+    if (st == GSM_OK && r->key16_ && !sort_bits_plan_fits(r->maxGaussians_, 16, r->tuning_.wideSort, sort_space(A)))
+        st = GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;
+    if (st == GSM_OK && tiles > 65536u && !sort_tiles_wide_fits(r->maxInstances_, (uint32_t)tiles, sort_space(A)))
+        st = GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;
     if (st != GSM_OK) {
         delete r;
         return st;
@@ -186,6 +211,28 @@ gsm_status DepthFirstRenderer::create(const gsm_renderer_config& cfg, int hipDev
     }
     *out = r;
     return GSM_OK;
+}
+
+// DepthRadixSortEncoder (DepthFirstRenderer.swift:664-681): stable LSD over the compacted keys.
+// 32-bit keys: 3 wide passes of 11/11/10 bits unless GSM_SORT_WIDE=0; 16-bit keys (depth_key_bits 16):
+// the low 16 bits in 2 passes of 8 bits (DepthRadixSortEncoder.swift:13-24) -- the same stable order
+// with either switch.  Returns the ping-pong index of the result (or kSortNoSpace: nothing launched).
+int DepthFirstRenderer::sortDepth(hipStream_t s) {
+    return radix_sort_bits(A_.dkeys, A_.dvals, &A_.visHdr->totalAssignments, maxGaussians_, 0, key16_ ? 16u : 32u,
+                           sort_space(A_), s, tuning_.ballotRank, tuning_.wideSort, tuning_.sortScanless);
+}
+
+// TileSortEncoder (DepthFirstRenderer.swift:683-768): stable sort by the tile id; the last pass also
+// writes the tile ranges' starts (no pass over the instances).  A frame of more than 65,536 tiles (only
+// with tile_id_bits 32) takes the two passes of radix_sort_tiles_wide; every other frame, in either
+// mode, the 16-bit field's passes.
+int DepthFirstRenderer::sortTiles(const DfArgs& a, hipStream_t s) {
+    if (a.tileCount > 65536u)
+        return radix_sort_tiles_wide(A_.ikeys, A_.ivals, &A_.instHdr->totalAssignments, maxInstances_, sort_space(A_),
+                                     A_.starts, A_.tileBuckets, a.tileCount, s, tuning_.ballotRank);
+    return radix_sort_tiles(A_.ikeys, A_.ivals, &A_.instHdr->totalAssignments, maxInstances_, 0, sort_space(A_),
+                            A_.starts, 0u, a.tileCount, a.tileCount, s, tuning_.ballotRank, tuning_.wideSort,
+                            tuning_.sortScanless);
 }
 
 // per-eye projectCovariance2D terms, the same fp32 operations the reference repeats per gaussian
@@ -272,24 +319,16 @@ gsm_status DepthFirstRenderer::renderStereoSbs(hipStream_t s, const gsm_gaussian
     if (prof) hipEventRecord(ev[0], s);
     df_launch_project(half, deg, in.gaussians, in.harmonics, a, A_, s);
     launch_scan_sums(A_.blockSums, nb, maxGaussians_, A_.visHdr, A_.queue, s);
-    df_launch_compact(a, A_, s);
+    df_launch_compact(a, A_, s, key16_);
     if (prof) hipEventRecord(ev[1], s);
-    // DepthRadixSortEncoder, 32-bit keys (DepthFirstRenderer.swift:664-681): stable LSD
-    // (3 wide passes of 11/11/10 bits unless GSM_SORT_WIDE=0: the same stable order)
-    const int dc = radix_sort_bits(A_.dkeys, A_.dvals, &A_.visHdr->totalAssignments, maxGaussians_, 0, 32,
-                                   sort_space(A_), s, tuning_.ballotRank, tuning_.wideSort,
-                                   tuning_.sortScanless);
+    const int dc = sortDepth(s);
     if (dc == kSortNoSpace) return GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;  // (nothing of the sort launched)
     if (prof) hipEventRecord(ev[2], s);
     df_launch_instance_counts(A_.dvals[dc], a, A_, s);
     launch_scan_sums(A_.instSums, nb, maxInstances_, A_.instHdr, A_.queue, s);
-    df_launch_instances(A_.dvals[dc], a, A_, s);  // with the blend's skip flags
+    df_launch_instances(A_.dvals[dc], a, A_, s, tile32_);  // with the blend's skip flags
     if (prof) hipEventRecord(ev[3], s);
-    // TileSortEncoder (DepthFirstRenderer.swift:683-768): stable sort by the 16-bit tile id
-    // the last pass also writes the tile ranges' starts (radix_sort_tiles: no pass over the instances)
-    const int ic = radix_sort_tiles(A_.ikeys, A_.ivals, &A_.instHdr->totalAssignments, maxInstances_, 0, sort_space(A_),
-                                    A_.starts, 0u, a.tileCount, a.tileCount, s, tuning_.ballotRank,
-                                    tuning_.wideSort, tuning_.sortScanless);
+    const int ic = sortTiles(a, s);
     if (ic == kSortNoSpace) return GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;
     // Blend schedule: (tile, eye) units handed out longest first by the walk lengths the previous
     // frame of the same geometry measured (the image does not depend on the order, only the load
@@ -308,6 +347,7 @@ gsm_status DepthFirstRenderer::renderStereoSbs(hipStream_t s, const gsm_gaussian
     lastTilesY_ = a.tilesY;
     lastMono_ = false;
     depthOrder_ = A_.dvals[dc];
+    sortedDepthKeys_ = A_.dkeys[dc];
     instTiles_ = A_.ikeys[ic];
     instGids_ = A_.ivals[ic];
     if (hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;
@@ -370,20 +410,16 @@ gsm_status DepthFirstRenderer::renderMono(hipStream_t s, const gsm_gaussian_inpu
     if (prof) hipEventRecord(ev[0], s);
     df_launch_project_mono(half, deg, in.gaussians, in.harmonics, a, A_, s);
     launch_scan_sums(A_.blockSums, nb, maxGaussians_, A_.visHdr, A_.queue, s);
-    df_launch_compact(a, A_, s);
+    df_launch_compact(a, A_, s, key16_);
     if (prof) hipEventRecord(ev[1], s);
-    const int dc = radix_sort_bits(A_.dkeys, A_.dvals, &A_.visHdr->totalAssignments, maxGaussians_, 0, 32,
-                                   sort_space(A_), s, tuning_.ballotRank, tuning_.wideSort,
-                                   tuning_.sortScanless);
+    const int dc = sortDepth(s);
     if (dc == kSortNoSpace) return GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;
     if (prof) hipEventRecord(ev[2], s);
     df_launch_instance_counts(A_.dvals[dc], a, A_, s);
     launch_scan_sums(A_.instSums, nb, maxInstances_, A_.instHdr, A_.queue, s);
-    df_launch_instances_mono(A_.dvals[dc], a, A_, s);
+    df_launch_instances_mono(A_.dvals[dc], a, A_, s, tile32_);
     if (prof) hipEventRecord(ev[3], s);
-    const int ic = radix_sort_tiles(A_.ikeys, A_.ivals, &A_.instHdr->totalAssignments, maxInstances_, 0, sort_space(A_),
-                                    A_.starts, 0u, a.tileCount, a.tileCount, s, tuning_.ballotRank,
-                                    tuning_.wideSort, tuning_.sortScanless);
+    const int ic = sortTiles(a, s);
     if (ic == kSortNoSpace) return GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;
     if (prof || blendOnly) hipEventRecord(ev[4], s);
     df_launch_blend_mono(A_.ivals[ic], a, A_, color, pitch, fmt, depth, depthPitch, numCUs_, s);
@@ -396,6 +432,7 @@ gsm_status DepthFirstRenderer::renderMono(hipStream_t s, const gsm_gaussian_inpu
     lastTilesY_ = a.tilesY;
     lastMono_ = true;
     depthOrder_ = A_.dvals[dc];
+    sortedDepthKeys_ = A_.dkeys[dc];
     instTiles_ = A_.ikeys[ic];
     instGids_ = A_.ivals[ic];
     if (hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;
@@ -432,6 +469,7 @@ gsm_status DepthFirstRenderer::debugCopy(int which, void* dst, size_t bytes, siz
         case GSM_DF_BUF_TOUCHED: src = A_.touched; full = n * 4; break;
         case GSM_DF_BUF_DEPTH_KEYS: src = A_.depthKeys; full = n * 4; break;
         case GSM_DF_BUF_DEPTH_ORDER: src = depthOrder_; full = (size_t)c.visible * 4; break;
+        case GSM_DF_BUF_SORTED_DEPTH_KEYS: src = sortedDepthKeys_; full = (size_t)c.visible * 4; break;
         case GSM_DF_BUF_INSTANCE_TILES: src = instTiles_; full = (size_t)c.total_instances * 4; break;
         case GSM_DF_BUF_INSTANCE_GAUSSIANS: src = instGids_; full = (size_t)c.total_instances * 4; break;
         case GSM_DF_BUF_HEADERS: full = (size_t)c.tile_count * 8; break;
@@ -536,11 +574,39 @@ struct gsm_depthfirst {
 
 extern "C" {
 
+void gsm_depthfirst_default_options(gsm_depthfirst_options* out) {
+    if (!out) return;
+    out->struct_bytes = (uint32_t)sizeof(gsm_depthfirst_options);
+    out->depth_key_bits = 32;
+    out->tile_id_bits = 16;
+    out->reserved = 0;
+}
+
 gsm_status gsm_depthfirst_create(const gsm_renderer_config* config, int hip_device, gsm_depthfirst** out) {
+    return gsm_depthfirst_create_with_options(config, hip_device, nullptr, out);
+}
+
+gsm_status gsm_depthfirst_get_options(gsm_depthfirst* r, gsm_depthfirst_options* out) {
+    if (!r || !out) return GSM_ERR_INVALID_ARGUMENT;
+    *out = r->impl->options();
+    return GSM_OK;
+}
+
+gsm_status gsm_depthfirst_create_with_options(const gsm_renderer_config* config, int hip_device,
+                                              const gsm_depthfirst_options* options, gsm_depthfirst** out) {
     if (!config || !out) return GSM_ERR_INVALID_ARGUMENT;
     *out = nullptr;
+    gsm_depthfirst_options opt;
+    gsm_depthfirst_default_options(&opt);
+    if (options) {
+        if (options->struct_bytes != sizeof(gsm_depthfirst_options) || options->reserved != 0 ||
+            (options->depth_key_bits != 16u && options->depth_key_bits != 32u) ||
+            (options->tile_id_bits != 16u && options->tile_id_bits != 32u))
+            return GSM_ERR_INVALID_ARGUMENT;
+        opt = *options;
+    }
     gsm::DepthFirstRenderer* impl = nullptr;
-    gsm_status st = gsm::DepthFirstRenderer::create(*config, hip_device, &impl);
+    gsm_status st = gsm::DepthFirstRenderer::create(*config, hip_device, opt, &impl);
     if (st != GSM_OK) return st;
     gsm_depthfirst* h = new (std::nothrow) gsm_depthfirst;
     if (!h) {

@@ -52,6 +52,8 @@ struct DfArena {
     size_t radixHistBytes = 0;
     uint32_t* radixBinTotals = nullptr;
     uint32_t* starts = nullptr;                   // [tileCount + 1] first instance of each tile
+    uint32_t* tileBuckets = nullptr;              // [kWideBins + 1] grids above 65,536 tiles (tile_id_bits 32):
+                                                  // the starts of the tile sort's low-digit buckets
     uint32_t* queue = nullptr;                    // blend work counter
     uint16_t* expTable = nullptr;                 // [65536] stereo alpha table (r^2 cutoff folded)
     uint16_t* unitCost = nullptr;                 // [2 * maxTiles] entries each (tile, eye) unit walked
@@ -76,10 +78,13 @@ constexpr uint32_t kDfGidMask = (1u << kDfSkipShift) - 1u;
 void df_launch_project(bool halfInput, uint32_t shDegree, const void* world, const void* harmonics,
                        const DfArgs& a, const DfArena& A, hipStream_t stream);
 // visibilityScatterCompactKernel (:589-621): (depth key, id) of the visible gaussians, ascending id
-void df_launch_compact(const DfArgs& a, const DfArena& A, hipStream_t stream);
+// key16: the 16-bit depth key of depth_key_bits 16 (DF_DEPTH_KEY_16, :606-611) in the key's low half
+void df_launch_compact(const DfArgs& a, const DfArena& A, hipStream_t stream, bool key16 = false);
 // applyDepthOrderingKernel + instance prefix sum + createInstancesStereoKernel (:623-640, :790-826)
 void df_launch_instance_counts(const uint32_t* order, const DfArgs& a, const DfArena& A, hipStream_t stream);
-void df_launch_instances(const uint32_t* order, const DfArgs& a, const DfArena& A, hipStream_t stream);
+// tile32: whole tile ids (tile_id_bits 32) instead of the reference's ushort truncation
+void df_launch_instances(const uint32_t* order, const DfArgs& a, const DfArena& A, hipStream_t stream,
+                         bool tile32 = false);
 // extractTileRangesKernel (:1258-1313)
 // clearStereoRenderTextureKernel + depthFirstStereoRender + DepthFirstStereoCopyEncoder
 // (:1813-1982; DepthFirstStereoCopyEncoder.swift:29-99) in one persistent kernel
@@ -95,7 +100,8 @@ void df_launch_blend(const uint32_t* sortedGids, const DfArgs& a, const DfArena&
 void df_launch_project_mono(bool halfInput, uint32_t shDegree, const void* world, const void* harmonics,
                             const DfArgs& a, const DfArena& A, hipStream_t stream);
 // createInstancesKernel (:642-716): only the tiles that pass the per-tile test (mono_tile_pass)
-void df_launch_instances_mono(const uint32_t* order, const DfArgs& a, const DfArena& A, hipStream_t stream);
+void df_launch_instances_mono(const uint32_t* order, const DfArgs& a, const DfArena& A, hipStream_t stream,
+                              bool tile32 = false);
 // clear + depthFirstRender (:2020-2034, :1703-1811) in one persistent kernel; depth may be null
 void df_launch_blend_mono(const uint32_t* sortedGids, const DfArgs& a, const DfArena& A, void* color, size_t pitch,
                           int colorFormat, void* depth, size_t depthPitch, int numCUs, hipStream_t stream);

@@ -11,6 +11,8 @@
 // side by side with the copy pass's row flip (k_df_blend_eye).
 // Numeric contract: DESIGN.md (built with -ffp-contract=off, IEEE div/sqrt); bit-exact with
 // oracle/gsm_oracle.c og_df_render_stereo.
+// Create options (gsm_depthfirst_options): k_df_compact<true> writes the 16-bit depth key,
+// k_df_expand<false> / k_df_expand_mono<false> whole tile ids; bit-exact with tests/df_options/df_options_ref.c.
 // The mono frame's three kernels (k_df_project_mono, k_df_expand_mono, k_df_blend_mono) follow the
 // stereo ones below; bit-exact with tests/df_mono/df_mono_ref.c.
 #include <hip/hip_runtime.h>
@@ -245,7 +247,15 @@ __global__ __launch_bounds__(kDfBlock) void k_df_project(const void* __restrict_
 
 // ---------------------------------------------------------------------------
 // 2. compaction (visibilityScatterCompactKernel, DepthFirstShaders.metal:589-621): ascending id
+//    KEY16 (depth_key_bits 16, DF_DEPTH_KEY_16 :606-611): the key becomes the fp16 depth's sortable
+//    bits, uint(bits(half(sortable_uint_to_float(key))) ^ 0x8000) -- the inverse mapping is exact, the
+//    conversion rounds to nearest even (v_cvt_f16_f32; above 65504: +inf)
 // ---------------------------------------------------------------------------
+// sortable_uint_to_float (DepthFirstShaders.metal:39-43)
+__device__ __forceinline__ float df_unsortable(uint32_t v) {
+    return __builtin_bit_cast(float, (v & 0x80000000u) ? (v ^ 0x80000000u) : ~v);
+}
+template <bool KEY16>
 __global__ __launch_bounds__(kDfBlock) void k_df_compact(uint32_t count, const uint32_t* __restrict__ touched,
                                                          const uint32_t* __restrict__ depthKeys,
                                                          const uint32_t* __restrict__ blockOffsets,
@@ -257,7 +267,9 @@ __global__ __launch_bounds__(kDfBlock) void k_df_compact(uint32_t count, const u
     const uint32_t off = block_exclusive_scan<kDfBlock>(v, lds, &total);
     if (v) {
         const uint32_t o = blockOffsets[blockIdx.x] + off;
-        keys[o] = depthKeys[gid];
+        uint32_t key = depthKeys[gid];
+        if constexpr (KEY16) key = (uint32_t)f_to_hbits(df_unsortable(key)) ^ 0x8000u;
+        keys[o] = key;
         vals[o] = gid;
     }
 }
@@ -298,6 +310,8 @@ __device__ __forceinline__ bool df_eye_misses_tile(const DfEyeSkip& e, int x0, i
 // maxInstances.  Each instance also gets the blend's skip flags: bit kDfSkipShift + e of the
 // gaussian id is set when eye e provably adds nothing to the instance's tile
 // (df_eye_misses_tile, with each gaussian's per-eye setup computed once into LDS).
+// TILE16: the reference's ushort tile id (tile_id_bits 16); otherwise the whole id (tile_id_bits 32)
+template <bool TILE16>
 __global__ __launch_bounds__(kDfBlock) void k_df_expand(const TileAssignmentHeader* __restrict__ visHdr,
                                                         const uint32_t* __restrict__ order,
                                                         const uint32_t* __restrict__ touched,
@@ -367,7 +381,8 @@ __global__ __launch_bounds__(kDfBlock) void k_df_expand(const TileAssignmentHead
         else if ((dy + 1u) * w <= local) dy++;
         const uint32_t dx = local - dy * w;
         const int tx = r.x + (int)dx, ty = r.z + (int)dy;
-        tiles[wp] = (uint32_t)(ty * (int)tilesX + tx) & 0xFFFFu;  // ushort tile id
+        const uint32_t tileId = (uint32_t)(ty * (int)tilesX + tx);
+        tiles[wp] = TILE16 ? tileId & 0xFFFFu : tileId;  // TILE16: the ushort tile id
         const int x0 = tx * (int)kDfTile, y0 = ty * (int)kDfTile;
         const uint32_t fl = (df_eye_misses_tile(sE[0][lo], x0, y0) ? 1u : 0u) |
                             (df_eye_misses_tile(sE[1][lo], x0, y0) ? 2u : 0u);
@@ -851,6 +866,7 @@ __global__ __launch_bounds__(kDfBlock) void k_df_project_mono(const void* __rest
 // The offset of a tile inside its gaussian is the number of passing tiles before it: a lane's own
 // counter for small rects, the wave's ballot and popcount for large ones (mono_rect_tiles).
 // ---------------------------------------------------------------------------
+template <bool TILE16>
 __global__ __launch_bounds__(kDfBlock) void k_df_expand_mono(const TileAssignmentHeader* __restrict__ visHdr,
                                                              const uint32_t* __restrict__ order,
                                                              const uint32_t* __restrict__ touched,
@@ -887,7 +903,8 @@ __global__ __launch_bounds__(kDfBlock) void k_df_expand_mono(const TileAssignmen
     mono_rect_tiles(T, r, c > 0, [&](int tx, int ty, uint32_t k, uint32_t owner) {
         const uint64_t wp = base + sOff[waveBase + owner] + k;
         if (wp < maxInstances) {
-            tiles[wp] = (uint32_t)(ty * (int)tilesX + tx) & 0xFFFFu;  // ushort tile id
+            const uint32_t tileId = (uint32_t)(ty * (int)tilesX + tx);
+            tiles[wp] = TILE16 ? tileId & 0xFFFFu : tileId;  // TILE16: the ushort tile id
             gids[wp] = sG[waveBase + owner];
         }
     });
@@ -1062,12 +1079,17 @@ void df_launch_project_mono(bool halfInput, uint32_t deg, const void* world, con
     else df_launch_project_mono_t<false>(deg, world, harm, a, A, s);
 }
 
-void df_launch_instances_mono(const uint32_t* order, const DfArgs& a, const DfArena& A, hipStream_t s) {
+void df_launch_instances_mono(const uint32_t* order, const DfArgs& a, const DfArena& A, hipStream_t s, bool tile32) {
     const uint32_t blocks = (a.count + kDfBlock - 1) / kDfBlock;
     if (blocks == 0) return;
-    hipLaunchKernelGGL(k_df_expand_mono, dim3(blocks), dim3(kDfBlock), 0, s, A.visHdr, order, A.touched, A.bounds,
-                       A.instSums, (const uint4*)A.renderData, A.sincos, a.maxInstances, a.tilesX, A.ikeys[0],
-                       A.ivals[0]);
+    if (tile32)
+        hipLaunchKernelGGL(k_df_expand_mono<false>, dim3(blocks), dim3(kDfBlock), 0, s, A.visHdr, order, A.touched,
+                           A.bounds, A.instSums, (const uint4*)A.renderData, A.sincos, a.maxInstances, a.tilesX,
+                           A.ikeys[0], A.ivals[0]);
+    else
+        hipLaunchKernelGGL(k_df_expand_mono<true>, dim3(blocks), dim3(kDfBlock), 0, s, A.visHdr, order, A.touched,
+                           A.bounds, A.instSums, (const uint4*)A.renderData, A.sincos, a.maxInstances, a.tilesX,
+                           A.ikeys[0], A.ivals[0]);
 }
 
 constexpr int kDfMonoBlendWaves = 16;
@@ -1107,11 +1129,15 @@ void df_launch_project(bool halfInput, uint32_t deg, const void* world, const vo
     else df_launch_project_t<false>(deg, world, harm, a, A, s);
 }
 
-void df_launch_compact(const DfArgs& a, const DfArena& A, hipStream_t s) {
+void df_launch_compact(const DfArgs& a, const DfArena& A, hipStream_t s, bool key16) {
     const uint32_t blocks = (a.count + kDfBlock - 1) / kDfBlock;
     if (blocks == 0) return;
-    hipLaunchKernelGGL(k_df_compact, dim3(blocks), dim3(kDfBlock), 0, s, a.count, A.touched, A.depthKeys,
-                       A.blockSums, A.dkeys[0], A.dvals[0]);
+    if (key16)
+        hipLaunchKernelGGL(k_df_compact<true>, dim3(blocks), dim3(kDfBlock), 0, s, a.count, A.touched, A.depthKeys,
+                           A.blockSums, A.dkeys[0], A.dvals[0]);
+    else
+        hipLaunchKernelGGL(k_df_compact<false>, dim3(blocks), dim3(kDfBlock), 0, s, a.count, A.touched, A.depthKeys,
+                           A.blockSums, A.dkeys[0], A.dvals[0]);
 }
 
 void df_launch_instance_counts(const uint32_t* order, const DfArgs& a, const DfArena& A, hipStream_t s) {
@@ -1120,11 +1146,15 @@ void df_launch_instance_counts(const uint32_t* order, const DfArgs& a, const DfA
     hipLaunchKernelGGL(k_df_icount, dim3(blocks), dim3(kDfBlock), 0, s, A.visHdr, order, A.touched, A.instSums);
 }
 
-void df_launch_instances(const uint32_t* order, const DfArgs& a, const DfArena& A, hipStream_t s) {
+void df_launch_instances(const uint32_t* order, const DfArgs& a, const DfArena& A, hipStream_t s, bool tile32) {
     const uint32_t blocks = (a.count + kDfBlock - 1) / kDfBlock;
     if (blocks == 0) return;
-    hipLaunchKernelGGL(k_df_expand, dim3(blocks), dim3(kDfBlock), 0, s, A.visHdr, order, A.touched, A.bounds,
-                       A.instSums, A.renderData, a.maxInstances, a.tilesX, A.ikeys[0], A.ivals[0]);
+    if (tile32)
+        hipLaunchKernelGGL(k_df_expand<false>, dim3(blocks), dim3(kDfBlock), 0, s, A.visHdr, order, A.touched,
+                           A.bounds, A.instSums, A.renderData, a.maxInstances, a.tilesX, A.ikeys[0], A.ivals[0]);
+    else
+        hipLaunchKernelGGL(k_df_expand<true>, dim3(blocks), dim3(kDfBlock), 0, s, A.visHdr, order, A.touched,
+                           A.bounds, A.instSums, A.renderData, a.maxInstances, a.tilesX, A.ikeys[0], A.ivals[0]);
 }
 
 constexpr int kDfBlendWaves = 16;

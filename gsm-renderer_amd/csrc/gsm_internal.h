@@ -333,6 +333,13 @@ int radix_sort_bits(uint32_t* keys[2], uint32_t* vals[2], const uint32_t* nPtr, 
 int radix_sort_tiles(uint32_t* keys[2], uint32_t* vals[2], const uint32_t* nPtr, uint32_t capacity, uint32_t shift,
                      const SortSpace& ws, uint32_t* tileStart, uint32_t tileBase, uint32_t numTiles,
                      uint32_t allTiles, hipStream_t stream, bool ballot, bool wide = true, bool scanless = true);
+// a tile field of 17 .. kTilesWideMaxBits bits (more than 65,536 tiles: DepthFirst tile_id_bits
+// 32) in two passes, the starts written by the last one as above; `buckets`: kWideBins + 1 words
+int radix_sort_tiles_wide(uint32_t* keys[2], uint32_t* vals[2], const uint32_t* nPtr, uint32_t capacity,
+                          const SortSpace& ws, uint32_t* tileStart, uint32_t* buckets, uint32_t allTiles,
+                          hipStream_t stream, bool ballot);
+constexpr uint32_t kTilesWideMaxBits = kWideMaxBits + 8u;  // one wide pass + one 8-bit pass
+bool sort_tiles_wide_fits(uint32_t capacity, uint32_t allTiles, const SortSpace& ws);
 // the workspace footprint of one pass (words of `hist`, incl. the super-group rows in front), and
 // whether every pass radix_sort_bits plans fits `ws` (host only: no launch)
 size_t sort_pass_hist_words(bool wide, int bits, uint32_t grid);

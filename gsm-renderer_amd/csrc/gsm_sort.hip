@@ -209,7 +209,8 @@ struct TileStarts {
 
 // Digits >= 2^BITS do not exist: their counters stay 0 (thread tid owns digit tid of 256).
 // STARTS: the last pass of radix_sort_tiles (tile starts written, see TileStarts).
-template <int BITS, bool BALLOT, bool STARTS>
+// BIGL (with STARTS): more low-digit buckets than threads (radix_sort_tiles_wide: up to 2048).
+template <int BITS, bool BALLOT, bool STARTS, bool BIGL = false>
 __global__ __launch_bounds__(kRadixBlock) void k_radix_downsweep(
     const uint32_t* __restrict__ keysIn, const uint32_t* __restrict__ valsIn,
     uint32_t* __restrict__ keysOut, uint32_t* __restrict__ valsOut, const uint32_t* __restrict__ nPtr,
@@ -238,7 +239,12 @@ __global__ __launch_bounds__(kRadixBlock) void k_radix_downsweep(
     // STARTS: bucket l's start (uniform l: a scalar load); the first bucket not yet handled
     auto bucketAt = [&](uint32_t l) -> uint32_t { return ts.bucketStart ? ts.bucketStart[l] : 0u; };
     uint32_t nextL = 0;  // (starts are non-decreasing: the earlier blocks' buckets come first)
-    if (STARTS) nextL = (uint32_t)__syncthreads_count(tid < L && bucketAt(tid) < begin);
+    if constexpr (STARTS && BIGL) {
+        for (uint32_t l0 = 0; l0 < L; l0 += kRadixBlock)  // (L is uniform)
+            nextL += (uint32_t)__syncthreads_count(l0 + tid < L && bucketAt(l0 + tid) < begin);
+    } else if (STARTS) {
+        nextL = (uint32_t)__syncthreads_count(tid < L && bucketAt(tid) < begin);
+    }
 
     // global base of every digit for this block: exclusive scan over digits + block column offset
     {
@@ -921,6 +927,51 @@ int radix_sort_tiles(uint32_t* keys[2], uint32_t* vals[2], const uint32_t* nPtr,
     ts.lowBits = lo;
     radix_pass(keys[1], vals[1], keys[0], vals[0], nPtr, grid, shift + lo, (int)hi, ws.hist, ws.binTotals, s, ballot,
                &ts, true, scanless ? 1 : -1);
+    return 0;
+}
+
+// The tile field of a grid above 65,536 tiles (DepthFirst tile_id_bits 32): 17..19 bits in two passes.
+// One wide pass over the low lo = bits - 8 bits (9..11) whose block 0 also writes its digits' global
+// bases -- the low-digit buckets' starts, as a STARTS pass "tile starts" of 2^lo tiles -- into
+// `buckets` (2^lo + 1 words), then one 8-bit pass over the high digit that writes the tile starts from
+// those buckets (TileStarts with up to 2048 buckets: k_radix_downsweep BIGL).  The plan does not depend
+// on `wide` / GSM_SORT_WIDE (three narrow passes could not write the starts); ballot ranks apply to both.
+// The reference sorts such a field in ceil(bits / 8) = 3 passes (TileSortEncoder.swift:60-62).
+static uint32_t tiles_wide_bits(uint32_t allTiles) {
+    uint32_t b = 17;
+    while (b < 32 && ((allTiles - 1u) >> b)) b++;
+    return b;
+}
+bool sort_tiles_wide_fits(uint32_t capacity, uint32_t allTiles, const SortSpace& ws) {
+    const uint32_t bits = tiles_wide_bits(allTiles);
+    if (bits > kTilesWideMaxBits) return false;
+    const uint32_t lo = bits - 8u;
+    return pass_fits(ws, true, (int)lo, wide_grid_for_capacity(capacity), (size_t)1 << lo) &&
+           pass_fits(ws, false, 8, radix_grid_for_capacity(capacity), 256);
+}
+int radix_sort_tiles_wide(uint32_t* keys[2], uint32_t* vals[2], const uint32_t* nPtr, uint32_t capacity,
+                          const SortSpace& ws, uint32_t* tileStart, uint32_t* buckets, uint32_t allTiles,
+                          hipStream_t s, bool ballot) {
+    if (!buckets || !sort_tiles_wide_fits(capacity, allTiles, ws)) return kSortNoSpace;
+    const uint32_t lo = tiles_wide_bits(allTiles) - 8u;
+    const uint32_t grid = radix_grid_for_capacity(capacity), wgrid = wide_grid_for_capacity(capacity);
+    wide_pass(keys[0], vals[0], keys[1], vals[1], nPtr, wgrid, 0u, 0u, (int)lo, ws.hist, ws.binTotals, s, ballot, true,
+              buckets, 1u << lo, 1u << lo);
+    TileStarts ts{};
+    ts.bucketStart = buckets;
+    ts.lowBits = lo;
+    ts.numTiles = allTiles;
+    ts.tileStart = tileStart;
+    uint32_t* hist = ws.hist + kSuperWords;
+    hipLaunchKernelGGL(k_radix_upsweep<8>, dim3(grid), dim3(kRadixBlock), 0, s, keys[1], nPtr, lo, hist,
+                       (uint32_t*)nullptr, (uint32_t*)nullptr);
+    hipLaunchKernelGGL(k_radix_scan, dim3(256), dim3(256), 0, s, hist, grid, ws.binTotals);
+    if (ballot)
+        hipLaunchKernelGGL((k_radix_downsweep<8, true, true, true>), dim3(grid), dim3(kRadixBlock), 0, s, keys[1], vals[1],
+                           keys[0], vals[0], nPtr, lo, hist, ws.binTotals, ts, (const uint32_t*)nullptr);
+    else
+        hipLaunchKernelGGL((k_radix_downsweep<8, false, true, true>), dim3(grid), dim3(kRadixBlock), 0, s, keys[1], vals[1],
+                           keys[0], vals[0], nPtr, lo, hist, ws.binTotals, ts, (const uint32_t*)nullptr);
     return 0;
 }
 

@@ -185,6 +185,11 @@ class _DfCounters(C.Structure):
                 ("tiles_y", C.c_uint32), ("tile_count", C.c_uint32)]
 
 
+class _DfOptions(C.Structure):  # gsm_depthfirst_options
+    _fields_ = [("struct_bytes", C.c_uint32), ("depth_key_bits", C.c_uint32), ("tile_id_bits", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class _LocalCounters(C.Structure):
     _fields_ = [("gaussian_count", C.c_uint32), ("visible", C.c_uint32), ("tiles_x", C.c_uint32),
                 ("tiles_y", C.c_uint32), ("tile_count", C.c_uint32), ("active_tiles", C.c_uint32),
@@ -232,6 +237,10 @@ _SIGNATURES = {
                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t], C.c_int),
     # include/gsm_depthfirst.h
     "gsm_depthfirst_create": ([C.POINTER(_Config), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
+    "gsm_depthfirst_default_options": ([C.POINTER(_DfOptions)], None),
+    "gsm_depthfirst_create_with_options": ([C.POINTER(_Config), C.c_int, C.POINTER(_DfOptions),
+                                            C.POINTER(C.c_void_p)], C.c_int),
+    "gsm_depthfirst_get_options": ([C.c_void_p, C.POINTER(_DfOptions)], C.c_int),
     "gsm_depthfirst_destroy": ([C.c_void_p], None),
     "gsm_depthfirst_render_stereo_sbs": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera),
                                           C.POINTER(_Camera), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
@@ -552,6 +561,7 @@ class DepthFirstBuffer(enum.IntEnum):  # include/gsm_depthfirst.h gsm_depthfirst
     INSTANCE_GAUSSIANS = 6
     HEADERS = 7
     BLEND_STATS = 8
+    SORTED_DEPTH_KEYS = 9  # uint32[visible]: the compacted keys as the depth sort left them
 
 
 DF_STAGES = ("project", "depth_sort", "instances", "tile_sort", "blend")  # gsm_depthfirst_stage
@@ -567,9 +577,12 @@ STEREO_RENDER_DATA = np.dtype([(f, "<u2") for f in (
 class DepthFirstRenderer:
     """DepthFirstRenderer (DepthFirstRenderer.swift:11-831) on one HIP device: the mono frame
     (render, :166-203, 237-465) and the stereo side-by-side path (renderStereo(target:
-    .sideBySide), :205-223, 469-512).  renderStereo(.foveated) is out of scope."""
+    .sideBySide), :205-223, 469-512).  renderStereo(.foveated) is out of scope.
+    depth_key_bits (16 | 32) and tile_id_bits (16 | 32) are depthSortKeyPrecision and tileIdPrecision
+    of DepthFirstRenderer.init (:45-50), fixed for the life of the renderer (include/gsm_depthfirst.h)."""
 
-    def __init__(self, device: Optional[int] = None, config: RendererConfig = RendererConfig()):
+    def __init__(self, device: Optional[int] = None, config: RendererConfig = RendererConfig(),
+                 depth_key_bits: int = 32, tile_id_bits: int = 16):
         L = _lib()
         self.config = config
         cfg = _Config(int(config.max_gaussians), int(config.max_width), int(config.max_height),
@@ -577,11 +590,20 @@ class DepthFirstRenderer:
                       int(config.gaussian_color_space), int(bool(config.back_to_front)))
         h = C.c_void_p()
         dev = -1 if device is None else int(device)
-        _check(L.gsm_depthfirst_create(C.byref(cfg), dev, C.byref(h)), "gsm_depthfirst_create")
+        opt = _DfOptions(C.sizeof(_DfOptions), int(depth_key_bits), int(tile_id_bits), 0)
+        _check(L.gsm_depthfirst_create_with_options(C.byref(cfg), dev, C.byref(opt), C.byref(h)),
+               "gsm_depthfirst_create_with_options")
         self._h = h
         self.device = dev
         self._bpp = ColorFormat(int(config.color_format)).bytes_per_pixel
         self._last_mono = False  # the last frame was a mono frame (copy_buffer's record dtype)
+
+    @property
+    def options(self) -> dict:
+        """{"depth_key_bits", "tile_id_bits"} as the handle holds them (gsm_depthfirst_get_options)."""
+        o = _DfOptions()
+        _check(_lib().gsm_depthfirst_get_options(self._h, C.byref(o)), "gsm_depthfirst_get_options")
+        return {"depth_key_bits": int(o.depth_key_bits), "tile_id_bits": int(o.tile_id_bits)}
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

@@ -29,13 +29,43 @@ extern "C" {
 typedef struct gsm_depthfirst gsm_depthfirst;
 
 /* DepthFirstRenderer.init(device:config:depthSortKeyPrecision:tileIdPrecision:)
- * (DepthFirstRenderer.swift:45-101) with its defaults: 32-bit depth keys, 16-bit tile ids.
+ * (DepthFirstRenderer.swift:45-101) with its defaults: 32-bit depth keys, 16-bit tile ids
+ * (gsm_depthfirst_create_with_options below sets the other two).
  * Errors as GlobalRenderer.init: max_gaussians > 30M -> GSM_ERR_INVALID_GAUSSIAN_COUNT
  * (:51-56); a 16x16 tile grid of max_width x max_height over 65535 tiles (16-bit tile ids,
  * 0xFFFF is the tile sort's sentinel) -> GSM_ERR_INVALID_TILE_COUNT.  Scratch is allocated
  * here: max_gaussians records and 4 * max_gaussians instances (DepthFirstResources.swift:399). */
 gsm_status gsm_depthfirst_create(const gsm_renderer_config *config, int hip_device, gsm_depthfirst **out);
 void gsm_depthfirst_destroy(gsm_depthfirst *renderer);
+
+/* The two other constructor arguments of DepthFirstRenderer.init (DepthFirstRenderer.swift:45-50),
+ * fixed for the life of the handle and applied to both of its frames (mono and stereo).
+ *   depth_key_bits 16 (depthSortKeyPrecision: .bits16): the compaction replaces the 32-bit key by
+ *     uint(bits(half(sortable_uint_to_float(key))) ^ 0x8000) (visibilityScatterCompactKernel,
+ *     DepthFirstShaders.metal:589-621; fp32 -> fp16 rounds to nearest even, depths above 65504
+ *     become +inf) and the depth sort is a stable sort of those 16 bits (2 passes,
+ *     DepthRadixSortEncoder.swift:13-24).  Gaussians whose depths share an fp16 value keep their
+ *     ascending ids, so the blend order differs from the 32-bit order there.
+ *   tile_id_bits 32 (tileIdPrecision: .bits32): the instance expansion writes the whole tile id and
+ *     the tile sort covers ceil(log2(tile count)) bits, so the 16x16 grid of max_width x max_height
+ *     may hold up to GSM_DF_MAX_TILES_32 tiles (one 9..11-bit pass and one 8-bit pass: 19 bits);
+ *     above it, or with more than GSM_DF_MAX_TILES_AXIS tiles along one axis (tile rects are 16-bit
+ *     signed), -> GSM_ERR_INVALID_TILE_COUNT.  Up to 65,535 tiles the frame is byte for byte the
+ *     16-bit handle's.  With tile_id_bits 16 the limit stays 65,535 tiles.
+ * struct_bytes must be sizeof(gsm_depthfirst_options), the bit counts 16 or 32 and reserved 0,
+ * else GSM_ERR_INVALID_ARGUMENT.  A NULL options pointer means the defaults. */
+#define GSM_DF_MAX_TILES_32 524288u
+#define GSM_DF_MAX_TILES_AXIS 32767u
+typedef struct {
+    uint32_t struct_bytes;    /* sizeof(gsm_depthfirst_options) == 16 */
+    uint32_t depth_key_bits;  /* 16 or 32; default 32 */
+    uint32_t tile_id_bits;    /* 16 or 32; default 16 */
+    uint32_t reserved;        /* must be 0 */
+} gsm_depthfirst_options;
+void gsm_depthfirst_default_options(gsm_depthfirst_options *out);
+gsm_status gsm_depthfirst_create_with_options(const gsm_renderer_config *config, int hip_device,
+                                              const gsm_depthfirst_options *options, gsm_depthfirst **out);
+gsm_status gsm_depthfirst_get_options(gsm_depthfirst *renderer, gsm_depthfirst_options *out);
 
 /* renderStereo(commandBuffer:target:.sideBySide(colorTexture:depthTexture:)input:camera:width:height:)
  * (DepthFirstRenderer.swift:205-223, 469-512).  width/height are per eye (<= config max_width /
@@ -109,8 +139,12 @@ typedef enum {
     GSM_DF_BUF_INSTANCE_TILES = 5,   /* uint32[total_instances] sorted tile ids [instanceTileIds] */
     GSM_DF_BUF_INSTANCE_GAUSSIANS = 6, /* int32[total_instances] [instanceGaussianIndices] */
     GSM_DF_BUF_HEADERS = 7,          /* GaussianHeader[tile_count] {offset, count} [tileHeaders] */
-    GSM_DF_BUF_BLEND_STATS = 8       /* uint64[4] (profiling bit 1): list entries the blend walked, of
+    GSM_DF_BUF_BLEND_STATS = 8,      /* uint64[4] (profiling bit 1): list entries the blend walked, of
                                         which had the eye's mean, of which blended; list entries */
+    GSM_DF_BUF_SORTED_DEPTH_KEYS = 9 /* uint32[visible] the compacted keys as the depth sort left them
+                                        [depthKeys]: the 32-bit keys, or with depth_key_bits 16 the
+                                        quantised keys in the low 16 bits; DEPTH_KEYS stays the 32-bit
+                                        preDepthKeys in every mode (the compaction quantises) */
 } gsm_depthfirst_buffer;
 
 gsm_status gsm_depthfirst_debug_counters(gsm_depthfirst *renderer, gsm_depthfirst_counters *out);

@@ -297,18 +297,38 @@ public final class GlobalRenderer: GaussianRenderer {
     public func debugReadTotalAssignments() -> Int { Int(gsm_global_debug_read_total_assignments(handle)) }
 }
 
+/// RadixSortKeyPrecision of the reference (DepthRadixSortEncoder.swift:15): the bits of DepthFirstRenderer's depth keys and tile ids
+/// (gsm_depthfirst_options.depth_key_bits / tile_id_bits).
+public enum RadixSortKeyPrecision: UInt32 {
+    case bits16 = 16
+    case bits32 = 32
+}
+
 /// DepthFirstRenderer's mono frame (DepthFirstRenderer.swift:166-203) and side-by-side stereo path (:205-223).
 public final class DepthFirstRenderer: GaussianRenderer {
     private var handle: OpaquePointer?
     public let device: Int32
     public private(set) var lastError: RendererError?
 
-    public init(device: Int32 = -1, config: RendererConfig = RendererConfig()) throws {
+    public let depthSortKeyPrecision: RadixSortKeyPrecision
+    public let tileIdPrecision: RadixSortKeyPrecision
+
+    /// init(device:config:depthSortKeyPrecision:tileIdPrecision:) (DepthFirstRenderer.swift:45-50), the
+    /// reference's defaults; gsm_depthfirst_create_with_options.
+    public init(device: Int32 = -1, config: RendererConfig = RendererConfig(),
+                depthSortKeyPrecision: RadixSortKeyPrecision = .bits32,
+                tileIdPrecision: RadixSortKeyPrecision = .bits16) throws {
         var cfg = config.c
+        var opt = gsm_depthfirst_options()
+        gsm_depthfirst_default_options(&opt)
+        opt.depth_key_bits = depthSortKeyPrecision.rawValue
+        opt.tile_id_bits = tileIdPrecision.rawValue
         var h: OpaquePointer?
-        if let err = RendererError(status: gsm_depthfirst_create(&cfg, device, &h)) { throw err }
+        if let err = RendererError(status: gsm_depthfirst_create_with_options(&cfg, device, &opt, &h)) { throw err }
         handle = h
         self.device = device
+        self.depthSortKeyPrecision = depthSortKeyPrecision
+        self.tileIdPrecision = tileIdPrecision
     }
 
     deinit { gsm_depthfirst_destroy(handle) }
