@@ -3,7 +3,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <new>
 
 #include "../../include/gsm_debug.h"
 #include "../../include/gsm_multigpu.h"
@@ -66,28 +65,13 @@ void gsm_camera_params_init(gsm_camera_params* cam, const float view[16], const 
 
 gsm_status gsm_global_create(const gsm_renderer_config* config, int hip_device, gsm_renderer** out) {
     if (!out) return GSM_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
     gsm_renderer_config cfg;
     if (config) cfg = *config;
     else gsm_renderer_config_default(&cfg);
-    gsm::GlobalRenderer* impl = nullptr;
-    gsm_status st = gsm::GlobalRenderer::create(cfg, hip_device, &impl);
-    if (st != GSM_OK) return st;
-    gsm_renderer* h = new (std::nothrow) gsm_renderer;
-    if (!h) {
-        delete impl;
-        return GSM_ERR_FAILED_TO_ALLOCATE_BUFFER;
-    }
-    h->impl = impl;
-    *out = h;
-    return GSM_OK;
+    return gsm_renderer::create(out, cfg, hip_device);
 }
 
-void gsm_global_destroy(gsm_renderer* r) {
-    if (!r) return;
-    delete r->impl;
-    delete r;
-}
+void gsm_global_destroy(gsm_renderer* r) { gsm_renderer::destroy(r); }
 
 gsm_status gsm_global_render(gsm_renderer* r, void* stream, const gsm_gaussian_input* input,
                              const gsm_camera_params* camera, uint32_t width, uint32_t height,

@@ -11,14 +11,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
-#include <new>
-#include <vector>
 
 #include "../../include/gsm_depthfirst.h"
 #include "gsm_detmath.h"
 #include "gsm_df_internal.h"
+#include "gsm_host.h"
 #include "gsm_internal.h"
 
 namespace gsm {
@@ -28,7 +26,7 @@ class DepthFirstRenderer {
     static gsm_status create(const gsm_renderer_config& cfg, int hipDevice, const gsm_depthfirst_options& opt,
                              DepthFirstRenderer** out);
     const gsm_depthfirst_options& options() const { return options_; }
-    ~DepthFirstRenderer() { release(); }
+    ~DepthFirstRenderer() { hipSetDevice(dev_.id); }  // (the events and buffers are released on their device)
     gsm_status renderStereoSbs(hipStream_t s, const gsm_gaussian_input& in, const gsm_camera_params& left,
                                const gsm_camera_params& right, const float* scene, uint32_t width, uint32_t height,
                                void* color, size_t pitch);
@@ -37,15 +35,26 @@ class DepthFirstRenderer {
     gsm_status counters(gsm_depthfirst_counters* out);
     gsm_status debugCopy(int which, void* dst, size_t bytes, size_t* needed);
     gsm_status setProfiling(int flags);
-    gsm_status stageTimes(float* ms, int n);
-    gsm_status lastGpuTime(double* seconds);
+    gsm_status stageTimes(float* ms, int n) {
+        hipSetDevice(dev_.id);
+        return timer_.stageTimes(ms, n, GSM_DF_STAGE_BLEND);
+    }
+    gsm_status lastGpuTime(double* seconds) {
+        hipSetDevice(dev_.id);
+        return timer_.lastGpuTime(seconds);
+    }
 
    private:
     DepthFirstRenderer() = default;
-    gsm_status alloc(void** p, size_t bytes);
-    void release();
-    int device_ = -1;
-    int numCUs_ = 256;
+    // the arguments both frames share; `cam` (the left eye, or the mono camera) gives eye[0], near and far
+    DfArgs frameArgs(const gsm_gaussian_input& in, const gsm_camera_params& cam, uint32_t width, uint32_t height) const;
+    // One frame after validation.  project(), expand(depth order), blend(sorted gaussian ids) are the mode's
+    // launches and beforeBlend() what it enqueues between the tile sort and the blend's events; the scans,
+    // the compaction, both sorts and the instance counts between them are common.
+    template <class Project, class Expand, class BeforeBlend, class Blend>
+    gsm_status runFrame(hipStream_t s, const DfArgs& a, bool mono, Project&& project, Expand&& expand,
+                        BeforeBlend&& beforeBlend, Blend&& blend);
+    Device dev_;
     gsm_renderer_config config_{};
     Tuning tuning_{};  // A/B switches, read once at create
     uint32_t maxGaussians_ = 1, maxWidth_ = 1, maxHeight_ = 1, maxInstances_ = 4;
@@ -56,7 +65,7 @@ class DepthFirstRenderer {
     int sortDepth(hipStream_t s);
     int sortTiles(const DfArgs& a, hipStream_t s);
     DfArena A_;
-    std::vector<void*> allocations_;
+    DeviceAllocations allocs_;
     // last frame
     uint32_t lastCount_ = 0, lastTilesX_ = 0, lastTilesY_ = 0;
     bool lastMono_ = false;  // the last frame was a mono frame (16-byte records)
@@ -65,45 +74,15 @@ class DepthFirstRenderer {
     const uint32_t* depthOrder_ = nullptr;
     const uint32_t* instTiles_ = nullptr;
     const uint32_t* instGids_ = nullptr;
-    // profiling: a ring of per-stage events
-    static constexpr int kRing = 64;
-    std::vector<hipEvent_t> events_;  // [kRing][GSM_DF_STAGE_COUNT + 1]
-    uint32_t profFrames_ = 0;
-    uint32_t sampleFrame_ = 0;  // frames since setProfiling (blend-event sampling)
-    int profiling_ = 0;
-    hipEvent_t* frameEvents(uint32_t f) { return &events_[(f % kRing) * (GSM_DF_STAGE_COUNT + 1)]; }
+    StageTimer timer_{GSM_DF_STAGE_COUNT, 64};  // the last 64 profiled frames are averaged
 };
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-void DepthFirstRenderer::release() {
-    if (device_ >= 0) hipSetDevice(device_);
-    for (void* p : allocations_) hipFree(p);
-    allocations_.clear();
-    for (auto& e : events_)
-        if (e) hipEventDestroy(e);
-    events_.clear();
-}
-
-gsm_status DepthFirstRenderer::alloc(void** p, size_t bytes) {
-    *p = nullptr;
-    if (bytes == 0) bytes = 16;
-    if (hipMalloc(p, align_up(bytes, 256)) != hipSuccess) {
-        *p = nullptr;
-        return GSM_ERR_FAILED_TO_ALLOCATE_BUFFER;
-    }
-    allocations_.push_back(*p);
-    return GSM_OK;
-}
 
 gsm_status DepthFirstRenderer::create(const gsm_renderer_config& cfg, int hipDevice,
                                       const gsm_depthfirst_options& opt, DepthFirstRenderer** out) {
     *out = nullptr;
     // DepthFirstRenderer.init guard (DepthFirstRenderer.swift:51-56)
-    if (cfg.max_gaussians > kMaxSupportedGaussians) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
-    if (cfg.precision != GSM_PRECISION_FLOAT32 && cfg.precision != GSM_PRECISION_FLOAT16)
-        return GSM_ERR_INVALID_ARGUMENT;
-    if (cfg.color_format > GSM_COLOR_FORMAT_BGRA8_UNORM_SRGB) return GSM_ERR_INVALID_ARGUMENT;
+    gsm_status st = check_config(cfg);
+    if (st != GSM_OK) return st;
     const uint32_t maxW = cfg.max_width ? cfg.max_width : 1u, maxH = cfg.max_height ? cfg.max_height : 1u;
     const uint64_t tiles = (uint64_t)((maxW + kDfTile - 1) / kDfTile) * ((maxH + kDfTile - 1) / kDfTile);
     const bool tile32 = opt.tile_id_bits == 32u;
@@ -115,17 +94,12 @@ gsm_status DepthFirstRenderer::create(const gsm_renderer_config& cfg, int hipDev
     if (tile32 && ((maxW + kDfTile - 1) / kDfTile > GSM_DF_MAX_TILES_AXIS ||
                    (maxH + kDfTile - 1) / kDfTile > GSM_DF_MAX_TILES_AXIS))
         return GSM_ERR_INVALID_TILE_COUNT;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return GSM_ERR_DEVICE_NOT_AVAILABLE;
-    }
-    int dev = hipDevice;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
-    if (dev >= ndev || hipSetDevice(dev) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
+    Device dev;
+    if ((st = pick_device(hipDevice, &dev)) != GSM_OK) return st;
     DepthFirstRenderer* r = new (std::nothrow) DepthFirstRenderer();
     if (!r) return GSM_ERR_FAILED_TO_ALLOCATE_BUFFER;
-    r->device_ = dev;
+    r->dev_ = dev;
+    r->allocs_.setDevice(dev.id);
     r->config_ = cfg;
     r->maxGaussians_ = cfg.max_gaussians ? cfg.max_gaussians : 1u;
     r->maxWidth_ = maxW;
@@ -136,51 +110,38 @@ gsm_status DepthFirstRenderer::create(const gsm_renderer_config& cfg, int hipDev
     r->tile32_ = tile32;
     const uint64_t cap64 = 4ull * r->maxGaussians_;  // DepthFirstResources.swift:399
     r->maxInstances_ = (uint32_t)(cap64 > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : cap64);
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-        delete r;
-        return GSM_ERR_DEVICE_NOT_AVAILABLE;
-    }
-    r->numCUs_ = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    r->tuning_ = tuning_from_env(dev);
+    r->tuning_ = tuning_from_env(dev.id);
     const size_t G = r->maxGaussians_, cap = r->maxInstances_;
     const size_t nb = (G + kDfBlock - 1) / kDfBlock;
     DfArena& A = r->A_;
-    gsm_status st = GSM_OK;
-#define GSM_DF_ALLOC(ptr, bytes) \
-    do {                         \
-        if (st == GSM_OK) st = r->alloc((void**)&(ptr), (bytes)); \
-    } while (0)
-    GSM_DF_ALLOC(A.renderData, G * sizeof(StereoTiledRenderData));
-    GSM_DF_ALLOC(A.bounds, G * sizeof(short4));
-    GSM_DF_ALLOC(A.touched, G * 4);
-    GSM_DF_ALLOC(A.depthKeys, G * 4);
-    GSM_DF_ALLOC(A.blockSums, (nb + 1) * 4);
-    GSM_DF_ALLOC(A.instSums, (nb + 1) * 4);
-    GSM_DF_ALLOC(A.visHdr, sizeof(TileAssignmentHeader));
-    GSM_DF_ALLOC(A.instHdr, sizeof(TileAssignmentHeader));
+    DeviceAllocations& M = r->allocs_;
+    M.alloc(st, A.renderData, G * sizeof(StereoTiledRenderData));
+    M.alloc(st, A.bounds, G * sizeof(short4));
+    M.alloc(st, A.touched, G * 4);
+    M.alloc(st, A.depthKeys, G * 4);
+    M.alloc(st, A.blockSums, (nb + 1) * 4);
+    M.alloc(st, A.instSums, (nb + 1) * 4);
+    M.alloc(st, A.visHdr, sizeof(TileAssignmentHeader));
+    M.alloc(st, A.instHdr, sizeof(TileAssignmentHeader));
     for (int i = 0; i < 2; ++i) {
-        GSM_DF_ALLOC(A.dkeys[i], G * 4);
-        GSM_DF_ALLOC(A.dvals[i], G * 4);
-        GSM_DF_ALLOC(A.ikeys[i], cap * 4);
-        GSM_DF_ALLOC(A.ivals[i], cap * 4);
+        M.alloc(st, A.dkeys[i], G * 4);
+        M.alloc(st, A.dvals[i], G * 4);
+        M.alloc(st, A.ikeys[i], cap * 4);
+        M.alloc(st, A.ivals[i], cap * 4);
     }
     A.radixHistBytes = radix_workspace_bytes(r->maxInstances_ > r->maxGaussians_ ? r->maxInstances_ : r->maxGaussians_);
-    GSM_DF_ALLOC(A.radixHist, A.radixHistBytes);
-    if (st == GSM_OK &&
-        hipMemset(A.radixHist, 0, radix_workspace_bytes(r->maxInstances_ > r->maxGaussians_ ? r->maxInstances_ : r->maxGaussians_)) != hipSuccess)
-        st = GSM_ERR_FAILED_TO_ALLOCATE_BUFFER;
-    GSM_DF_ALLOC(A.radixBinTotals, kSortTotalsWords * 4);  // radix_sort_tiles: totals + block table
-    GSM_DF_ALLOC(A.starts, ((size_t)r->maxTiles_ + 1) * sizeof(uint32_t));
-    GSM_DF_ALLOC(A.queue, kQueueStripes * kQueueStride * sizeof(uint32_t));
-    GSM_DF_ALLOC(A.expTable, 65536 * 2);
-    GSM_DF_ALLOC(A.unitCost, (size_t)r->maxTiles_ * 2 * sizeof(uint16_t));
-    GSM_DF_ALLOC(A.unitOrder, (size_t)r->maxTiles_ * 2 * sizeof(uint32_t));
-    GSM_DF_ALLOC(A.costMax, kCostMaxSlots * sizeof(uint32_t));
-    GSM_DF_ALLOC(A.sincos, 65536 * sizeof(float2));
-    GSM_DF_ALLOC(A.expTableMono, 65536 * 2);
-    if (tiles > 65536u) GSM_DF_ALLOC(A.tileBuckets, ((size_t)kWideBins + 1) * sizeof(uint32_t));
-#undef GSM_DF_ALLOC
+    M.alloc(st, A.radixHist, A.radixHistBytes);
+    if (st == GSM_OK && hipMemset(A.radixHist, 0, A.radixHistBytes) != hipSuccess) st = GSM_ERR_FAILED_TO_ALLOCATE_BUFFER;
+    M.alloc(st, A.radixBinTotals, kSortTotalsWords * 4);  // radix_sort_tiles: totals + block table
+    M.alloc(st, A.starts, ((size_t)r->maxTiles_ + 1) * sizeof(uint32_t));
+    M.alloc(st, A.queue, kQueueStripes * kQueueStride * sizeof(uint32_t));
+    M.alloc(st, A.expTable, 65536 * 2);
+    M.alloc(st, A.unitCost, (size_t)r->maxTiles_ * 2 * sizeof(uint16_t));
+    M.alloc(st, A.unitOrder, (size_t)r->maxTiles_ * 2 * sizeof(uint32_t));
+    M.alloc(st, A.costMax, kCostMaxSlots * sizeof(uint32_t));
+    M.alloc(st, A.sincos, 65536 * sizeof(float2));
+    M.alloc(st, A.expTableMono, 65536 * 2);
+    if (tiles > 65536u) M.alloc(st, A.tileBuckets, ((size_t)kWideBins + 1) * sizeof(uint32_t));
     // the sort plans the options add must fit the workspace now, not at the first frame
     if (st == GSM_OK && r->key16_ && !sort_bits_plan_fits(r->maxGaussians_, 16, r->tuning_.wideSort, sort_space(A)))
         st = GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;
@@ -190,18 +151,15 @@ gsm_status DepthFirstRenderer::create(const gsm_renderer_config& cfg, int hipDev
         delete r;
         return st;
     }
-    std::vector<uint16_t> expt(65536);
-    for (uint32_t i = 0; i < 65536; ++i) expt[i] = stereo_exp_table_entry((uint16_t)i);
-    // the mono frame's tables: the Global blend's alpha table and the sin/cos of the quantised angles
-    std::vector<uint16_t> exptMono(65536);
-    std::vector<float2> sc(65536);
-    for (uint32_t i = 0; i < 65536; ++i) {
-        exptMono[i] = blend_exp_table_entry((uint16_t)i);
-        det_sincos_table_entry(i, &sc[i].x, &sc[i].y);
-    }
-    if (hipMemcpy(A.expTableMono, exptMono.data(), 65536 * 2, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(A.sincos, sc.data(), 65536 * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(A.expTable, expt.data(), 65536 * 2, hipMemcpyHostToDevice) != hipSuccess ||
+    // the stereo alpha table; the mono frame's tables: the Global blend's alpha table and the sin/cos of
+    // the quantised angles
+    if (upload_table(A.expTableMono, [](uint32_t i) { return blend_exp_table_entry((uint16_t)i); }) != GSM_OK ||
+        upload_table(A.sincos, [](uint32_t i) {
+            float2 v;
+            det_sincos_table_entry(i, &v.x, &v.y);
+            return v;
+        }) != GSM_OK ||
+        upload_table(A.expTable, [](uint32_t i) { return stereo_exp_table_entry((uint16_t)i); }) != GSM_OK ||
         hipMemset(A.visHdr, 0, sizeof(TileAssignmentHeader)) != hipSuccess ||
         hipMemset(A.instHdr, 0, sizeof(TileAssignmentHeader)) != hipSuccess ||
         hipMemset(A.costMax, 0, kCostMaxSlots * sizeof(uint32_t)) != hipSuccess ||
@@ -235,57 +193,30 @@ int DepthFirstRenderer::sortTiles(const DfArgs& a, hipStream_t s) {
                             tuning_.sortScanless);
 }
 
-// per-eye projectCovariance2D terms, the same fp32 operations the reference repeats per gaussian
-// (GaussianShared.h:340-355)
-static void eye_const(const gsm_camera_params& c, float W, float H, DfEyeConst* e) {
+// one eye's matrices and its projectCovariance2D terms (GaussianShared.h:340-355)
+static void set_eye(const gsm_camera_params& c, const ProjectionUniforms& u, DfEyeConst* e) {
     std::memcpy(e->view, c.view, sizeof(e->view));
     std::memcpy(e->proj, c.proj, sizeof(e->proj));
-    const float p00 = c.proj[0], p11 = c.proj[5];
-    e->limX = 1.3f * (1.0f / std::fmax(std::fabs(p00), 1e-4f));
-    e->limY = 1.3f * (1.0f / std::fmax(std::fabs(p11), 1e-4f));
-    e->focalX = W * std::fabs(p00) * 0.5f;
-    e->focalY = H * std::fabs(p11) * 0.5f;
+    e->limX = u.limX;
+    e->limY = u.limY;
+    e->focalX = u.focalX;
+    e->focalY = u.focalY;
 }
 
-gsm_status DepthFirstRenderer::renderStereoSbs(hipStream_t s, const gsm_gaussian_input& in,
-                                               const gsm_camera_params& left, const gsm_camera_params& right,
-                                               const float* scene, uint32_t width, uint32_t height, void* color,
-                                               size_t pitch) {
-    (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's: the launches below are checked)
-    // encodeStereoPipeline guards (DepthFirstRenderer.swift:478, 607) -- errors, not a silent skip
-    if (in.gaussian_count > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
-    if (width == 0 || height == 0 || width > maxWidth_ || height > maxHeight_) return GSM_ERR_INVALID_DIMENSIONS;
-    if (!color) return GSM_ERR_MISSING_REQUIRED_BUFFER;
-    if (in.gaussian_count > 0 && (!in.gaussians || !in.harmonics)) return GSM_ERR_MISSING_REQUIRED_BUFFER;
-    const int fmt = (int)config_.color_format;
-    const size_t bpp = fmt == GSM_COLOR_FORMAT_RGBA16F ? 8 : (fmt == GSM_COLOR_FORMAT_RGBA32F ? 16 : 4);
-    if (pitch < (size_t)2 * width * bpp) return GSM_ERR_INVALID_BUFFER_SIZE;
-    if ((((uintptr_t)color) & 3u) || (pitch & 3u)) return GSM_ERR_INVALID_BUFFER_SIZE;
-    if (hipSetDevice(device_) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
-
+DfArgs DepthFirstRenderer::frameArgs(const gsm_gaussian_input& in, const gsm_camera_params& cam, uint32_t width,
+                                     uint32_t height) const {
     DfArgs a;
     std::memset(&a, 0, sizeof(a));
-    const float W = (float)width, H = (float)height;
-    eye_const(left, W, H, &a.eye[0]);
-    eye_const(right, W, H, &a.eye[1]);
-    static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    std::memcpy(a.scene, scene ? scene : kIdentity, sizeof(a.scene));
-    {  // length(sceneTransform[0].xyz) (DepthFirstShaders.metal:293)
-        float d = a.scene[0] * a.scene[0] + a.scene[1] * a.scene[1];
-        d = d + a.scene[2] * a.scene[2];
-        a.sceneScale = std::sqrt(d);
-    }
-    a.width = W;
-    a.height = H;
+    a.width = (float)width;
+    a.height = (float)height;
     // makeStereoCameraUniforms: near/far of the left camera (DepthFirstRenderer.swift:583-584)
-    a.nearPlane = left.near_plane;
-    a.farPlane = left.far_plane;
-    const float maxDim = std::fmax(W, H);
-    const float maxEig = (maxDim * 2.0f) / 3.0f;
-    a.maxEig = maxEig * maxEig;
-    a.adjFar = a.farPlane * 0.02f;
-    a.adjDen = a.adjFar - a.nearPlane;
-    for (int i = 0; i < 3; ++i) a.mid[i] = (left.position[i] + right.position[i]) * 0.5f;
+    a.nearPlane = cam.near_plane;
+    a.farPlane = cam.far_plane;
+    const ProjectionUniforms u = projection_uniforms(cam.proj, a.width, a.height, a.nearPlane, a.farPlane);
+    set_eye(cam, u, &a.eye[0]);
+    a.maxEig = u.maxEig;
+    a.adjFar = u.adjFar;
+    a.adjDen = u.adjDen;
     a.inputIsSRGB = config_.gaussian_color_space == GSM_COLOR_SPACE_SRGB ? 1.0f : 0.0f;
     a.shComponents = in.sh_components;
     a.count = in.gaussian_count;
@@ -294,64 +225,90 @@ gsm_status DepthFirstRenderer::renderStereoSbs(hipStream_t s, const gsm_gaussian
     a.tilesY = (height + kDfTile - 1) / kDfTile;
     a.tileCount = a.tilesX * a.tilesY;
     a.maxInstances = maxInstances_;
-    const uint32_t k = in.sh_components;
-    const uint32_t deg = k <= 1 ? 0u : (k <= 4 ? 1u : (k <= 9 ? 2u : 3u));
-    const bool half = config_.precision == GSM_PRECISION_FLOAT16;
-    const uint32_t nb = (a.count + kDfBlock - 1) / kDfBlock;
+    return a;
+}
 
-    // The blend schedule only needs the previous frame's walk lengths: one extra workgroup of the
-    // projection launch orders the units while the others project (no side stream, no join).
-    const bool costOrder = tuning_.costOrder;
-    a.schedUnits = costOrder ? 2u * a.tileCount : 0u;
-    {
-        const uint64_t key = ((uint64_t)a.tilesX << 32) | a.tilesY;
-        if (key != schedKey_) {  // costs of another geometry: start from index order
-            hipMemsetAsync(A_.unitCost, 0, (size_t)a.tileCount * 2 * sizeof(uint16_t), s);
-            hipMemsetAsync(A_.costMax, 0, kCostMaxSlots * sizeof(uint32_t), s);
-            schedKey_ = key;
-        }
-    }
-    const bool prof = (profiling_ & 1) != 0;                   // every stage bracketed
-    // only the blend's pair of events, on every frame or every period-th (bits 8-15)
-    const uint32_t period = ((uint32_t)profiling_ >> 8) & 0xFFu;
-    const bool blendOnly = !prof && (profiling_ & 8) != 0 && (period <= 1 || (sampleFrame_++ % period) == 0);
-    hipEvent_t* ev = (prof || blendOnly) ? frameEvents(profFrames_) : nullptr;
-    if (prof) hipEventRecord(ev[0], s);
-    df_launch_project(half, deg, in.gaussians, in.harmonics, a, A_, s);
+template <class Project, class Expand, class BeforeBlend, class Blend>
+gsm_status DepthFirstRenderer::runFrame(hipStream_t s, const DfArgs& a, bool mono, Project&& project, Expand&& expand,
+                                        BeforeBlend&& beforeBlend, Blend&& blend) {
+    const uint32_t nb = (a.count + kDfBlock - 1) / kDfBlock;
+    timer_.beginFrame();
+    timer_.record(0, s);
+    project();
     launch_scan_sums(A_.blockSums, nb, maxGaussians_, A_.visHdr, A_.queue, s);
     df_launch_compact(a, A_, s, key16_);
-    if (prof) hipEventRecord(ev[1], s);
+    timer_.record(1, s);
     const int dc = sortDepth(s);
     if (dc == kSortNoSpace) return GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;  // (nothing of the sort launched)
-    if (prof) hipEventRecord(ev[2], s);
+    timer_.record(2, s);
     df_launch_instance_counts(A_.dvals[dc], a, A_, s);
     launch_scan_sums(A_.instSums, nb, maxInstances_, A_.instHdr, A_.queue, s);
-    df_launch_instances(A_.dvals[dc], a, A_, s, tile32_);  // with the blend's skip flags
-    if (prof) hipEventRecord(ev[3], s);
+    expand(A_.dvals[dc]);
+    timer_.record(3, s);
     const int ic = sortTiles(a, s);
     if (ic == kSortNoSpace) return GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;
-    // Blend schedule: (tile, eye) units handed out longest first by the walk lengths the previous
-    // frame of the same geometry measured (the image does not depend on the order, only the load
-    // balance does).  Tuning::costOrder false (GSM_BLEND_SCHED=0 at create): index order.
-
-    A_.blendStats = (profiling_ & 2) ? statsBuf_ : nullptr;
-    if (A_.blendStats) hipMemsetAsync(statsBuf_, 0, 4 * sizeof(unsigned long long), s);
-    if (prof || blendOnly) hipEventRecord(ev[4], s);
-    df_launch_blend(A_.ivals[ic], a, A_, color, pitch, fmt, numCUs_, costOrder, s);
-    if (prof || blendOnly) {
-        hipEventRecord(ev[5], s);
-        profFrames_++;
-    }
+    beforeBlend();
+    timer_.record(4, s, true);
+    blend(A_.ivals[ic]);
+    timer_.record(5, s, true);
+    timer_.frameDone();
     lastCount_ = a.count;
     lastTilesX_ = a.tilesX;
     lastTilesY_ = a.tilesY;
-    lastMono_ = false;
+    lastMono_ = mono;
     depthOrder_ = A_.dvals[dc];
     sortedDepthKeys_ = A_.dkeys[dc];
     instTiles_ = A_.ikeys[ic];
     instGids_ = A_.ivals[ic];
     if (hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;
     return GSM_OK;
+}
+
+gsm_status DepthFirstRenderer::renderStereoSbs(hipStream_t s, const gsm_gaussian_input& in,
+                                               const gsm_camera_params& left, const gsm_camera_params& right,
+                                               const float* scene, uint32_t width, uint32_t height, void* color,
+                                               size_t pitch) {
+    (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's: the launches below are checked)
+    // encodeStereoPipeline guards (DepthFirstRenderer.swift:478, 607) -- errors, not a silent skip
+    const gsm_status st = validate_frame(config_, maxGaussians_, maxWidth_, maxHeight_, in.gaussian_count, true,
+                                         !in.gaussians || !in.harmonics, width, height, color, pitch, 2, nullptr, 0);
+    if (st != GSM_OK) return st;
+    if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
+
+    DfArgs a = frameArgs(in, left, width, height);
+    set_eye(right, projection_uniforms(right.proj, a.width, a.height, a.nearPlane, a.farPlane), &a.eye[1]);
+    static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    std::memcpy(a.scene, scene ? scene : kIdentity, sizeof(a.scene));
+    {  // length(sceneTransform[0].xyz) (DepthFirstShaders.metal:293)
+        float d = a.scene[0] * a.scene[0] + a.scene[1] * a.scene[1];
+        d = d + a.scene[2] * a.scene[2];
+        a.sceneScale = std::sqrt(d);
+    }
+    for (int i = 0; i < 3; ++i) a.mid[i] = (left.position[i] + right.position[i]) * 0.5f;
+    // Blend schedule: (tile, eye) units handed out longest first by the walk lengths the previous
+    // frame of the same geometry measured (the image does not depend on the order, only the load
+    // balance does).  Tuning::costOrder false (GSM_BLEND_SCHED=0 at create): index order.
+    // The schedule only needs the previous frame's walk lengths: one extra workgroup of the
+    // projection launch orders the units while the others project (no side stream, no join).
+    const bool costOrder = tuning_.costOrder;
+    a.schedUnits = costOrder ? 2u * a.tileCount : 0u;
+    const uint64_t key = ((uint64_t)a.tilesX << 32) | a.tilesY;
+    if (key != schedKey_) {  // costs of another geometry: start from index order
+        hipMemsetAsync(A_.unitCost, 0, (size_t)a.tileCount * 2 * sizeof(uint16_t), s);
+        hipMemsetAsync(A_.costMax, 0, kCostMaxSlots * sizeof(uint32_t), s);
+        schedKey_ = key;
+    }
+    const uint32_t deg = sh_degree(in.sh_components);
+    const bool half = config_.precision == GSM_PRECISION_FLOAT16;
+    const int fmt = (int)config_.color_format;
+    return runFrame(
+        s, a, false, [&] { df_launch_project(half, deg, in.gaussians, in.harmonics, a, A_, s); },
+        [&](const uint32_t* order) { df_launch_instances(order, a, A_, s, tile32_); },  // with the blend's skip flags
+        [&] {
+            A_.blendStats = (timer_.flags() & 2) ? statsBuf_ : nullptr;
+            if (A_.blendStats) hipMemsetAsync(statsBuf_, 0, 4 * sizeof(unsigned long long), s);
+        },
+        [&](const uint32_t* gids) { df_launch_blend(gids, a, A_, color, pitch, fmt, dev_.numCUs, costOrder, s); });
 }
 
 // DepthFirstRenderer.render -> encodeRender (DepthFirstRenderer.swift:166-203, 237-465) on the same
@@ -364,83 +321,28 @@ gsm_status DepthFirstRenderer::renderMono(hipStream_t s, const gsm_gaussian_inpu
                                           size_t depthPitch) {
     (void)hipGetLastError();
     // encodeRender's guard (:249) and the texture sizes -- errors, not a silent return
-    if (in.gaussian_count == 0 || in.gaussian_count > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
-    if (width == 0 || height == 0 || width > maxWidth_ || height > maxHeight_) return GSM_ERR_INVALID_DIMENSIONS;
-    if (!color || !in.gaussians || !in.harmonics) return GSM_ERR_MISSING_REQUIRED_BUFFER;
-    const int fmt = (int)config_.color_format;
-    const size_t bpp = fmt == GSM_COLOR_FORMAT_RGBA16F ? 8 : (fmt == GSM_COLOR_FORMAT_RGBA32F ? 16 : 4);
-    if (pitch < (size_t)width * bpp) return GSM_ERR_INVALID_BUFFER_SIZE;
-    if ((((uintptr_t)color) & 3u) || (pitch & 3u)) return GSM_ERR_INVALID_BUFFER_SIZE;
-    if (depth && (depthPitch < (size_t)width * 2 || (depthPitch & 1u) || (((uintptr_t)depth) & 1u)))
-        return GSM_ERR_INVALID_BUFFER_SIZE;
-    if (hipSetDevice(device_) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
+    const gsm_status st = validate_frame(config_, maxGaussians_, maxWidth_, maxHeight_, in.gaussian_count, false,
+                                         !in.gaussians || !in.harmonics, width, height, color, pitch, 1, depth,
+                                         depthPitch);
+    if (st != GSM_OK) return st;
+    if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
 
-    DfArgs a;
-    std::memset(&a, 0, sizeof(a));
-    const float W = (float)width, H = (float)height;
     // CameraUniforms(from: camera, ...) (KernelTypes.swift:107-123)
-    eye_const(cam, W, H, &a.eye[0]);
-    a.width = W;
-    a.height = H;
-    a.nearPlane = cam.near_plane;
-    a.farPlane = cam.far_plane;
-    const float maxDim = std::fmax(W, H);
-    const float maxEig = (maxDim * 2.0f) / 3.0f;
-    a.maxEig = maxEig * maxEig;
-    a.adjFar = a.farPlane * 0.02f;
-    a.adjDen = a.adjFar - a.nearPlane;
+    DfArgs a = frameArgs(in, cam, width, height);
     for (int i = 0; i < 3; ++i) a.mid[i] = cam.position[i];
-    a.inputIsSRGB = config_.gaussian_color_space == GSM_COLOR_SPACE_SRGB ? 1.0f : 0.0f;
-    a.shComponents = in.sh_components;
-    a.count = in.gaussian_count;
-    // buildBinningParams(gaussianCount:width:height:) on 16x16 tiles (GlobalRenderer.swift:54-70)
-    a.tilesX = (width + kDfTile - 1) / kDfTile;
-    a.tilesY = (height + kDfTile - 1) / kDfTile;
-    a.tileCount = a.tilesX * a.tilesY;
-    a.maxInstances = maxInstances_;
-    const uint32_t k = in.sh_components;
-    const uint32_t deg = k <= 1 ? 0u : (k <= 4 ? 1u : (k <= 9 ? 2u : 3u));
+    const uint32_t deg = sh_degree(in.sh_components);
     const bool half = config_.precision == GSM_PRECISION_FLOAT16;
-    const uint32_t nb = (a.count + kDfBlock - 1) / kDfBlock;
-
-    const bool prof = (profiling_ & 1) != 0;
-    const uint32_t period = ((uint32_t)profiling_ >> 8) & 0xFFu;
-    const bool blendOnly = !prof && (profiling_ & 8) != 0 && (period <= 1 || (sampleFrame_++ % period) == 0);
-    hipEvent_t* ev = (prof || blendOnly) ? frameEvents(profFrames_) : nullptr;
-    if (prof) hipEventRecord(ev[0], s);
-    df_launch_project_mono(half, deg, in.gaussians, in.harmonics, a, A_, s);
-    launch_scan_sums(A_.blockSums, nb, maxGaussians_, A_.visHdr, A_.queue, s);
-    df_launch_compact(a, A_, s, key16_);
-    if (prof) hipEventRecord(ev[1], s);
-    const int dc = sortDepth(s);
-    if (dc == kSortNoSpace) return GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;
-    if (prof) hipEventRecord(ev[2], s);
-    df_launch_instance_counts(A_.dvals[dc], a, A_, s);
-    launch_scan_sums(A_.instSums, nb, maxInstances_, A_.instHdr, A_.queue, s);
-    df_launch_instances_mono(A_.dvals[dc], a, A_, s, tile32_);
-    if (prof) hipEventRecord(ev[3], s);
-    const int ic = sortTiles(a, s);
-    if (ic == kSortNoSpace) return GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;
-    if (prof || blendOnly) hipEventRecord(ev[4], s);
-    df_launch_blend_mono(A_.ivals[ic], a, A_, color, pitch, fmt, depth, depthPitch, numCUs_, s);
-    if (prof || blendOnly) {
-        hipEventRecord(ev[5], s);
-        profFrames_++;
-    }
-    lastCount_ = a.count;
-    lastTilesX_ = a.tilesX;
-    lastTilesY_ = a.tilesY;
-    lastMono_ = true;
-    depthOrder_ = A_.dvals[dc];
-    sortedDepthKeys_ = A_.dkeys[dc];
-    instTiles_ = A_.ikeys[ic];
-    instGids_ = A_.ivals[ic];
-    if (hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;
-    return GSM_OK;
+    const int fmt = (int)config_.color_format;
+    return runFrame(
+        s, a, true, [&] { df_launch_project_mono(half, deg, in.gaussians, in.harmonics, a, A_, s); },
+        [&](const uint32_t* order) { df_launch_instances_mono(order, a, A_, s, tile32_); }, [] {},
+        [&](const uint32_t* gids) {
+            df_launch_blend_mono(gids, a, A_, color, pitch, fmt, depth, depthPitch, dev_.numCUs, s);
+        });
 }
 
 gsm_status DepthFirstRenderer::counters(gsm_depthfirst_counters* out) {
-    hipSetDevice(device_);
+    hipSetDevice(dev_.id);
     TileAssignmentHeader v, i;
     if (hipMemcpy(&v, A_.visHdr, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(&i, A_.instHdr, sizeof(i), hipMemcpyDeviceToHost) != hipSuccess)
@@ -473,38 +375,15 @@ gsm_status DepthFirstRenderer::debugCopy(int which, void* dst, size_t bytes, siz
         case GSM_DF_BUF_INSTANCE_TILES: src = instTiles_; full = (size_t)c.total_instances * 4; break;
         case GSM_DF_BUF_INSTANCE_GAUSSIANS: src = instGids_; full = (size_t)c.total_instances * 4; break;
         case GSM_DF_BUF_HEADERS: full = (size_t)c.tile_count * 8; break;
-        case GSM_DF_BUF_BLEND_STATS: src = (profiling_ & 2) ? statsBuf_ : nullptr; full = 32; break;
+        case GSM_DF_BUF_BLEND_STATS: src = (timer_.flags() & 2) ? statsBuf_ : nullptr; full = 32; break;
         default: return GSM_ERR_INVALID_ARGUMENT;
     }
     if (needed) *needed = full;
     if (!dst || bytes == 0 || full == 0) return GSM_OK;
     const size_t cpy = bytes < full ? bytes : full;
-    if (which == GSM_DF_BUF_BOUNDS) {  // short4 on the device, int4 in the reference buffer
-        std::vector<short4> b(n);
-        if (hipMemcpy(b.data(), A_.bounds, n * sizeof(short4), hipMemcpyDeviceToHost) != hipSuccess)
-            return GSM_ERR_RENDER_FAILED;
-        std::vector<int32_t> w(n * 4);
-        for (size_t i = 0; i < n; ++i) {
-            w[4 * i] = b[i].x;
-            w[4 * i + 1] = b[i].y;
-            w[4 * i + 2] = b[i].z;
-            w[4 * i + 3] = b[i].w;
-        }
-        std::memcpy(dst, w.data(), cpy);
-        return GSM_OK;
-    }
-    if (which == GSM_DF_BUF_HEADERS) {  // GaussianHeader {offset, count} from the run starts
-        std::vector<uint32_t> st((size_t)c.tile_count + 1);
-        if (hipMemcpy(st.data(), A_.starts, st.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
-            return GSM_ERR_RENDER_FAILED;
-        std::vector<uint32_t> h((size_t)c.tile_count * 2);
-        for (size_t t = 0; t < c.tile_count; ++t) {
-            h[2 * t] = st[t];
-            h[2 * t + 1] = st[t + 1] - st[t];
-        }
-        std::memcpy(dst, h.data(), cpy);
-        return GSM_OK;
-    }
+    // short4 on the device, int4 in the reference buffer; GaussianHeader {offset, count} from the run starts
+    if (which == GSM_DF_BUF_BOUNDS) return copy_bounds_int4(A_.bounds, n, dst, bytes);
+    if (which == GSM_DF_BUF_HEADERS) return copy_headers(A_.starts, c.tile_count, dst, bytes);
     if (!src) return GSM_ERR_RENDER_FAILED;
     if (hipMemcpy(dst, src, cpy, hipMemcpyDeviceToHost) != hipSuccess) return GSM_ERR_RENDER_FAILED;
     if (which == GSM_DF_BUF_INSTANCE_GAUSSIANS) {  // drop the blend's skip flags (kDfSkipShift)
@@ -515,62 +394,17 @@ gsm_status DepthFirstRenderer::debugCopy(int which, void* dst, size_t bytes, siz
 }
 
 gsm_status DepthFirstRenderer::setProfiling(int flags) {
-    hipSetDevice(device_);
+    hipSetDevice(dev_.id);
     if ((flags & 2) && !statsBuf_) {
-        gsm_status st = alloc((void**)&statsBuf_, 4 * sizeof(unsigned long long));
+        gsm_status st = allocs_.alloc((void**)&statsBuf_, 4 * sizeof(unsigned long long));
         if (st != GSM_OK) return st;
     }
-    if ((flags & 9) && events_.empty()) {  // bit 0: every stage, bit 3: the blend only
-        events_.assign((size_t)kRing * (GSM_DF_STAGE_COUNT + 1), nullptr);
-        for (auto& e : events_)
-            if (hipEventCreate(&e) != hipSuccess) return GSM_ERR_ENCODER_CREATION_FAILED;
-    }
-    profiling_ = flags;
-    profFrames_ = 0;
-    sampleFrame_ = 0;
-    return GSM_OK;
-}
-
-gsm_status DepthFirstRenderer::stageTimes(float* ms, int n) {
-    if (profFrames_ == 0 || events_.empty()) return GSM_ERR_RENDER_FAILED;
-    hipSetDevice(device_);
-    if (hipEventSynchronize(frameEvents(profFrames_ - 1)[GSM_DF_STAGE_COUNT]) != hipSuccess)
-        return GSM_ERR_RENDER_FAILED;
-    const uint32_t frames = profFrames_ < (uint32_t)kRing ? profFrames_ : (uint32_t)kRing;
-    const bool blendOnly = (profiling_ & 1) == 0;
-    for (int i = 0; i < n && i < GSM_DF_STAGE_COUNT; ++i) {
-        if (blendOnly && i != GSM_DF_STAGE_BLEND) {
-            ms[i] = 0.0f;
-            continue;
-        }
-        double acc = 0.0;
-        for (uint32_t f = profFrames_ - frames; f < profFrames_; ++f) {
-            float t = 0.f;
-            if (hipEventElapsedTime(&t, frameEvents(f)[i], frameEvents(f)[i + 1]) != hipSuccess)
-                return GSM_ERR_RENDER_FAILED;
-            acc += t;
-        }
-        ms[i] = (float)(acc / frames);
-    }
-    return GSM_OK;
-}
-
-gsm_status DepthFirstRenderer::lastGpuTime(double* seconds) {
-    if (profFrames_ == 0 || events_.empty() || (profiling_ & 1) == 0) return GSM_ERR_RENDER_FAILED;
-    hipSetDevice(device_);
-    hipEvent_t* ev = frameEvents(profFrames_ - 1);
-    if (hipEventSynchronize(ev[GSM_DF_STAGE_COUNT]) != hipSuccess) return GSM_ERR_RENDER_FAILED;
-    float t = 0.f;
-    if (hipEventElapsedTime(&t, ev[0], ev[GSM_DF_STAGE_COUNT]) != hipSuccess) return GSM_ERR_RENDER_FAILED;
-    *seconds = (double)t * 1e-3;
-    return GSM_OK;
+    return timer_.setProfiling(flags);  // bit 0: every stage, bit 3: the blend only
 }
 
 }  // namespace gsm
 
-struct gsm_depthfirst {
-    gsm::DepthFirstRenderer* impl;
-};
+struct gsm_depthfirst : gsm::Handle<gsm::DepthFirstRenderer> {};
 
 extern "C" {
 
@@ -605,24 +439,10 @@ gsm_status gsm_depthfirst_create_with_options(const gsm_renderer_config* config,
             return GSM_ERR_INVALID_ARGUMENT;
         opt = *options;
     }
-    gsm::DepthFirstRenderer* impl = nullptr;
-    gsm_status st = gsm::DepthFirstRenderer::create(*config, hip_device, opt, &impl);
-    if (st != GSM_OK) return st;
-    gsm_depthfirst* h = new (std::nothrow) gsm_depthfirst;
-    if (!h) {
-        delete impl;
-        return GSM_ERR_FAILED_TO_ALLOCATE_BUFFER;
-    }
-    h->impl = impl;
-    *out = h;
-    return GSM_OK;
+    return gsm_depthfirst::create(out, *config, hip_device, opt);
 }
 
-void gsm_depthfirst_destroy(gsm_depthfirst* r) {
-    if (!r) return;
-    delete r->impl;
-    delete r;
-}
+void gsm_depthfirst_destroy(gsm_depthfirst* r) { gsm_depthfirst::destroy(r); }
 
 gsm_status gsm_depthfirst_render_stereo_sbs(gsm_depthfirst* r, void* stream, const gsm_gaussian_input* input,
                                             const gsm_camera_params* left, const gsm_camera_params* right,

@@ -3,10 +3,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <vector>
-
 #include "../../include/gsm_debug.h"
 #include "../../include/gsm_renderer.h"
+#include "gsm_host.h"
 #include "gsm_internal.h"
 
 namespace gsm {
@@ -15,7 +14,7 @@ class GlobalRenderer {
    public:
     // GlobalRenderer.init(device:config:) (GlobalRenderer.swift:110-193)
     static gsm_status create(const gsm_renderer_config& cfg, int hipDevice, GlobalRenderer** out);
-    ~GlobalRenderer();
+    ~GlobalRenderer() { hipSetDevice(dev_.id); }  // (the events and buffers are released on their device)
 
     // GlobalRenderer.render (GlobalRenderer.swift:201-238)
     gsm_status render(hipStream_t stream, const gsm_gaussian_input& input,
@@ -62,26 +61,28 @@ class GlobalRenderer {
     uint32_t tilesY() const { return tilesY_; }
     uint32_t maxWidth() const { return maxWidth_; }
     uint32_t maxHeight() const { return maxHeight_; }
-    uint32_t colorBytesPerPixel() const {
-        return config_.color_format == GSM_COLOR_FORMAT_RGBA16F ? 8u
-               : (config_.color_format == GSM_COLOR_FORMAT_RGBA32F ? 16u : 4u);
-    }
+    uint32_t colorBytesPerPixel() const { return color_bytes_per_pixel(config_.color_format); }
     bool halfPrecision() const { return config_.precision == GSM_PRECISION_FLOAT16; }
 
     gsm_status counters(gsm_debug_counters* out);
     int lastBlendKernel() const { return lastBlendKernel_; }
     gsm_status debugCopy(int which, void* dst, size_t bytes, size_t* needed);
     gsm_status setProfiling(int flags);  // bit0: stage events, bit1: keep unsorted keys
-    gsm_status stageTimes(float* ms, int n);
-    gsm_status lastGpuTime(double* seconds);
+    gsm_status stageTimes(float* ms, int n) {
+        hipSetDevice(dev_.id);
+        return timer_.stageTimes(ms, n, GSM_STAGE_BLEND);
+    }
+    gsm_status lastGpuTime(double* seconds) {
+        hipSetDevice(dev_.id);
+        return timer_.lastGpuTime(seconds);
+    }
     // the renderer's tile rows: begin, begin + stride, ... < end (0, 0: the whole frame)
     gsm_status setTileRows(uint32_t begin, uint32_t end, uint32_t stride = 1);
     uint32_t rowCount() const { return rowEnd_ > rowBegin_ ? (rowEnd_ - rowBegin_ + rowStride_ - 1) / rowStride_ : 0u; }
-    int device() const { return device_; }
+    int device() const { return dev_.id; }
 
    private:
     GlobalRenderer() = default;
-    gsm_status alloc(void** p, size_t bytes);
     ProjectArgs frameArgs(const gsm_camera_params& camera, uint32_t width, uint32_t height, uint32_t count,
                           uint32_t shComponents) const;
     // scan, scatter, sort, headers and blend after `front` filled the per-gaussian arrays
@@ -113,11 +114,9 @@ class GlobalRenderer {
                                 uint32_t height, uint32_t first, uint32_t count, const uint32_t* slabRows,
                                 uint32_t numSlabs, bool needSend, const void* send, const uint32_t* sendCounts,
                                 PartitionFrame* f, bool interleave = false);
-    void release();
     int sortPassCount() const;
 
-    int device_ = -1;
-    int numCUs_ = 256;
+    Device dev_;
     gsm_renderer_config config_{};
     Tuning tuning_{};  // A/B switches, read once at create
     uint32_t maxGaussians_ = 1, maxWidth_ = 1, maxHeight_ = 1;
@@ -125,16 +124,10 @@ class GlobalRenderer {
     uint32_t rowBegin_ = 0, rowEnd_ = 1, rowStride_ = 1;
     uint32_t maxAssignments_ = 4;
     DeviceArena arena_;
-    std::vector<void*> allocations_;
-    static constexpr int kEventRing = 128;  // frames of stage events kept for averaging
-    std::vector<hipEvent_t> events_;       // [kEventRing][GSM_STAGE_COUNT + 1]
-    uint32_t profFrames_ = 0;
-    uint32_t sampleFrame_ = 0;  // frames since setProfiling (blend-event sampling)
-    hipEvent_t* frameEvents(uint32_t frame) { return &events_[(frame % kEventRing) * (GSM_STAGE_COUNT + 1)]; }
-    int profiling_ = 0;
+    DeviceAllocations allocs_;
+    StageTimer timer_{GSM_STAGE_COUNT, 128};  // the last 128 profiled frames are averaged
     int lastBlendKernel_ = 0;  // gsm_blend_kernel of the last enqueued frame (gsm_global_debug_blend_kernel)
     bool keptRenderData_ = false;  // the last frame wrote GaussianRenderData for readback
-    bool haveTimes_ = false;
     uint32_t lastCount_ = 0, lastWidth_ = 0, lastHeight_ = 0;
     const uint32_t* sortedKeys_ = nullptr;
     const uint32_t* sortedVals_ = nullptr;
@@ -146,6 +139,4 @@ class GlobalRenderer {
 
 }  // namespace gsm
 
-struct gsm_renderer {
-    gsm::GlobalRenderer* impl;
-};
+struct gsm_renderer : gsm::Handle<gsm::GlobalRenderer> {};

@@ -364,25 +364,32 @@ def _stream_handle(stream) -> Optional[int]:
     return int(stream.cuda_stream)
 
 
-class GlobalRenderer:
-    """GlobalRenderer (GlobalRenderer.swift:72-572) on one HIP device."""
+class _Renderer:
+    """What the single-device renderers share over their C entry points <_PREFIX>_*: the handle's
+    life, the stage times, the counters and the raw two-call debug copy."""
+    _PREFIX = ""       # gsm_global | gsm_depthfirst | gsm_local
+    _STAGE_NAMES = ()  # stage_times_ms keys, in the C enum's order
+    _COUNTERS = None   # the ctypes struct <_PREFIX>_debug_counters fills
 
-    def __init__(self, device: Optional[int] = None, config: RendererConfig = RendererConfig()):
-        L = _lib()
+    def _fn(self, name: str):
+        return getattr(_lib(), f"{self._PREFIX}_{name}")
+
+    def _open(self, device: Optional[int], config: RendererConfig, create: str = "create", *options):
+        """<_PREFIX>_<create>(config, device, *options, &handle)"""
         self.config = config
         cfg = _Config(int(config.max_gaussians), int(config.max_width), int(config.max_height),
                       int(config.precision), int(config.color_format),
                       int(config.gaussian_color_space), int(bool(config.back_to_front)))
         h = C.c_void_p()
         dev = -1 if device is None else int(device)
-        _check(L.gsm_global_create(C.byref(cfg), dev, C.byref(h)), "gsm_global_create")
+        _check(self._fn(create)(C.byref(cfg), dev, *options, C.byref(h)), f"{self._PREFIX}_{create}")
         self._h = h
         self.device = dev
         self._bpp = ColorFormat(int(config.color_format)).bytes_per_pixel
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
-            _lib().gsm_global_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):  # pragma: no cover
@@ -390,6 +397,41 @@ class GlobalRenderer:
             self.close()
         except Exception:
             pass
+
+    @property
+    def last_gpu_time(self) -> Optional[float]:
+        s = C.c_double()
+        st = self._fn("last_gpu_time")(self._h, C.byref(s))
+        return float(s.value) if st == 0 else None
+
+    def stage_times_ms(self) -> dict:
+        arr = (C.c_float * len(self._STAGE_NAMES))()
+        _check(self._fn("stage_times")(self._h, arr, len(arr)), f"{self._PREFIX}_stage_times")
+        return {k: float(v) for k, v in zip(self._STAGE_NAMES, arr)}
+
+    def counters(self) -> dict:
+        c = self._COUNTERS()
+        _check(self._fn("debug_counters")(self._h, C.byref(c)), f"{self._PREFIX}_debug_counters")
+        return {name: int(getattr(c, name)) for name, _ in c._fields_}
+
+    def _debug_copy(self, which) -> np.ndarray:
+        """The bytes of buffer `which`: one call for the size, one for the copy."""
+        copy = self._fn("debug_copy")
+        need = C.c_size_t()
+        _check(copy(self._h, int(which), None, 0, C.byref(need)), "debug_copy")
+        n = int(need.value)
+        raw = np.zeros(max(n, 1), np.uint8)
+        if n:
+            _check(copy(self._h, int(which), raw.ctypes.data, n, None), "debug_copy")
+        return raw[:n]
+
+
+class GlobalRenderer(_Renderer):
+    """GlobalRenderer (GlobalRenderer.swift:72-572) on one HIP device."""
+    _PREFIX, _STAGE_NAMES, _COUNTERS = "gsm_global", STAGES, _Counters
+
+    def __init__(self, device: Optional[int] = None, config: RendererConfig = RendererConfig()):
+        self._open(device, config)
 
     # -- GlobalRenderer.render (GlobalRenderer.swift:201-238) --
     def render(self, color_texture, depth_texture, input: GaussianInput, camera: CameraParams,
@@ -488,12 +530,6 @@ class GlobalRenderer:
     def debug_read_total_assignments(self) -> int:
         return int(_lib().gsm_global_debug_read_total_assignments(self._h))
 
-    @property
-    def last_gpu_time(self) -> Optional[float]:
-        s = C.c_double()
-        st = _lib().gsm_global_last_gpu_time(self._h, C.byref(s))
-        return float(s.value) if st == 0 else None
-
     # -- introspection (include/gsm_debug.h) --
     def set_profiling(self, stage_events: bool = True, keep_unsorted: bool = False,
                       blend_trace: bool = False, blend_events: bool = False, blend_event_period: int = 1,
@@ -506,11 +542,6 @@ class GlobalRenderer:
             ((max(1, min(255, int(blend_event_period))) & 0xFF) << 8)
         _check(_lib().gsm_global_set_profiling(self._h, flags), "gsm_global_set_profiling")
 
-    def stage_times_ms(self) -> dict:
-        arr = (C.c_float * len(STAGES))()
-        _check(_lib().gsm_global_stage_times(self._h, arr, len(STAGES)), "gsm_global_stage_times")
-        return {k: float(v) for k, v in zip(STAGES, arr)}
-
     def set_tile_rows(self, begin: int, end: int):
         _check(_lib().gsm_global_set_tile_rows(self._h, int(begin), int(end)), "gsm_global_set_tile_rows")
 
@@ -520,20 +551,8 @@ class GlobalRenderer:
         _check(_lib().gsm_global_debug_blend_kernel(self._h, C.byref(k)), "gsm_global_debug_blend_kernel")
         return BLEND_KERNELS[k.value]
 
-    def counters(self) -> dict:
-        c = _Counters()
-        _check(_lib().gsm_global_debug_counters(self._h, C.byref(c)), "gsm_global_debug_counters")
-        return {name: int(getattr(c, name)) for name, _ in _Counters._fields_}
-
     def copy_buffer(self, which: BufferId) -> np.ndarray:
-        L = _lib()
-        need = C.c_size_t()
-        _check(L.gsm_global_debug_copy(self._h, int(which), None, 0, C.byref(need)), "debug_copy")
-        n = int(need.value)
-        raw = np.zeros(max(n, 1), np.uint8)
-        if n:
-            _check(L.gsm_global_debug_copy(self._h, int(which), raw.ctypes.data, n, None), "debug_copy")
-        raw = raw[:n]
+        raw = self._debug_copy(which)
         if which == BufferId.RENDER_DATA:
             return raw.view(RENDER_DATA)
         if which == BufferId.BOUNDS:
@@ -574,28 +593,18 @@ STEREO_RENDER_DATA = np.dtype([(f, "<u2") for f in (
      ("centerDepth", "<u2"), ("pad0", "<u2")])
 
 
-class DepthFirstRenderer:
+class DepthFirstRenderer(_Renderer):
     """DepthFirstRenderer (DepthFirstRenderer.swift:11-831) on one HIP device: the mono frame
     (render, :166-203, 237-465) and the stereo side-by-side path (renderStereo(target:
     .sideBySide), :205-223, 469-512).  renderStereo(.foveated) is out of scope.
     depth_key_bits (16 | 32) and tile_id_bits (16 | 32) are depthSortKeyPrecision and tileIdPrecision
     of DepthFirstRenderer.init (:45-50), fixed for the life of the renderer (include/gsm_depthfirst.h)."""
+    _PREFIX, _STAGE_NAMES, _COUNTERS = "gsm_depthfirst", DF_STAGES, _DfCounters
 
     def __init__(self, device: Optional[int] = None, config: RendererConfig = RendererConfig(),
                  depth_key_bits: int = 32, tile_id_bits: int = 16):
-        L = _lib()
-        self.config = config
-        cfg = _Config(int(config.max_gaussians), int(config.max_width), int(config.max_height),
-                      int(config.precision), int(config.color_format),
-                      int(config.gaussian_color_space), int(bool(config.back_to_front)))
-        h = C.c_void_p()
-        dev = -1 if device is None else int(device)
         opt = _DfOptions(C.sizeof(_DfOptions), int(depth_key_bits), int(tile_id_bits), 0)
-        _check(L.gsm_depthfirst_create_with_options(C.byref(cfg), dev, C.byref(opt), C.byref(h)),
-               "gsm_depthfirst_create_with_options")
-        self._h = h
-        self.device = dev
-        self._bpp = ColorFormat(int(config.color_format)).bytes_per_pixel
+        self._open(device, config, "create_with_options", C.byref(opt))
         self._last_mono = False  # the last frame was a mono frame (copy_buffer's record dtype)
 
     @property
@@ -604,11 +613,6 @@ class DepthFirstRenderer:
         o = _DfOptions()
         _check(_lib().gsm_depthfirst_get_options(self._h, C.byref(o)), "gsm_depthfirst_get_options")
         return {"depth_key_bits": int(o.depth_key_bits), "tile_id_bits": int(o.tile_id_bits)}
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            _lib().gsm_depthfirst_destroy(self._h)
-            self._h = C.c_void_p()
 
     # -- DepthFirstRenderer.render (DepthFirstRenderer.swift:166-203) --
     def render(self, color_texture, depth_texture, input: GaussianInput, camera: CameraParams,
@@ -626,12 +630,6 @@ class DepthFirstRenderer:
                                           _ptr(depth_texture), dp)
         _check(st, "gsm_depthfirst_render")
         self._last_mono = True
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def render_stereo_sbs(self, color_texture, input: GaussianInput, left: CameraParams, right: CameraParams,
                           width_per_eye: int, height: int, scene_transform=None, stream=None,
@@ -651,37 +649,14 @@ class DepthFirstRenderer:
         _check(st, "gsm_depthfirst_render_stereo_sbs")
         self._last_mono = False
 
-    @property
-    def last_gpu_time(self) -> Optional[float]:
-        s = C.c_double()
-        st = _lib().gsm_depthfirst_last_gpu_time(self._h, C.byref(s))
-        return float(s.value) if st == 0 else None
-
     def set_profiling(self, stage_events: bool = True, blend_events: bool = False, blend_stats: bool = False,
                       blend_event_period: int = 1):
         flags = (1 if stage_events else 0) | (2 if blend_stats else 0) | (8 if blend_events else 0) | \
             ((max(1, min(255, int(blend_event_period))) & 0xFF) << 8)
         _check(_lib().gsm_depthfirst_set_profiling(self._h, flags), "set_profiling")
 
-    def stage_times_ms(self) -> dict:
-        arr = (C.c_float * len(DF_STAGES))()
-        _check(_lib().gsm_depthfirst_stage_times(self._h, arr, len(DF_STAGES)), "gsm_depthfirst_stage_times")
-        return {k: float(v) for k, v in zip(DF_STAGES, arr)}
-
-    def counters(self) -> dict:
-        c = _DfCounters()
-        _check(_lib().gsm_depthfirst_debug_counters(self._h, C.byref(c)), "gsm_depthfirst_debug_counters")
-        return {name: int(getattr(c, name)) for name, _ in _DfCounters._fields_}
-
     def copy_buffer(self, which: DepthFirstBuffer) -> np.ndarray:
-        L = _lib()
-        need = C.c_size_t()
-        _check(L.gsm_depthfirst_debug_copy(self._h, int(which), None, 0, C.byref(need)), "debug_copy")
-        n = int(need.value)
-        raw = np.zeros(max(n, 1), np.uint8)
-        if n:
-            _check(L.gsm_depthfirst_debug_copy(self._h, int(which), raw.ctypes.data, n, None), "debug_copy")
-        raw = raw[:n]
+        raw = self._debug_copy(which)
         if which == DepthFirstBuffer.RENDER_DATA:  # 16-byte records after a mono frame
             return raw.view(RENDER_DATA if self._last_mono else STEREO_RENDER_DATA)
         if which == DepthFirstBuffer.BOUNDS:
@@ -705,33 +680,13 @@ LOCAL_STAGES = ("project", "scatter", "sort", "blend")  # gsm_local_stage
 LOCAL_MAX_PER_TILE = 2048  # GSM_LOCAL_MAX_PER_TILE
 
 
-class LocalRenderer:
+class LocalRenderer(_Renderer):
     """LocalRenderer (LocalRenderer.swift:6-257) on one HIP device: per-tile slot lists sorted by a 16-bit
     depth key, no global sort (include/gsm_local.h).  renderStereo is a fatalError in the reference."""
+    _PREFIX, _STAGE_NAMES, _COUNTERS = "gsm_local", LOCAL_STAGES, _LocalCounters
 
     def __init__(self, device: Optional[int] = None, config: RendererConfig = RendererConfig()):
-        L = _lib()
-        self.config = config
-        cfg = _Config(int(config.max_gaussians), int(config.max_width), int(config.max_height),
-                      int(config.precision), int(config.color_format),
-                      int(config.gaussian_color_space), int(bool(config.back_to_front)))
-        h = C.c_void_p()
-        dev = -1 if device is None else int(device)
-        _check(L.gsm_local_create(C.byref(cfg), dev, C.byref(h)), "gsm_local_create")
-        self._h = h
-        self.device = dev
-        self._bpp = ColorFormat(int(config.color_format)).bytes_per_pixel
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            _lib().gsm_local_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(device, config)
 
     # -- LocalRenderer.render (LocalRenderer.swift:83-106) --
     def render(self, color_texture, depth_texture, input: GaussianInput, camera: CameraParams,
@@ -748,34 +703,11 @@ class LocalRenderer:
                                      int(width), int(height), _ptr(color_texture), cp, _ptr(depth_texture), dp)
         _check(st, "gsm_local_render")
 
-    @property
-    def last_gpu_time(self) -> Optional[float]:
-        s = C.c_double()
-        st = _lib().gsm_local_last_gpu_time(self._h, C.byref(s))
-        return float(s.value) if st == 0 else None
-
     def set_profiling(self, stage_events: bool = True):
         _check(_lib().gsm_local_set_profiling(self._h, 1 if stage_events else 0), "set_profiling")
 
-    def stage_times_ms(self) -> dict:
-        arr = (C.c_float * len(LOCAL_STAGES))()
-        _check(_lib().gsm_local_stage_times(self._h, arr, len(LOCAL_STAGES)), "gsm_local_stage_times")
-        return {k: float(v) for k, v in zip(LOCAL_STAGES, arr)}
-
-    def counters(self) -> dict:
-        c = _LocalCounters()
-        _check(_lib().gsm_local_debug_counters(self._h, C.byref(c)), "gsm_local_debug_counters")
-        return {name: int(getattr(c, name)) for name, _ in _LocalCounters._fields_}
-
     def copy_buffer(self, which: LocalBuffer) -> np.ndarray:
-        L = _lib()
-        need = C.c_size_t()
-        _check(L.gsm_local_debug_copy(self._h, int(which), None, 0, C.byref(need)), "debug_copy")
-        n = int(need.value)
-        raw = np.zeros(max(n, 1), np.uint8)
-        if n:
-            _check(L.gsm_local_debug_copy(self._h, int(which), raw.ctypes.data, n, None), "debug_copy")
-        raw = raw[:n]
+        raw = self._debug_copy(which)
         if which == LocalBuffer.PROJECTED:
             return raw.view(PROJECTED)
         if which == LocalBuffer.TILE_LISTS:
