@@ -551,6 +551,13 @@ class GlobalRenderer(_Renderer):
         _check(_lib().gsm_global_debug_blend_kernel(self._h, C.byref(k)), "gsm_global_debug_blend_kernel")
         return BLEND_KERNELS[k.value]
 
+    def blend_kernel_kind(self) -> int:
+        """gsm_blend_kernel (include/gsm_debug.h) of the last enqueued frame: 1 quadrant units, 2 half-tile
+        units, 3 pair walk -- blend_kernel() gives the first two one name."""
+        k = C.c_int(0)
+        _check(_lib().gsm_global_debug_blend_kernel(self._h, C.byref(k)), "gsm_global_debug_blend_kernel")
+        return k.value
+
     def copy_buffer(self, which: BufferId) -> np.ndarray:
         raw = self._debug_copy(which)
         if which == BufferId.RENDER_DATA:
