@@ -81,6 +81,15 @@ gsm_status gsm_global_render(gsm_renderer* r, void* stream, const gsm_gaussian_i
                            depth, depth_pitch);
 }
 
+gsm_status gsm_global_render_views(gsm_renderer* r, void* stream, const gsm_gaussian_input* input,
+                                   const gsm_camera_params* cameras, uint32_t view_count, uint32_t width,
+                                   uint32_t height, void* color, size_t color_pitch, size_t color_view_stride,
+                                   void* depth, size_t depth_pitch, size_t depth_view_stride) {
+    if (!r || !r->impl || !input) return GSM_ERR_INVALID_ARGUMENT;
+    return r->impl->renderViews((hipStream_t)stream, *input, cameras, view_count, width, height, color, color_pitch,
+                                color_view_stride, depth, depth_pitch, depth_view_stride);
+}
+
 gsm_status gsm_global_project_partition(gsm_renderer* r, void* stream, const gsm_gaussian_input* input,
                                         const gsm_camera_params* camera, uint32_t width, uint32_t height,
                                         uint32_t first, uint32_t count, const uint32_t* slab_rows,

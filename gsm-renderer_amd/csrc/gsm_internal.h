@@ -32,6 +32,29 @@ struct ProjectArgs {
     float limX, limY, focalX, focalY, maxEig, adjFar, adjDen;
 };
 
+// A batch of views (gsm_global_render_views): what differs per view in ProjectArgs -- the
+// camera and the terms projection_uniforms derives from it.  One entry per view in a device array the
+// view-aware projection reads with a block-uniform index; everything else of ProjectArgs is the batch's.
+struct ViewArgs {
+    CameraUniforms cam;
+    float limX, limY, focalX, focalY, maxEig, adjFar, adjDen;
+    float pad;
+};
+static_assert(sizeof(ViewArgs) == 240, "ViewArgs: 15 16-B words");
+// the array is filled by kernel arguments, kViewChunk entries per launch (a kernel argument block holds 4 KiB)
+constexpr uint32_t kViewChunk = 16;
+struct ViewChunk {
+    ViewArgs v[kViewChunk];
+};
+// Item i of a batch = view * blocksPerView * 256 + gaussian id: a view's items start on a projection-block
+// boundary (the view is uniform per block), and ascending item index within a view is ascending id.
+struct ViewBatch {
+    uint32_t views = 0;
+    uint32_t blocksPerView = 0;  // ceil(count / 256)
+    uint32_t tilesPerView = 0;   // tiles of one view: ProjectArgs::bin.tilesX * tilesY (the frame's own grid)
+    const ViewArgs* args = nullptr;  // device, [views]
+};
+
 // Multi-GPU partition: tile-row boundaries of the slabs, and the 48-byte
 // record a slab owner receives per gaussian (GaussianRenderData + blend record + tile rect).
 constexpr uint32_t kMaxSlabs = 16;
@@ -205,6 +228,7 @@ struct DeviceArena {
     uint32_t* halfVals[2] = {nullptr, nullptr};  // [cap] per half tile: the tile's sorted gaussian ids whose
                                                  // skip flag for that half is clear, from the tile's start
     uint32_t* halfCount = nullptr;             // [2 * tileCount] entries of each half list (half-major)
+    ViewArgs* viewArgs = nullptr;              // [maxViews] per-view projection constants (render_views; lazily)
     uint16_t* expTable = nullptr;              // [65536]
     float2* sincosTable = nullptr;             // [kSincosEntries + 256]: sin/cos, then the byte table (det_byte_lut_entry)
 };
@@ -264,6 +288,11 @@ inline SortSpace sort_space(const DeviceArena& A) { return SortSpace{A.radixHist
 // project + cull + SH + tile count + per-block count sums (GlobalShaders.metal:19-123, 563-616)
 void launch_project(bool halfInput, uint32_t shDegree, const void* world, const void* harmonics,
                     const ProjectArgs& args, const DeviceArena& A, hipStream_t stream);
+// the same for a batch of views (k_project_views): args.count gaussians per view, vb.views views; entries
+// [first, first + n) of the device array filled from `chunk` by launch_fill_views (n <= kViewChunk)
+void launch_project_views(bool halfInput, uint32_t shDegree, const void* world, const void* harmonics,
+                          const ProjectArgs& args, const ViewBatch& vb, const DeviceArena& A, hipStream_t stream);
+void launch_fill_views(const ViewChunk& chunk, uint32_t first, uint32_t n, ViewArgs* dst, hipStream_t stream);
 // exclusive scan of the per-block sums, total + clamp into the header (GlobalShaders.metal:685-712)
 // project gaussians [0, a.count) of world/harm (already offset to the rank's range) and pack
 // the records of each slab's gaussians into `send` (slab-major, ascending id), counts to sendCounts
@@ -294,8 +323,9 @@ void launch_scan_sums(uint32_t* sums, uint32_t nb, uint32_t cap, TileAssignmentH
 // duplicate-with-keys (GlobalShaders.metal:623-678 fused with :266-295)
 // fusedScan: A.blockSums holds the unscanned block counts (no launch_scan_blocks before it); each
 // workgroup adds up the counts before its own, workgroup 0 also the total (header, blend queue)
+// views (nullable): a batch's items (k_scatter_views): tile ids v * tilesPerView + local tile
 void launch_scatter(const ProjectArgs& args, const DeviceArena& A, hipStream_t stream,
-                    const uint32_t* devCount = nullptr, bool fusedScan = false);
+                    const uint32_t* devCount = nullptr, bool fusedScan = false, const ViewBatch* views = nullptr);
 // the blend's half-tile lists from the sorted values (skip flags, k_scatter), tiles [tileBegin, +numTiles)
 void launch_half_lists(const uint32_t* sortedVals, uint32_t tileBegin, uint32_t numTiles, const DeviceArena& A,
                        uint32_t tileCount, hipStream_t stream);

@@ -298,125 +298,20 @@ __device__ __forceinline__ float2 band_of(const BlendRecordA& ra, short4 r, cons
 // the answers meet in LDS (mask bits for rects of <= 32 tiles, a counter beyond).  A thread no
 // longer walks its own rect while the rest of its wave waits, so one large rect costs its wave
 // nothing extra.  Candidate k of a gaussian is bit k of count_tiles' mask (ty-major, tx-minor).
-template <bool HALF, int DEG>
-__global__ __launch_bounds__(kProjectBlock) void k_project(
-    const void* __restrict__ world, const void* __restrict__ harm, ProjectArgs P,
-    GaussianRenderData* __restrict__ outRD, short4* __restrict__ outBounds,
-    BlendRecord* __restrict__ outRec, uint32_t* __restrict__ counts,
-    uint32_t* __restrict__ masks, uint32_t* __restrict__ blockSums, const float2* __restrict__ sincos,
-    const uint16_t* __restrict__ unitCost, uint32_t* __restrict__ unitOrder, uint32_t* __restrict__ costMax) {
-    __shared__ uint32_t lds[kProjectBlock / 64];
-    __shared__ ByteLut lut;
-    // block 0 of a scheduled launch orders the blend's units from the previous frame's walks while
-    // the other blocks project (no launch, no second stream, no join before the blend)
-    if (P.schedUnits) {
-        if (blockIdx.x == 0) {
-            __shared__ uint32_t uoBase[kUoBuckets], uoMax[kProjectBlock / 64];
-            unit_order_block<kProjectBlock>(unitCost, unitOrder, P.schedUnits, uoBase, uoMax, costMax, P.pairBucket);
-            return;
-        }
-    }
-    const uint32_t blk = blockIdx.x - (P.schedUnits ? 1u : 0u);
-    __shared__ float4 sEll[kProjectBlock];   // cmx, cmy, conic A, conic B
-    __shared__ float2 sEll2[kProjectBlock];  // conic C, level w
-    __shared__ uint32_t sOff[kProjectBlock];  // exclusive candidate offsets
-    __shared__ uint32_t sRect[kProjectBlock]; // x0 | rw << 16
-    __shared__ int sTy0[kProjectBlock];
-    __shared__ uint32_t sMask[kProjectBlock];
-    __shared__ uint32_t sMore[kProjectBlock];  // hits among candidates >= 32 (large rects)
-    // the block's first kCandCap candidates: owner << 8 | k for rects of <= kCandRect tiles,
-    // kSearch for the candidates of larger rects (their owner comes from a binary search).  (r06: 8 waves
-    // per SIMD -- 3072 candidates and a 64-VGPR cap -- measured no faster than 7, profiles/r06_proj_ab.txt)
-    constexpr uint32_t kCandCap = 4096, kCandRect = 64;
-    constexpr uint16_t kSearch = 0xFFFFu;
-    __shared__ uint16_t sCand[kCandCap];
-    uint4 preW[2];
-    preload_world<HALF>(world, blk * kProjectBlock + threadIdx.x, P.count, preW);
-    fill_byte_lut(lut, sincos);
-    const uint32_t tid = threadIdx.x;
-    const uint32_t gid = blk * kProjectBlock + tid;
-    ProjOut o;
-    o.vis = false;
-    o.countable = false;
-    o.bounds = make_short4(0, -1, 0, -1);
-    uint32_t area = 0;
-    int ty0 = 0;
-    if (gid < P.count) {
-        o = project_gaussian<HALF, DEG>(world, harm, gid, P, sincos, lut, HALF ? preW : nullptr);
-        outBounds[gid] = o.bounds;
-        if (o.vis) {
-            // GaussianRenderData: the frame itself only reads it for rects the scatter re-tests
-            const int ry0 = max((int)o.bounds.z, (int)P.rowBegin), ry1 = min((int)o.bounds.w, (int)P.rowEnd - 1);
-            if (P.keepRenderData || (ry1 - ry0 + 1) * ((int)o.bounds.y - (int)o.bounds.x + 1) > kMaskTiles)
-                *(uint4*)(outRD + gid) = o.rd;
-            if (o.countable && ry1 >= ry0) {  // rows limited to the slab
-                area = (uint32_t)((ry1 - ry0 + 1) * ((int)o.bounds.y - (int)o.bounds.x + 1));
-                ty0 = ry0;
-            }
-        }
-    }
-    sEll[tid] = make_float4(o.cmx, o.cmy, o.k.A, o.k.B);
-    sEll2[tid] = make_float2(o.k.C, o.w);
-    sRect[tid] = ((uint32_t)(int)o.bounds.x & 0xFFFFu) | ((uint32_t)((int)o.bounds.y - (int)o.bounds.x + 1) << 16);
-    sTy0[tid] = ty0;
-    sMask[tid] = 0;
-    sMore[tid] = 0;
-    uint32_t total;
-    const uint32_t coff = block_exclusive_scan<kProjectBlock>(area, lds, &total);
-    sOff[tid] = coff;
-    const uint32_t nCand = min(total, kCandCap);
-    for (uint32_t i = tid; i < nCand; i += kProjectBlock) sCand[i] = kSearch;
-    __syncthreads();
-    if (area <= kCandRect)
-        for (uint32_t k = 0; k < area && coff + k < kCandCap; ++k) sCand[coff + k] = (uint16_t)((tid << 8) | k);
-    __syncthreads();
-    for (uint32_t c = tid; c < total; c += kProjectBlock) {
-        uint32_t lo, k;
-        const uint32_t v = c < kCandCap ? (uint32_t)sCand[c] : (uint32_t)kSearch;
-        if (v != kSearch) {
-            lo = v >> 8;
-            k = v & 0xFFu;
-        } else {
-            lo = 0;
-            uint32_t hi = kProjectBlock - 1;  // owner: the largest g with sOff[g] <= c
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi + 1) >> 1;
-                if (sOff[mid] <= c) lo = mid;
-                else hi = mid - 1;
-            }
-            k = c - sOff[lo];
-        }
-        const uint32_t rect = sRect[lo], rw = rect >> 16;
-        // k / rw from the hardware reciprocal (within one of the quotient), then corrected exactly
-        uint32_t row = (uint32_t)((float)k * __builtin_amdgcn_rcpf((float)rw));
-        if (row * rw > k) row--;
-        else if ((row + 1u) * rw <= k) row++;
-        const int ty = sTy0[lo] + (int)row, tx = (int)(rect & 0xFFFFu) + (int)(k - row * rw);
-        const float4 e = sEll[lo];
-        const float2 e2 = sEll2[lo];
-        Conic kk;
-        kk.A = e.z;
-        kk.B = e.w;
-        kk.C = e2.x;
-        if (intersects_tile(tx, ty, e.x, e.y, kk, e2.y)) {
-            if (k < (uint32_t)kMaskTiles) atomicOr(&sMask[lo], 1u << k);
-            else atomicAdd(&sMore[lo], 1u);
-        }
-    }
-    __syncthreads();
-    uint32_t ntiles = 0;
-    if (gid < P.count && o.vis) {
-        const uint32_t mask = sMask[tid];
-        ntiles = (uint32_t)__builtin_popcount(mask) + sMore[tid];
-        masks[gid] = mask;
-        const float2 band = ntiles ? band_of(o.ra, o.bounds, rows_of(P)) : make_float2(0.f, -1.f);
-        uint4* rp = (uint4*)(outRec + gid);
-        rp[0] = make_uint4(o.ra.x, o.ra.y, o.ra.z, o.ra.w);
-        rp[1] = make_uint4(o.rb, __float_as_uint(band.x), __float_as_uint(band.y), 0u);
-    }
-    if (gid < P.count) counts[gid] = ntiles;
-    uint32_t s = block_reduce_add<kProjectBlock>(ntiles, lds);
-    if (threadIdx.x == 0) blockSums[blk] = s;
+#define GSM_VIEWS 0
+#include "gsm_project_body.h"
+#undef GSM_VIEWS
+#define GSM_VIEWS 1
+#include "gsm_project_body.h"
+#undef GSM_VIEWS
+
+// entries [first, first + n) of the per-view array from a kernel argument (plain vector stores): the host's
+// copy of the cameras is consumed when the frame is enqueued, so the call needs no staging buffer that a
+// later call could overwrite, and a captured frame replays the cameras it was captured with
+__global__ __launch_bounds__(256) void k_fill_views(ViewChunk chunk, uint32_t n, ViewArgs* __restrict__ dst) {
+    constexpr uint32_t kWords = sizeof(ViewArgs) / 4u;
+    const uint32_t* src = (const uint32_t*)&chunk;
+    for (uint32_t i = threadIdx.x; i < n * kWords; i += 256u) ((uint32_t*)dst)[i] = src[i];
 }
 
 // ---------------------------------------------------------------------------
@@ -1098,169 +993,12 @@ __device__ __forceinline__ uint64_t block_sum_prefix(const uint32_t* __restrict_
 // each workgroup adds up those before its own -- the offset k_scan_blocks would have written, with
 // its saturation at 2^32 - 1 -- and workgroup 0 adds up all of them for the header and resets the
 // blend's queue (k_scan_blocks' other duties), so the frame needs no scan launch
-__global__ __launch_bounds__(kProjectBlock) void k_scatter(
-    ProjectArgs P, const GaussianRenderData* __restrict__ rd, const short4* __restrict__ bounds,
-    const uint32_t* __restrict__ counts, const uint32_t* __restrict__ masks,
-    const uint32_t* __restrict__ blockOffsets, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
-    const float2* __restrict__ sincos, const BlendRecord* __restrict__ rec, const uint32_t* __restrict__ devCount,
-    uint32_t fusedScan, TileAssignmentHeader* __restrict__ hdr, uint32_t* __restrict__ blendQueue) {
-    __shared__ uint32_t lds[kProjectBlock / 64];
-    __shared__ unsigned long long lds64[kProjectBlock / 64];
-    __shared__ uint32_t sOff[kProjectBlock];
-    __shared__ uint32_t sMask[kProjectBlock];  // 0: no cooperative slots (large rect or no tiles)
-    __shared__ uint32_t sRect[kProjectBlock];  // x0 | rw << 16 (rw <= 32)
-    __shared__ uint32_t sInv[kProjectBlock];   // ceil(2^16 / rw): bit / rw = (bit * inv) >> 16 for bit < 32
-    __shared__ int sTy0[kProjectBlock];        // first row index of the rect in the renderer's rows
-    __shared__ uint32_t sD[kProjectBlock];     // depth bits of the key
-    __shared__ float2 sBand[kProjectBlock];    // skip-flag band of each gaussian: mean x, half width (< 0: none)
-    // the block's first kOwnCap slots: owner << 5 | tile bit of each small-rect slot, kNoOwner for the
-    // slots of large rects (their own thread writes them); later slots take the binary search
-    constexpr uint32_t kOwnCap = 4096;
-    constexpr uint16_t kNoOwner = 0xFFFFu;
-    __shared__ uint16_t sOwn[kOwnCap];
-    const uint32_t gid = blockIdx.x * kProjectBlock + threadIdx.x;
-    // records path: the count lives on the device and the grid covers the capacity
-    const uint32_t n = devCount ? min(*devCount, P.count) : P.count;
-    if (fusedScan && blockIdx.x == 0) {  // (before any exit: an empty frame still gets its header)
-        const uint64_t all = block_sum_prefix(blockOffsets, (n + kProjectBlock - 1u) / kProjectBlock, lds64);
-        if (threadIdx.x == 0) {
-            uint32_t tot = all > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)all;
-            uint32_t ovf = 0;
-            if (tot > P.maxAssignments) {
-                tot = P.maxAssignments;
-                ovf = 1;
-            }
-            hdr->totalAssignments = tot;
-            hdr->maxCapacity = P.maxAssignments;
-            hdr->paddedCount = ((tot + 1023u) / 1024u) * 1024u;
-            hdr->overflow = ovf;
-            for (uint32_t q = 0; q < kQueueStripes; ++q) blendQueue[q * kQueueStride] = 0;
-        }
-    }
-    if (blockIdx.x * kProjectBlock >= n) return;  // (uniform; the scan stopped at the count too)
-    // The scatter's once-read inputs (counts, bounds, the records' band half, masks) are streaming loads
-    // (nt): they no longer displace the keys and values this kernel writes from the 256 MiB infinity
-    // cache, which the first tile pass reads next -- config 3: that pass 64.4-66.1 -> 59.6-61.3 us, nothing
-    // else slower (r06, VERDICT r05 item 4: profiles/r06_nt_loads_ab.txt)
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-#define GSM_SLD(p) __builtin_nontemporal_load(p)
-    // every input of the block in flight at once, while the block counts are added up (r06: the bounds,
-    // band and mask no longer wait for the count -- one memory round trip less per workgroup; a gaussian
-    // without tiles reads 28 B it does not use)
-    uint32_t c = 0u, mw = 0u;
-    unsigned long long rb = 0ull;
-    u32x4 r1v = {0u, 0u, 0u, 0u};
-    if (gid < n) {
-        c = GSM_SLD(counts + gid);
-        rb = GSM_SLD((const unsigned long long*)(bounds + gid));
-        r1v = GSM_SLD((const u32x4*)(rec + gid) + 1);  // the band k_project left in the padding
-        mw = GSM_SLD(masks + gid);
-    }
-    uint32_t base;
-    if (fusedScan) {
-        const uint64_t before = blockIdx.x ? block_sum_prefix(blockOffsets, blockIdx.x, lds64) : 0ull;
-        base = before > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)before;
-    } else {
-        base = blockOffsets[blockIdx.x];
-    }
-    uint32_t total;
-    const uint32_t off = block_exclusive_scan<kProjectBlock>(c, lds, &total);
-    bool large = false;
-    short4 r = make_short4(0, -1, 0, -1);
-    uint32_t dbits = 0;
-    int ty0 = 0, ty1 = -1;
-    uint32_t mask = 0;
-    float2 band = make_float2(0.0f, -1.0f);
-    if (c != 0) {
-        r = __builtin_bit_cast(short4, rb);
-        const uint4 r1 = make_uint4(r1v.x, r1v.y, r1v.z, r1v.w);
-        band = make_float2(__uint_as_float(r1.y), __uint_as_float(r1.z));
-        // the key's depth: the fp16 depth bits of the blend record (b = colB | depth << 16, the same
-        // bits as GaussianRenderData.depth), so the scatter reads one 16-B slot per gaussian
-        dbits = ((r1.x >> 16) ^ 0x8000u) & 0xFFFFu;
-        // row indices of the renderer's rows inside the rect (the keys carry local tile ids,
-        // k * tilesX + tx: the sort, the tile starts and the blend count the renderer's rows only)
-        rows_within(rows_of(P), (int)r.z, (int)r.w, &ty0, &ty1);
-        const int rw = (int)r.y - (int)r.x + 1;
-        large = (ty1 - ty0 + 1) * rw > kMaskTiles;
-        if (!large) mask = mw;
-        sRect[threadIdx.x] = ((uint32_t)(int)r.x & 0xFFFFu) | ((uint32_t)rw << 16);
-        // 2^16 / rw is a power of two (v_rcp_f32 exact) or >= 1/rw >= 1/32 away from an integer, and the
-        // 1-ulp reciprocal moves it by <= 2^16 * 2^-23 < 0.008: the ceiling is exact.  With inv = ceil(2^16
-        // / rw), (bit * inv) >> 16 = bit / rw for every bit < 32 and rw <= 32 (checked exhaustively)
-        sInv[threadIdx.x] = (uint32_t)__builtin_ceilf(65536.0f * __builtin_amdgcn_rcpf((float)rw));
-    }
-    sOff[threadIdx.x] = off;
-    sMask[threadIdx.x] = mask;
-    sD[threadIdx.x] = dbits;
-    sTy0[threadIdx.x] = ty0;
-    sBand[threadIdx.x] = band;
-    const uint32_t nOwn = min(total, kOwnCap);
-    for (uint32_t i = threadIdx.x; i < nOwn; i += kProjectBlock) sOwn[i] = kNoOwner;
-    __syncthreads();
-    {  // each small rect lists its slots (<= 32, one per set bit of its mask, in bit order)
-        uint32_t m = mask;
-        for (uint32_t i = off; m != 0 && i < kOwnCap; ++i) {
-            sOwn[i] = (uint16_t)((threadIdx.x << 5) | (uint32_t)__builtin_ctz(m));
-            m &= m - 1u;
-        }
-    }
-    __syncthreads();
-    for (uint32_t sl = threadIdx.x; sl < total; sl += kProjectBlock) {
-        uint32_t lo, bit;
-        if (sl < kOwnCap) {
-            const uint32_t v = sOwn[sl];
-            if (v == kNoOwner) continue;  // a large rect: its own thread writes it
-            lo = v >> 5;
-            bit = v & 31u;
-        } else {
-            // owner: the largest g with sOff[g] <= sl (zero-count gaussians share the next offset)
-            lo = 0;
-            uint32_t hi = kProjectBlock - 1;
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi + 1) >> 1;
-                if (sOff[mid] <= sl) lo = mid;
-                else hi = mid - 1;
-            }
-            uint32_t m = sMask[lo];
-            if (m == 0) continue;  // a large rect: its own thread writes it
-            for (uint32_t k = sl - sOff[lo]; k > 0; --k) m &= m - 1u;
-            bit = (uint32_t)__builtin_ctz(m);
-        }
-        const uint64_t wp = (uint64_t)base + sl;
-        if (wp >= P.maxAssignments) continue;
-        const uint32_t rect = sRect[lo];
-        const uint32_t rwo = rect >> 16;
-        const uint32_t row = (bit * sInv[lo]) >> 16;  // bit / rwo (bit < 32)
-        const int k = sTy0[lo] + (int)row, tx = (int)(rect & 0xFFFFu) + (int)(bit - row * rwo);
-        keys[wp] = ((uint32_t)(k * (int)P.bin.tilesX + tx) << 16) | sD[lo];
-        const float2 bd = sBand[lo];
-        vals[wp] = (blockIdx.x * kProjectBlock + lo) | (half_skip_flags(bd.x, bd.y, tx) << kHalfSkipShift);
-    }
-    if (!large) return;
-    uint64_t wp = (uint64_t)base + off;
-    if (wp >= P.maxAssignments) return;
-    // large rects: repeat the tests (tileScatterIndirectKernel, GlobalShaders.metal:623-678)
-    uint4 rdw = *(const uint4*)(rd + gid);
-    uint16_t hmx = (uint16_t)(rdw.x & 0xFFFFu), hmy = (uint16_t)(rdw.x >> 16);
-    uint16_t thq = (uint16_t)(rdw.y & 0xFFFFu), hs1 = (uint16_t)(rdw.y >> 16);
-    uint16_t hs2 = (uint16_t)(rdw.z & 0xFFFFu);
-    uint32_t opac = rdw.w >> 24;
-    float cx = hbits_to_f(hmx), cy = hbits_to_f(hmy);
-    Conic k = conic_from_quant(sincos, thq, hbits_to_f(hs1), hbits_to_f(hs2));
-    float w = 2.0f * compute_power((float)opac);
-    const RowSet R = rows_of(P);
-    for (int kr = ty0; kr <= ty1; ++kr)
-        for (int tx = (int)r.x, ty = R.b + kr * R.s; tx <= (int)r.y; ++tx)
-            if (intersects_tile(tx, ty, cx, cy, k, w)) {
-                if (wp < P.maxAssignments) {
-                    uint32_t tile = (uint32_t)(kr * (int)P.bin.tilesX + tx);
-                    keys[wp] = (tile << 16) | dbits;
-                    vals[wp] = gid | (half_skip_flags(band.x, band.y, tx) << kHalfSkipShift);
-                    wp++;
-                }
-            }
-}
+#define GSM_VIEWS 0
+#include "gsm_scatter_body.h"
+#undef GSM_VIEWS
+#define GSM_VIEWS 1
+#include "gsm_scatter_body.h"
+#undef GSM_VIEWS
 
 __global__ __launch_bounds__(256) void k_tile_starts(const uint32_t* __restrict__ sortedKeys,
                                                      const TileAssignmentHeader* __restrict__ hdr,
@@ -1391,6 +1129,36 @@ void launch_project(bool halfInput, uint32_t deg, const void* world, const void*
 }
 
 template <bool HALF>
+static void launch_project_views_t(uint32_t deg, const void* world, const void* harm, const ProjectArgs& a,
+                                   const ViewBatch& vb, const DeviceArena& A, hipStream_t s) {
+    const uint32_t blocks = vb.views * vb.blocksPerView;
+    if (blocks == 0 && a.schedUnits == 0) return;  // (an empty batch still orders its blend units)
+#define GSM_LAUNCH_PROJV(D)                                                                                          \
+    hipLaunchKernelGGL((k_project_views<HALF, D>), dim3(blocks + (a.schedUnits ? 1u : 0u)), dim3(kProjectBlock), 0, \
+                       s, world, harm, a, vb.args, vb.blocksPerView ? vb.blocksPerView : 1u, A.renderData, A.bounds, \
+                       A.rec, A.tileCounts, A.tileMasks, A.blockSums, A.sincosTable, A.unitCost, A.unitOrder,        \
+                       A.costMax)
+    switch (deg) {
+        case 0: GSM_LAUNCH_PROJV(0); break;
+        case 1: GSM_LAUNCH_PROJV(1); break;
+        case 2: GSM_LAUNCH_PROJV(2); break;
+        default: GSM_LAUNCH_PROJV(3); break;
+    }
+#undef GSM_LAUNCH_PROJV
+}
+
+void launch_project_views(bool halfInput, uint32_t deg, const void* world, const void* harm, const ProjectArgs& a,
+                          const ViewBatch& vb, const DeviceArena& A, hipStream_t s) {
+    if (halfInput) launch_project_views_t<true>(deg, world, harm, a, vb, A, s);
+    else launch_project_views_t<false>(deg, world, harm, a, vb, A, s);
+}
+
+void launch_fill_views(const ViewChunk& chunk, uint32_t first, uint32_t n, ViewArgs* dst, hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_fill_views, dim3(1), dim3(256), 0, s, chunk, n > kViewChunk ? kViewChunk : n, dst + first);
+}
+
+template <bool HALF>
 static void launch_project_part_t(uint32_t deg, const void* world, const void* harm, const ProjectArgs& a,
                                   const SlabTable& slabs, const PartitionBuffers& B, const float2* sincos,
                                   const DeviceArena* A, hipStream_t s) {
@@ -1484,7 +1252,15 @@ void launch_scan_blocks(uint32_t nb, const ProjectArgs& a, const DeviceArena& A,
 }
 
 void launch_scatter(const ProjectArgs& a, const DeviceArena& A, hipStream_t s, const uint32_t* devCount,
-                    bool fusedScan) {
+                    bool fusedScan, const ViewBatch* vb) {
+    if (vb) {
+        const uint32_t vblocks = vb->views * vb->blocksPerView;
+        if (vblocks == 0) return;
+        hipLaunchKernelGGL(k_scatter_views, dim3(vblocks), dim3(kProjectBlock), 0, s, a, vb->blocksPerView,
+                           vb->tilesPerView, A.renderData, A.bounds, A.tileCounts, A.tileMasks, A.blockSums, A.keys[0],
+                           A.vals[0], A.sincosTable, A.rec, fusedScan ? 1u : 0u, A.header, A.tileQueue);
+        return;
+    }
     const uint32_t blocks = (a.count + kProjectBlock - 1) / kProjectBlock;
     if (blocks == 0) return;  // (the caller scans such a frame with launch_scan_blocks)
     hipLaunchKernelGGL(k_scatter, dim3(blocks), dim3(kProjectBlock), 0, s, a, A.renderData, A.bounds,
@@ -1494,7 +1270,7 @@ void launch_scatter(const ProjectArgs& a, const DeviceArena& A, hipStream_t s, c
 
 void launch_headers(const uint32_t* sortedKeys, const FrameGeometry& g, const DeviceArena& A,
                     hipStream_t s) {
-    const uint32_t t0 = 0, t1 = g.rowCount * g.tilesX;  // the keys hold local tile ids (k_scatter)
+    const uint32_t t0 = 0, t1 = frame_tiles(g);  // the keys hold local tile ids (k_scatter)
     if (t1 <= t0) return;
     uint32_t blocks = (g.maxAssignments + 1u + 1023u) / 1024u;  // grid-stride over the device-side total
     if (blocks > 4096u) blocks = 4096u;

@@ -201,6 +201,83 @@ gsm_status GlobalRenderer::render(hipStream_t s, const gsm_gaussian_input& in,
                     });
 }
 
+uint32_t GlobalRenderer::tiles_of(uint32_t width, uint32_t height) {
+    return ((width + kTileWidth - 1) / kTileWidth) * ((height + kTileHeight - 1) / kTileHeight);
+}
+
+gsm_status GlobalRenderer::renderViews(hipStream_t s, const gsm_gaussian_input& in, const gsm_camera_params* cameras,
+                                       uint32_t viewCount, uint32_t width, uint32_t height, void* color,
+                                       size_t colorPitch, size_t colorStride, void* depth, size_t depthPitch,
+                                       size_t depthStride) {
+    // validate_frame's precedence: count, dimensions, (tiles,) a missing buffer, sizes -- all before anything
+    // is enqueued.  A view's items start on a projection-block boundary, and the values keep 30 bits of item.
+    const uint64_t padded = ((uint64_t)in.gaussian_count + kProjectBlock - 1) / kProjectBlock * kProjectBlock;
+    if (viewCount == 0 || (uint64_t)viewCount * padded > maxGaussians_ || in.gaussian_count > maxGaussians_)
+        return GSM_ERR_INVALID_GAUSSIAN_COUNT;
+    if (width == 0 || height == 0 || width > maxWidth_ || height > maxHeight_) return GSM_ERR_INVALID_DIMENSIONS;
+    const uint32_t T = tiles_of(width, height);
+    const uint64_t allTiles = (uint64_t)viewCount * T;
+    if (allTiles > tileCount_ || allTiles > 65535u) return GSM_ERR_INVALID_TILE_COUNT;
+    if (!cameras) return GSM_ERR_MISSING_REQUIRED_BUFFER;
+    gsm_status st = validateFrame(in.gaussian_count, !in.gaussians || !in.harmonics, width, height, color, colorPitch,
+                                  depth, depthPitch);
+    if (st != GSM_OK) return st;
+    // a view's rows fit in its stride, and every view's first row is as aligned as validate_frame asks of the first
+    if (colorStride < (size_t)height * colorPitch || (colorStride & 3u)) return GSM_ERR_INVALID_BUFFER_SIZE;
+    if (depth && (depthStride < (size_t)height * depthPitch || (depthStride & 1u))) return GSM_ERR_INVALID_BUFFER_SIZE;
+    if (rowBegin_ != 0 || rowEnd_ != tilesY_ || rowStride_ != 1) return GSM_ERR_UNSUPPORTED;  // (set_tile_rows)
+    // the per-view array: allocated by the first batch, for the most views the handle's tile space holds
+    if (!arena_.viewArgs) {
+        maxViews_ = std::min(tileCount_, 65535u);
+        st = allocs_.alloc((void**)&arena_.viewArgs, (size_t)maxViews_ * sizeof(ViewArgs));
+        if (st != GSM_OK) return st;
+    }
+    (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's)
+    // what the batch shares: view 0's arguments on the frame's own tile grid, rows [0, tilesY)
+    ProjectArgs a = frameArgs(cameras[0], width, height, in.gaussian_count, in.sh_components);
+    a.bin.tilesX = (width + kTileWidth - 1) / kTileWidth;
+    a.bin.tilesY = (height + kTileHeight - 1) / kTileHeight;
+    a.rowBegin = 0;
+    a.rowEnd = a.bin.tilesY;
+    a.rowStride = 1;
+    // the host copy of the per-view terms (the cameras are consumed before the call returns), to the device
+    // array in kernel-argument chunks
+    viewHost_.resize(viewCount);
+    for (uint32_t v = 0; v < viewCount; ++v) {
+        const ProjectArgs pv = frameArgs(cameras[v], width, height, in.gaussian_count, in.sh_components);
+        ViewArgs& d = viewHost_[v];
+        std::memset(&d, 0, sizeof(d));
+        d.cam = pv.cam;
+        d.limX = pv.limX;
+        d.limY = pv.limY;
+        d.focalX = pv.focalX;
+        d.focalY = pv.focalY;
+        d.maxEig = pv.maxEig;
+        d.adjFar = pv.adjFar;
+        d.adjDen = pv.adjDen;
+    }
+    for (uint32_t v0 = 0; v0 < viewCount; v0 += kViewChunk) {
+        ViewChunk c;
+        const uint32_t n = std::min(kViewChunk, viewCount - v0);
+        std::memset(&c, 0, sizeof(c));
+        std::memcpy(c.v, viewHost_.data() + v0, (size_t)n * sizeof(ViewArgs));
+        launch_fill_views(c, v0, n, arena_.viewArgs, s);
+    }
+    ViewFrame vf;
+    vf.batch.views = viewCount;
+    vf.batch.blocksPerView = (uint32_t)(padded / kProjectBlock);
+    vf.batch.tilesPerView = T;
+    vf.batch.args = arena_.viewArgs;
+    vf.colorStride = colorStride;
+    vf.depthStride = depthStride;
+    const uint32_t deg = sh_degree(in.sh_components);
+    const bool half = config_.precision == GSM_PRECISION_FLOAT16;
+    return runFrame(s, a, width, height, color, colorPitch, depth, depthPitch,
+                    [&](const ProjectArgs& pa) {
+                        launch_project_views(half, deg, in.gaussians, in.harmonics, pa, vf.batch, arena_, s);
+                    }, nullptr, false, nullptr, &vf);
+}
+
 gsm_status GlobalRenderer::renderRecords(hipStream_t s, const void* records, uint32_t count, uint32_t width,
                                          uint32_t height, void* color, size_t colorPitch, void* depth,
                                          size_t depthPitch, const uint32_t* devCount, bool preOrdered,
@@ -335,18 +412,22 @@ gsm_status GlobalRenderer::partitionPush(hipStream_t s, uint32_t world, uint32_t
     return GSM_OK;
 }
 
-uint32_t GlobalRenderer::scheduleUnits(hipStream_t s, uint32_t width, uint32_t height) {
-    const uint32_t upt = blend_units_per_tile(rowCount() * tilesX_, dev_.numCUs);
-    const uint32_t units = rowCount() * tilesX_ * upt;
+uint32_t GlobalRenderer::scheduleUnits(hipStream_t s, uint32_t width, uint32_t height, uint32_t views) {
+    // (a batch of views: the units of views * tiles(width, height) tiles; the view count is part of the key, so
+    // a batch neither inherits nor leaves behind a single frame's costs)
+    const uint32_t tiles = views ? views * tiles_of(width, height) : rowCount() * tilesX_;
+    const uint32_t upt = blend_units_per_tile(tiles, dev_.numCUs);
+    const uint32_t units = tiles * upt;
     const uint64_t key = ((uint64_t)upt << 60) ^ ((uint64_t)width << 40) ^ ((uint64_t)height << 20) ^
                          ((uint64_t)rowStride_ << 30) ^ ((uint64_t)rowBegin_ << 10) ^ rowEnd_;
-    if (key != schedKey_) {  // new geometry: no walks to order by yet (either schedule set)
+    if (key != schedKey_ || views != schedViews_) {  // new geometry: no walks to order by yet (either schedule set)
         for (const ScheduleSet& t : sched_) {
             if (!t.unitCost) continue;
             hipMemsetAsync(t.unitCost, 0, (size_t)units * sizeof(uint16_t), s);
             hipMemsetAsync(t.costMax, 0, (kCostMaxSlots + 2) * sizeof(uint32_t), s);
         }
         schedKey_ = key;
+        schedViews_ = views;
     }
     return tuning_.costOrder ? units : 0u;
 }
@@ -355,14 +436,16 @@ template <class Front>
 gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_t width, uint32_t height,
                                     void* color, size_t colorPitch, void* depth, size_t depthPitch,
                                     Front&& front, const uint32_t* devCount, bool preOrdered,
-                                    const MgArrive* blendArrive) {
+                                    const MgArrive* blendArrive, const ViewFrame* views) {
     (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's: the launches below are checked)
     const int profiling = timer_.flags();
     const bool keep = (profiling & 2) != 0;
     // captured frame: the reference's intermediates (render data, sorted keys / values) are kept
     // for readback; the product path writes neither (the blend reads its records and half lists)
     const bool capture = (profiling & (2 | 16)) != 0;
-    const uint32_t nb = (a.count + kProjectBlock - 1) / kProjectBlock;
+    // (a batch of views: a.count gaussians per view, every view's items padded to whole blocks)
+    const uint32_t nb = views ? views->batch.views * views->batch.blocksPerView
+                              : (a.count + kProjectBlock - 1) / kProjectBlock;
     // GaussianRenderData for readback only when profiling (bits 0, 1), gsm_debug.h
     ProjectArgs fa = a;
     fa.keepRenderData = capture ? 1u : 0u;
@@ -375,7 +458,7 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     // The ordering only needs those costs: one extra workgroup of the projection launch does it
     // (unit_order_block) while the others project (k_project, or k_records_in on the records path;
     // the multi-GPU frame orders them earlier, in its partition projection: preOrdered).
-    const uint32_t units = preOrdered ? 0u : scheduleUnits(s, width, height);
+    const uint32_t units = preOrdered ? 0u : scheduleUnits(s, width, height, views ? views->batch.views : 0u);
     const bool costOrder = preOrdered ? tuning_.costOrder : units > 0;
     fa.schedUnits = units;
     // (written on every scheduled frame: the blend's remaining-walk priorities read the longest walk too)
@@ -392,7 +475,7 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     const bool fusedScan = tuning_.fusedScan && nb > 0 && nb <= (devCount ? 4u : 1u) * kFusedScanMaxBlocks;
     if (!fusedScan) launch_scan_blocks(nb, a, arena_, s, devCount);
     timer_.record(2, s);
-    launch_scatter(a, arena_, s, devCount, fusedScan);
+    launch_scatter(a, arena_, s, devCount, fusedScan, views ? &views->batch : nullptr);
     if (keep) {  // preserve the unsorted assignment arrays for readback
         hipMemcpyAsync(arena_.keysKeep, arena_.keys[0], (size_t)maxAssignments_ * 4, hipMemcpyDeviceToDevice, s);
         hipMemcpyAsync(arena_.valsKeep, arena_.vals[0], (size_t)maxAssignments_ * 4, hipMemcpyDeviceToDevice, s);
@@ -411,6 +494,17 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     g.width = width;
     g.height = height;
     g.maxAssignments = maxAssignments_;
+    if (views) {  // the frame's own tile grid, one after another in the handle's tile space
+        g.tilesX = a.bin.tilesX;
+        g.tilesY = a.bin.tilesY;
+        g.rowBegin = 0;
+        g.rowEnd = g.rowCount = g.tilesY;
+        g.rowStride = 1;
+        g.views = views->batch.views;
+        g.tilesPerView = views->batch.tilesPerView;
+        g.colorViewStride = views->colorStride;
+        g.depthViewStride = views->depthStride;
+    }
     // Frame sort.  Default: a stable LSD sort by the tile field only
     // (ceil(tileBits / 8) passes, the last one writing the tile starts), then each tile's run sorted
     // stably by depth by one wave in LDS -- the same order as the reference's 4-pass sort of
@@ -421,7 +515,7 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
         // the last tile pass also writes the tile starts (radix_sort_tiles: no pass over the keys); the
         // keys hold local tile ids of the renderer's rows (k_scatter): a slab of <= 2048 tiles
         // (multi-GPU) takes one wide pass
-        const uint32_t localTiles = rowCount() * tilesX_;
+        const uint32_t localTiles = frame_tiles(g);  // (a batch: the pass plan follows views * tiles)
         const int res = radix_sort_tiles(kb, vb, &arena_.header->totalAssignments, maxAssignments_, 16,
                                          sort_space(arena_), arena_.tileStart, 0u, localTiles,
                                          tileCount_, s, ballot, tuning_.wideSort, tuning_.sortScanless);
@@ -446,7 +540,7 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     // the blend walks per-half lists without the entries its half provably skips (k_scatter flags);
     // the tile sort writes them, the 4-pass sort needs the separate pass
     if (fullRadix)
-        launch_half_lists(sortedVals_, 0u, rowCount() * tilesX_, arena_, tileCount_, s);
+        launch_half_lists(sortedVals_, 0u, frame_tiles(g), arena_, tileCount_, s);
     arena_.blendTrace = (profiling & 4) ? traceBuf_ : nullptr;
     // the schedule from the walks the previous frame's blend recorded (same stream: no join)
     timer_.record(5, s, true);

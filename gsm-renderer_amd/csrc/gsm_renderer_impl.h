@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 #include "../../include/gsm_debug.h"
 #include "../../include/gsm_renderer.h"
 #include "gsm_host.h"
@@ -20,6 +22,11 @@ class GlobalRenderer {
     gsm_status render(hipStream_t stream, const gsm_gaussian_input& input,
                       const gsm_camera_params& camera, uint32_t width, uint32_t height, void* color,
                       size_t colorPitch, void* depth, size_t depthPitch);
+
+    // several views of one scene in one frame over a combined tile space (gsm_global_render_views)
+    gsm_status renderViews(hipStream_t stream, const gsm_gaussian_input& input, const gsm_camera_params* cameras,
+                           uint32_t viewCount, uint32_t width, uint32_t height, void* color, size_t colorPitch,
+                           size_t colorStride, void* depth, size_t depthPitch, size_t depthStride);
 
     // multi-GPU partition: project ids [first, first+count) and pack the splat
     // records of every tile-row slab they meet; render a slab from the records it received
@@ -86,14 +93,20 @@ class GlobalRenderer {
     ProjectArgs frameArgs(const gsm_camera_params& camera, uint32_t width, uint32_t height, uint32_t count,
                           uint32_t shComponents) const;
     // scan, scatter, sort, headers and blend after `front` filled the per-gaussian arrays
+    // (views: a batch -- `a` holds what its views share, the targets are view 0's)
+    struct ViewFrame {
+        ViewBatch batch;
+        size_t colorStride = 0, depthStride = 0;
+    };
     template <class Front>
     gsm_status runFrame(hipStream_t s, const ProjectArgs& a, uint32_t width, uint32_t height, void* color,
                         size_t colorPitch, void* depth, size_t depthPitch, Front&& front,
                         const uint32_t* devCount = nullptr, bool preOrdered = false,
-                        const MgArrive* blendArrive = nullptr);
-    // the blend schedule's unit count for the current rows (0 when cost order is off), its cost
-    // arrays cleared when the geometry changed
-    uint32_t scheduleUnits(hipStream_t s, uint32_t width, uint32_t height);
+                        const MgArrive* blendArrive = nullptr, const ViewFrame* views = nullptr);
+    // the blend schedule's unit count for the current rows, or for a batch of `views` frames (0 when cost
+    // order is off), its cost arrays cleared when the geometry or the view count changed
+    uint32_t scheduleUnits(hipStream_t s, uint32_t width, uint32_t height, uint32_t views = 0);
+    static uint32_t tiles_of(uint32_t width, uint32_t height);  // tiles of a width x height frame
     PartitionBuffers part_;
     uint32_t partCount_ = 0;  // ids of the last partitionCounts
     SlabTable partSlabs_{};
@@ -135,6 +148,9 @@ class GlobalRenderer {
     const uint32_t* unsortedVals_ = nullptr;
     unsigned long long* traceBuf_ = nullptr;  // blend unit trace (profiling bit 2)
     uint64_t schedKey_ = ~0ull;               // geometry the unit costs belong to
+    uint32_t schedViews_ = 0;                 // ... and the view count (0: a single frame)
+    std::vector<ViewArgs> viewHost_;          // the last batch's per-view terms (render_views)
+    uint32_t maxViews_ = 0;                   // entries of arena_.viewArgs
 };
 
 }  // namespace gsm

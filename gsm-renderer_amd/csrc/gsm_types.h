@@ -135,7 +135,16 @@ struct FrameGeometry {
     uint32_t rowStride, rowCount;
     uint32_t width, height;     // frame (camera) size
     uint32_t maxAssignments;
+    // A batch of views (gsm_global_render_views): `views` frames of tilesX x tilesY tiles
+    // in one tile space, tile v * tilesPerView + local tile; view v's targets start viewStride bytes
+    // after view v - 1's.  views == 0: a single frame.
+    uint32_t views = 0, tilesPerView = 0;
+    size_t colorViewStride = 0, depthViewStride = 0;
 };
+// tiles the frame's sort and blend cover
+inline uint32_t frame_tiles(const FrameGeometry& g) {
+    return g.views ? g.views * g.tilesPerView : g.rowCount * g.tilesX;
+}
 
 constexpr uint32_t kTileWidth = 32;   // GlobalRenderer.swift:74
 constexpr uint32_t kTileHeight = 16;  // GlobalRenderer.swift:75

@@ -210,6 +210,9 @@ _SIGNATURES = {
     "gsm_global_destroy": ([C.c_void_p], None),
     "gsm_global_render": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera), C.c_uint32,
                            C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t], C.c_int),
+    "gsm_global_render_views": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera), C.c_uint32,
+                                 C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
+                                 C.c_size_t, C.c_size_t], C.c_int),
     "gsm_global_render_stereo": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera),
                                   C.POINTER(_Camera), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                   C.c_void_p, C.c_size_t], C.c_int),
@@ -446,6 +449,24 @@ class GlobalRenderer(_Renderer):
                                       int(width), int(height), _ptr(color_texture), cp,
                                       _ptr(depth_texture), dp)
         _check(st, "gsm_global_render")
+
+    def render_views(self, color_texture, depth_texture, input: GaussianInput, cameras, width: int, height: int,
+                     stream=None, color_pitch: Optional[int] = None, depth_pitch: Optional[int] = None,
+                     color_view_stride: Optional[int] = None, depth_view_stride: Optional[int] = None):
+        """gsm_global_render_views: len(cameras) views of one scene in one frame; view v's targets start v
+        view strides (default: height rows) after color_texture / depth_texture.  cameras None: a NULL
+        camera array with view_count 1 (the C entry's error path)."""
+        inp = _Input(_ptr(input.gaussians), _ptr(input.harmonics), int(input.gaussian_count),
+                     int(input.sh_components))
+        n = 1 if cameras is None else len(cameras)
+        cams = None if cameras is None else (_Camera * max(n, 1))(*[_camera_struct(c) for c in cameras])
+        cp = color_pitch if color_pitch is not None else int(width) * self._bpp
+        dp = depth_pitch if depth_pitch is not None else int(width) * 2
+        cs = color_view_stride if color_view_stride is not None else int(height) * cp
+        ds = depth_view_stride if depth_view_stride is not None else int(height) * dp
+        st = _lib().gsm_global_render_views(self._h, _stream_handle(stream), C.byref(inp), cams, n, int(width),
+                                            int(height), _ptr(color_texture), cp, cs, _ptr(depth_texture), dp, ds)
+        _check(st, "gsm_global_render_views")
 
     def project_partition(self, input: GaussianInput, camera: CameraParams, width: int, height: int,
                           first: int, count: int, slab_rows, send, send_capacity: int, send_counts,

@@ -131,6 +131,33 @@ gsm_status gsm_global_render(gsm_renderer *renderer, void *stream, const gsm_gau
                              void *color_rgba16f, size_t color_pitch_bytes, void *depth_r16f,
                              size_t depth_pitch_bytes);
 
+/* Several views of one scene in one frame (no reference analogue): view_count cameras
+ * over the same input, every view width x height, rendered by one launch chain over a combined tile
+ * space.  View v's colour target starts at color + v * color_view_stride_bytes (height rows of
+ * color_pitch bytes), its depth target at depth + v * depth_view_stride_bytes (depth may be NULL).
+ * Every view's bytes equal those of gsm_global_render for its camera; view_count == 1 is allowed.
+ * Enqueue-only on `stream`; `cameras` is host memory and is consumed before the call returns.
+ *
+ * The batch runs inside the handle's allocations (gsm_global_create sizes them; only a small
+ * per-view constant array is allocated, by the handle's first batch).  Checked before anything is
+ * enqueued, in this order:
+ *   GSM_ERR_INVALID_GAUSSIAN_COUNT   view_count == 0, or view_count * roundup(gaussian_count, 256)
+ *                                    > max_gaussians (a view's items start on a 256-item boundary);
+ *   GSM_ERR_INVALID_DIMENSIONS       width > max_width or height > max_height (or zero);
+ *   GSM_ERR_INVALID_TILE_COUNT       view_count * tiles(width, height) exceeds the handle's tile count
+ *                                    (tiles(max_width, max_height), 32 x 16 pixel tiles) or 65535;
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  cameras or color NULL (or the input's buffers, with a count > 0);
+ *   GSM_ERR_INVALID_BUFFER_SIZE      a pitch smaller than a row, a view stride smaller than height
+ *                                    rows, or one that misaligns a view (colour 4 bytes, depth 2);
+ *   GSM_ERR_UNSUPPORTED              the handle is restricted to tile rows (gsm_global_set_tile_rows).
+ * The assignment capacity (4 * max_gaussians) is shared by the batch: a batch whose views together
+ * exceed it sets the overflow counter (gsm_debug.h), and no parity is promised for that frame. */
+gsm_status gsm_global_render_views(gsm_renderer *renderer, void *stream, const gsm_gaussian_input *input,
+                                   const gsm_camera_params *cameras, uint32_t view_count,
+                                   uint32_t width, uint32_t height,
+                                   void *color, size_t color_pitch_bytes, size_t color_view_stride_bytes,
+                                   void *depth, size_t depth_pitch_bytes, size_t depth_view_stride_bytes);
+
 /* GlobalRenderer.renderStereo (GlobalRenderer.swift:240-255) calls fatalError for
  * every target; this entry returns GSM_ERR_UNSUPPORTED instead. */
 gsm_status gsm_global_render_stereo(gsm_renderer *renderer, void *stream,
