@@ -98,6 +98,9 @@ __device__ __forceinline__ void blend_wave_sync() {
 #define GSM_BLEND_VIEWS 1
 #include "gsm_blend_px_body.h"
 #undef GSM_BLEND_VIEWS
+#define GSM_BLEND_VIEWS 2
+#include "gsm_blend_px_body.h"
+#undef GSM_BLEND_VIEWS
 
 
 int blend_pairs_per_lane(uint32_t numTiles, int numCUs) {
@@ -177,6 +180,26 @@ int launch_blend(const FrameGeometry& g, const DeviceArena& A, void* color,
                        A.tileQueue, numTiles, g.tilesX, g.tilesPerView, g.width, g.height, (uint8_t*)color,           \
                        colorPitch, g.colorViewStride, (uint8_t*)depth, depthPitch, g.depthViewStride, flags, order,   \
                        A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1], A.halfCount, g.tileCount, A.costMax)
+    // a batch of different views: the targets, sizes and store widths are per view (BatchTarget);
+    // the kernel's flags keep what the batch shares
+#define GSM_LAUNCH_BLEND_BATCH(NTH, PP, CMP)                                                                       \
+    hipLaunchKernelGGL((k_blend_px_batch<NTH, PP, CMP>), dim3(grid), dim3(NTH), 0, s, A.tileStart, A.rec, A.expTable, \
+                       A.tileQueue, numTiles, (const BatchViewArgs*)g.batchArgs, g.batchTileView, flags & ~(1 | 2048), \
+                       order, A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1], A.halfCount, g.tileCount,       \
+                       A.costMax)
+    if (g.batchTiles) {
+        if (P == 1) {
+            if (waves == 16) GSM_LAUNCH_BLEND_BATCH(1024, 1, false);
+            else if (waves == 12) GSM_LAUNCH_BLEND_BATCH(768, 1, false);
+            else GSM_LAUNCH_BLEND_BATCH(512, 1, false);
+        } else {
+            if (waves == 16) GSM_LAUNCH_BLEND_BATCH(1024, 2, true);
+            else if (waves == 12) GSM_LAUNCH_BLEND_BATCH(768, 2, true);
+            else GSM_LAUNCH_BLEND_BATCH(512, 2, true);
+        }
+        return P == 1 ? GSM_BLEND_KERNEL_QUADRANT : GSM_BLEND_KERNEL_HALF_TILE;
+    }
+#undef GSM_LAUNCH_BLEND_BATCH
     if (g.views) {
         if (P == 1) {
             if (waves == 16) GSM_LAUNCH_BLEND_VIEWS(1024, 1, false);

@@ -144,6 +144,9 @@ __device__ __forceinline__ void pw_write_pair(const PwTarget& t, uint32_t px, ui
 #define GSM_BLEND_VIEWS 1
 #include "gsm_blend_pw_body.h"
 #undef GSM_BLEND_VIEWS
+#define GSM_BLEND_VIEWS 2
+#include "gsm_blend_pw_body.h"
+#undef GSM_BLEND_VIEWS
 
 
 // the pair walk for a frame of half-tile units on one GPU (no multi-GPU gather); `waves` per workgroup
@@ -176,6 +179,19 @@ void launch_blend_pw(const FrameGeometry& g, const DeviceArena& A, void* color, 
                        A.tileQueue, numTiles, g.tilesX, g.tilesPerView, tg, g.colorViewStride, g.depthViewStride,    \
                        order, A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1], A.halfCount, g.tileCount,      \
                        A.costMax, flags)
+    // a batch of different views: the targets, sizes and store widths are per view (BatchTarget)
+#define GSM_LAUNCH_PW_BATCH(NTH)                                                                                    \
+    hipLaunchKernelGGL((k_blend_pw_batch<NTH>), dim3(grid), dim3(NTH), 0, s, A.tileStart, A.rec, A.expTable,         \
+                       A.tileQueue, numTiles, (const BatchViewArgs*)g.batchArgs, g.batchTileView, tg.flags & ~1,     \
+                       order, A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1], A.halfCount, g.tileCount,      \
+                       A.costMax, flags)
+    if (g.batchTiles) {
+        if (waves >= 16) GSM_LAUNCH_PW_BATCH(1024);
+        else if (waves >= 12) GSM_LAUNCH_PW_BATCH(768);
+        else GSM_LAUNCH_PW_BATCH(512);
+        return;
+    }
+#undef GSM_LAUNCH_PW_BATCH
     if (g.views) {
         if (waves >= 16) GSM_LAUNCH_PW_VIEWS(1024);
         else if (waves >= 12) GSM_LAUNCH_PW_VIEWS(768);

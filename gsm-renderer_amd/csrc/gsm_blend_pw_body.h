@@ -1,10 +1,24 @@
-// gsm_blend_pw_body.h -- the text of k_blend_pw, compiled twice by gsm_blend_pw.hip: as the single frame's
-// kernel (GSM_BLEND_VIEWS 0: k_blend_pw, exactly the kernel it was before batches of views existed) and as
-// the kernel of a batch of views (GSM_BLEND_VIEWS 1: k_blend_pw_views, gsm_global_render_views).
+// gsm_blend_pw_body.h -- the text of k_blend_pw, compiled three times by gsm_blend_pw.hip: as the single frame's
+// kernel (GSM_BLEND_VIEWS 0: k_blend_pw, exactly the kernel it was before batches of views existed), as
+// the kernel of a batch of views (GSM_BLEND_VIEWS 1: k_blend_pw_views, gsm_global_render_views)
+// and as the kernel of a batch of views of different scenes and sizes (GSM_BLEND_VIEWS 2: k_blend_pw_batch,
+// gsm_global_render_batch, DESIGN.md 18: a unit's view comes from a per-tile table; the two units of a pair may
+// belong to views of different sizes, so every lane stores through its own unit's target and bounds).
 // A batch's tile t belongs to view t / tilesPerView; a unit's pixel coordinates are its view's own, and its
 // stores go to that view's targets -- the first view's advanced by the view strides.  The two units of a pair
 // may belong to different views, so every lane stores through the target of its own unit.  No include guard.
-#if GSM_BLEND_VIEWS
+#if GSM_BLEND_VIEWS == 2
+// the pair walk of a batch of different views (gsm_global_render_batch): numTiles = the sum of the views' tiles;
+// tgFlags: PwTarget::flags without bit 0, which is the view's own
+template <int NT>
+__global__ __launch_bounds__(NT) void k_blend_pw_batch(
+    const uint32_t* __restrict__ tileStart, const BlendRecord* __restrict__ rec,
+    const uint16_t* __restrict__ expTable, uint32_t* __restrict__ queue, uint32_t numTiles,
+    const BatchViewArgs* __restrict__ views, const uint16_t* __restrict__ tileView, int tgFlags,
+    const uint32_t* __restrict__ order, uint16_t* __restrict__ unitCost, unsigned long long* __restrict__ trace,
+    const uint32_t* __restrict__ half0, const uint32_t* __restrict__ half1, const uint32_t* __restrict__ halfCount,
+    uint32_t tileCount, uint32_t* __restrict__ costMax, int flags) {
+#elif GSM_BLEND_VIEWS
 // the pair walk of a batch of views (gsm_global_render_views): numTiles = views * tilesPerView
 template <int NT>
 __global__ __launch_bounds__(NT) void k_blend_pw_views(
@@ -84,7 +98,11 @@ __global__ __launch_bounds__(NT) void k_blend_pw(
         // the two units (scalars, not arrays: a lane-dependent pick from an array would go to scratch)
         uint32_t Uu0 = 0, Uu1 = 0, UX0 = 0, UX1 = 0, UY0 = 0, UY1 = 0, CNT0 = 0, CNT1 = 0, FULL0 = 0, FULL1 = 0;
         const uint32_t *LST0 = half0, *LST1 = half0;
-#if GSM_BLEND_VIEWS
+#if GSM_BLEND_VIEWS == 2
+        // the units' targets, pitches, bounds and store widths: their views' (the two units of a pair may belong
+        // to views of different sizes)
+        PwTarget TG0{nullptr, 0, nullptr, 0, 0u, 0u, tgFlags}, TG1 = TG0;
+#elif GSM_BLEND_VIEWS
         // the units' targets: their views' (the two units of a pair may belong to different views)
         uint8_t *COL0 = tg.color, *COL1 = tg.color, *DEP0 = tg.depth, *DEP1 = tg.depth;
 #endif
@@ -93,7 +111,15 @@ __global__ __launch_bounds__(NT) void k_blend_pw(
             uint32_t u = order ? __builtin_amdgcn_readfirstlane(order[pos + k]) : pos + k;
             if (u >= numUnits) u = pos + k;  // a schedule is a permutation of [0, numUnits); never trust it further
             const uint32_t tile = u >> 1, part = u & 1u;
-#if GSM_BLEND_VIEWS
+#if GSM_BLEND_VIEWS == 2
+            // the unit's view (one uniform table load, then scalar loads of the view's 64-B target line), and the
+            // tile within its own grid (pixel coordinates are the view's own)
+            const BatchTarget& VT = views[__builtin_amdgcn_readfirstlane((uint32_t)tileView[tile])].tg;
+            (k ? TG1 : TG0) = PwTarget{VT.color, VT.colorPitch, VT.depth, VT.depthPitch, VT.width, VT.height,
+                                       tgFlags | (int)(VT.vec & 1u)};
+            const uint32_t tilesX = VT.tilesX, ltile = tile - VT.tileBase;
+            const uint32_t tileX = ltile % tilesX, tileY = ltile / tilesX;
+#elif GSM_BLEND_VIEWS
             // the unit's view: its targets, and the tile within its frame (pixel coordinates are the view's own)
             const uint32_t view = tile / tilesPerView, ltile = tile - view * tilesPerView;
             (k ? COL1 : COL0) = tg.color + (size_t)view * colorViewStride;
@@ -112,7 +138,11 @@ __global__ __launch_bounds__(NT) void k_blend_pw(
         };
         unitOf(0u, Uu0, UX0, UY0, CNT0, FULL0, LST0);
         if (pair) unitOf(1u, Uu1, UX1, UY1, CNT1, FULL1, LST1);
-#if GSM_BLEND_VIEWS
+#if GSM_BLEND_VIEWS == 2
+        // the target of unit k of the job: every lane stores through its own unit's, within its own bounds
+        auto tgOf = [&](uint32_t k) { return k ? TG1 : TG0; };
+#define GSM_PW_TG(k) tgOf(k)
+#elif GSM_BLEND_VIEWS
         // the target of unit k of the job: every lane stores through its own unit's
         auto tgOf = [&](uint32_t k) {
             PwTarget t = tg;

@@ -1,10 +1,30 @@
-// gsm_blend_px_body.h -- the text of k_blend_px, compiled twice by gsm_blend.hip: as the single frame's
-// kernel (GSM_BLEND_VIEWS 0: k_blend_px, exactly the kernel it was before batches of views existed) and as
-// the kernel of a batch of views (GSM_BLEND_VIEWS 1: k_blend_px_views, gsm_global_render_views).
+// gsm_blend_px_body.h -- the text of k_blend_px, compiled three times by gsm_blend.hip: as the single frame's
+// kernel (GSM_BLEND_VIEWS 0: k_blend_px, exactly the kernel it was before batches of views existed), as
+// the kernel of a batch of views (GSM_BLEND_VIEWS 1: k_blend_px_views, gsm_global_render_views)
+// and as the kernel of a batch of views of different scenes and sizes (GSM_BLEND_VIEWS 2: k_blend_px_batch,
+// gsm_global_render_batch, DESIGN.md 18: a tile's view comes from a per-tile table, and the view's entry gives
+// its targets, pitches, size and tile grid -- scalar loads, once per unit).
 // A batch's tile t belongs to view t / tilesPerView, whose targets start that many view strides after the
 // first view's; the unit's pixel coordinates are the view's own (the fp16 half(x), half(y) of the quadratic
 // form see the single frame's values), and nothing else of the walk knows what a view is.  No include guard.
-#if GSM_BLEND_VIEWS
+#if GSM_BLEND_VIEWS == 2
+// the blend of a batch of different views (gsm_global_render_batch): numTiles = the sum of the views' tiles
+template <int NT, int P, bool COMPACT = false>
+__global__ __launch_bounds__(NT) void k_blend_px_batch(
+    const uint32_t* __restrict__ tileStart, const BlendRecord* __restrict__ rec,
+    const uint16_t* __restrict__ expTable, uint32_t* __restrict__ queue, uint32_t numTiles,
+    const BatchViewArgs* __restrict__ views, const uint16_t* __restrict__ tileView, int flags,
+    const uint32_t* __restrict__ order, uint16_t* __restrict__ unitCost, unsigned long long* __restrict__ trace,
+    const uint32_t* __restrict__ half0, const uint32_t* __restrict__ half1, const uint32_t* __restrict__ halfCount,
+    uint32_t tileCount, uint32_t* __restrict__ costMax) {
+    constexpr uint32_t tileBegin = 0;  // whole frames on one GPU: no tile rows, no gather
+    const MgArrive arrive{};
+    // the current unit's view: its targets, pitches, size and whether its wide stores are aligned (flags bit 0)
+    uint8_t *color = nullptr, *depth = nullptr;
+    size_t colorPitch = 0, depthPitch = 0;
+    uint32_t W = 0, H = 0;
+    const int flags0 = flags & ~1;
+#elif GSM_BLEND_VIEWS
 // the blend of a batch of views (gsm_global_render_views): numTiles = views * tilesPerView
 template <int NT, int P, bool COMPACT = false>
 __global__ __launch_bounds__(NT) void k_blend_px_views(
@@ -172,7 +192,20 @@ __global__ __launch_bounds__(NT) void k_blend_px(
         uint32_t u = order ? __builtin_amdgcn_readfirstlane(order[qi]) : qi;
         if (u >= numUnits) u = qi;  // a schedule is a permutation of [0, numUnits); never trust it further
         const uint32_t tile = tileBegin + u / UPT, part = u % UPT;
-#if GSM_BLEND_VIEWS
+#if GSM_BLEND_VIEWS == 2
+        // the unit's view (one uniform table load, then scalar loads of the view's 64-B target line): its targets
+        // and bounds, and the tile within its own grid (pixel coordinates are the view's own)
+        const BatchTarget& VT = views[__builtin_amdgcn_readfirstlane((uint32_t)tileView[tile])].tg;
+        color = VT.color;
+        depth = VT.depth;
+        colorPitch = VT.colorPitch;
+        depthPitch = VT.depthPitch;
+        W = VT.width;
+        H = VT.height;
+        flags = flags0 | (int)(VT.vec & 1u);
+        const uint32_t tilesX = VT.tilesX, ltile = tile - VT.tileBase;
+        const uint32_t tileX = ltile % tilesX, tileY = ltile / tilesX;
+#elif GSM_BLEND_VIEWS
         // the unit's view: its targets, and the tile within its frame (pixel coordinates are the view's own)
         const uint32_t view = tile / tilesPerView, ltile = tile - view * tilesPerView;
         color = color0 + (size_t)view * colorViewStride;

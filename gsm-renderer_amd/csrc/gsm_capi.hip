@@ -90,6 +90,11 @@ gsm_status gsm_global_render_views(gsm_renderer* r, void* stream, const gsm_gaus
                                 color_view_stride, depth, depth_pitch, depth_view_stride);
 }
 
+gsm_status gsm_global_render_batch(gsm_renderer* r, void* stream, const gsm_global_view* views, uint32_t view_count) {
+    if (!r || !r->impl) return GSM_ERR_INVALID_ARGUMENT;
+    return r->impl->renderBatch((hipStream_t)stream, views, view_count);
+}
+
 gsm_status gsm_global_project_partition(gsm_renderer* r, void* stream, const gsm_gaussian_input* input,
                                         const gsm_camera_params* camera, uint32_t width, uint32_t height,
                                         uint32_t first, uint32_t count, const uint32_t* slab_rows,

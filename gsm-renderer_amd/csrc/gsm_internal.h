@@ -55,6 +55,45 @@ struct ViewBatch {
     const ViewArgs* args = nullptr;  // device, [views]
 };
 
+// A batch of views of different scenes and sizes (gsm_global_render_batch): everything a view
+// owns.  View v's items start at 256 * blockBase (blockBase = the blocks of the views before it), its tiles
+// at tileBase on its own tilesX x tilesY grid.  One entry per view in a device array; a projection or scatter
+// block finds its view in a per-block table, a blend unit in a per-tile table (both written with the array),
+// so every lookup is one uniform 2-byte load followed by scalar loads of the entry.
+struct BatchTarget {  // what a blend unit reads (one 64-B line of the entry)
+    uint8_t* color;
+    uint8_t* depth;  // null: this view has no depth target
+    size_t colorPitch, depthPitch;
+    uint32_t tileBase, tilesX, tilesY, width, height;
+    uint32_t vec;    // bit 0: 16-B colour / 4-B depth stores are aligned in this view's targets
+    uint32_t pad[2];
+};
+static_assert(sizeof(BatchTarget) == 64, "BatchTarget: one 64-B line");
+struct BatchViewArgs {
+    CameraUniforms cam;
+    float limX, limY, focalX, focalY, maxEig, adjFar, adjDen;
+    uint32_t count;      // gaussians of this view's scene
+    TileBinningParams bin;  // on the view's own tile grid
+    uint32_t blockBase, pad0;
+    const void* world;
+    const void* harm;
+    BatchTarget tg;
+};
+static_assert(sizeof(BatchViewArgs) == 368 && offsetof(BatchViewArgs, tg) % 16 == 0, "BatchViewArgs: 23 16-B words");
+// the array is filled by kernel arguments, kBatchChunk entries per launch (a kernel argument block holds 4 KiB)
+constexpr uint32_t kBatchChunk = 10;
+struct BatchChunk {
+    BatchViewArgs v[kBatchChunk];
+};
+struct BatchFrame {
+    uint32_t views = 0;
+    uint32_t blocks = 0;  // projection / scatter blocks of the batch: sum of ceil(count_v / 256)
+    uint32_t tiles = 0;   // sum of the views' tiles
+    const BatchViewArgs* args = nullptr;   // device, [views]
+    const uint16_t* blockView = nullptr;   // device, [blocks]: the view of every block
+    const uint16_t* tileView = nullptr;    // device, [tiles]: the view of every tile
+};
+
 // Multi-GPU partition: tile-row boundaries of the slabs, and the 48-byte
 // record a slab owner receives per gaussian (GaussianRenderData + blend record + tile rect).
 constexpr uint32_t kMaxSlabs = 16;
@@ -229,6 +268,9 @@ struct DeviceArena {
                                                  // skip flag for that half is clear, from the tile's start
     uint32_t* halfCount = nullptr;             // [2 * tileCount] entries of each half list (half-major)
     ViewArgs* viewArgs = nullptr;              // [maxViews] per-view projection constants (render_views; lazily)
+    BatchViewArgs* batchArgs = nullptr;        // [maxBatchViews] per-view entries (render_batch; lazily)
+    uint16_t* batchBlockView = nullptr;        // [ceil(maxG / 256)] the view of every projection block of a batch
+    uint16_t* batchTileView = nullptr;         // [tileCount] the view of every tile of a batch
     uint16_t* expTable = nullptr;              // [65536]
     float2* sincosTable = nullptr;             // [kSincosEntries + 256]: sin/cos, then the byte table (det_byte_lut_entry)
 };
@@ -293,6 +335,15 @@ void launch_project(bool halfInput, uint32_t shDegree, const void* world, const 
 void launch_project_views(bool halfInput, uint32_t shDegree, const void* world, const void* harmonics,
                           const ProjectArgs& args, const ViewBatch& vb, const DeviceArena& A, hipStream_t stream);
 void launch_fill_views(const ViewChunk& chunk, uint32_t first, uint32_t n, ViewArgs* dst, hipStream_t stream);
+// a batch of views of different scenes and sizes (k_project_batch): every block's scene, count,
+// camera terms and tile grid come from its view's entry; `args` holds what the batch shares (the thresholds,
+// the capacity, the schedule).  launch_fill_batch writes entries [first, first + n) of the device array from
+// `chunk` (n <= kBatchChunk) and those views' ranges of the block and tile tables (at most maxBlocks / maxTiles
+// entries of either table are written, whatever the entries say).
+void launch_project_batch(bool halfInput, uint32_t shDegree, const ProjectArgs& args, const BatchFrame& bf,
+                          const DeviceArena& A, hipStream_t stream);
+void launch_fill_batch(const BatchChunk& chunk, uint32_t first, uint32_t n, BatchViewArgs* dst, uint16_t* blockView,
+                       uint32_t maxBlocks, uint16_t* tileView, uint32_t maxTiles, hipStream_t stream);
 // exclusive scan of the per-block sums, total + clamp into the header (GlobalShaders.metal:685-712)
 // project gaussians [0, a.count) of world/harm (already offset to the rank's range) and pack
 // the records of each slab's gaussians into `send` (slab-major, ascending id), counts to sendCounts
@@ -324,8 +375,10 @@ void launch_scan_sums(uint32_t* sums, uint32_t nb, uint32_t cap, TileAssignmentH
 // fusedScan: A.blockSums holds the unscanned block counts (no launch_scan_blocks before it); each
 // workgroup adds up the counts before its own, workgroup 0 also the total (header, blend queue)
 // views (nullable): a batch's items (k_scatter_views): tile ids v * tilesPerView + local tile
+// batch (nullable): a batch of different views (k_scatter_batch): tile ids tileBase of the view + local tile
 void launch_scatter(const ProjectArgs& args, const DeviceArena& A, hipStream_t stream,
-                    const uint32_t* devCount = nullptr, bool fusedScan = false, const ViewBatch* views = nullptr);
+                    const uint32_t* devCount = nullptr, bool fusedScan = false, const ViewBatch* views = nullptr,
+                    const BatchFrame* batch = nullptr);
 // the blend's half-tile lists from the sorted values (skip flags, k_scatter), tiles [tileBegin, +numTiles)
 void launch_half_lists(const uint32_t* sortedVals, uint32_t tileBegin, uint32_t numTiles, const DeviceArena& A,
                        uint32_t tileCount, hipStream_t stream);

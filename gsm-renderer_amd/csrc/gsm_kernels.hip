@@ -304,6 +304,9 @@ __device__ __forceinline__ float2 band_of(const BlendRecordA& ra, short4 r, cons
 #define GSM_VIEWS 1
 #include "gsm_project_body.h"
 #undef GSM_VIEWS
+#define GSM_VIEWS 2
+#include "gsm_project_body.h"
+#undef GSM_VIEWS
 
 // entries [first, first + n) of the per-view array from a kernel argument (plain vector stores): the host's
 // copy of the cameras is consumed when the frame is enqueued, so the call needs no staging buffer that a
@@ -312,6 +315,29 @@ __global__ __launch_bounds__(256) void k_fill_views(ViewChunk chunk, uint32_t n,
     constexpr uint32_t kWords = sizeof(ViewArgs) / 4u;
     const uint32_t* src = (const uint32_t*)&chunk;
     for (uint32_t i = threadIdx.x; i < n * kWords; i += 256u) ((uint32_t*)dst)[i] = src[i];
+}
+
+// The same for a batch of different views (gsm_global_render_batch): entries [first, first + n) of
+// the per-view array, and those views' ranges of the two lookup tables -- view v owns blocks [blockBase, +
+// ceil(count / 256)) of blockView and tiles [tileBase, + tilesX * tilesY) of tileView.  The ranges come from the
+// kernel argument (uniform), the stores are plain vector stores clamped to the tables' sizes.
+__global__ __launch_bounds__(256) void k_fill_batch(BatchChunk chunk, uint32_t first, uint32_t n,
+                                                    BatchViewArgs* __restrict__ dst, uint16_t* __restrict__ blockView,
+                                                    uint32_t maxBlocks, uint16_t* __restrict__ tileView,
+                                                    uint32_t maxTiles) {
+    constexpr uint32_t kWords = sizeof(BatchViewArgs) / 4u;
+    const uint32_t* src = (const uint32_t*)&chunk;
+    for (uint32_t i = threadIdx.x; i < n * kWords; i += 256u) ((uint32_t*)(dst + first))[i] = src[i];
+    for (uint32_t k = 0; k < n; ++k) {
+        const BatchViewArgs& V = chunk.v[k];
+        const uint16_t view = (uint16_t)(first + k);
+        const uint32_t b0 = min(V.blockBase, maxBlocks);
+        const uint32_t b1 = min(V.blockBase + (V.count + kProjectBlock - 1u) / kProjectBlock, maxBlocks);
+        for (uint32_t i = b0 + threadIdx.x; i < b1; i += 256u) blockView[i] = view;
+        const uint32_t t0 = min(V.tg.tileBase, maxTiles);
+        const uint32_t t1 = min(V.tg.tileBase + V.tg.tilesX * V.tg.tilesY, maxTiles);
+        for (uint32_t i = t0 + threadIdx.x; i < t1; i += 256u) tileView[i] = view;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -999,6 +1025,9 @@ __device__ __forceinline__ uint64_t block_sum_prefix(const uint32_t* __restrict_
 #define GSM_VIEWS 1
 #include "gsm_scatter_body.h"
 #undef GSM_VIEWS
+#define GSM_VIEWS 2
+#include "gsm_scatter_body.h"
+#undef GSM_VIEWS
 
 __global__ __launch_bounds__(256) void k_tile_starts(const uint32_t* __restrict__ sortedKeys,
                                                      const TileAssignmentHeader* __restrict__ hdr,
@@ -1159,6 +1188,36 @@ void launch_fill_views(const ViewChunk& chunk, uint32_t first, uint32_t n, ViewA
 }
 
 template <bool HALF>
+static void launch_project_batch_t(uint32_t deg, const ProjectArgs& a, const BatchFrame& bf, const DeviceArena& A,
+                                   hipStream_t s) {
+    if (bf.blocks == 0 && a.schedUnits == 0) return;  // (an empty batch still orders its blend units)
+#define GSM_LAUNCH_PROJB(D)                                                                                          \
+    hipLaunchKernelGGL((k_project_batch<HALF, D>), dim3(bf.blocks + (a.schedUnits ? 1u : 0u)), dim3(kProjectBlock), \
+                       0, s, a, bf.args, bf.blockView, A.renderData, A.bounds, A.rec, A.tileCounts, A.tileMasks,     \
+                       A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax)
+    switch (deg) {
+        case 0: GSM_LAUNCH_PROJB(0); break;
+        case 1: GSM_LAUNCH_PROJB(1); break;
+        case 2: GSM_LAUNCH_PROJB(2); break;
+        default: GSM_LAUNCH_PROJB(3); break;
+    }
+#undef GSM_LAUNCH_PROJB
+}
+
+void launch_project_batch(bool halfInput, uint32_t deg, const ProjectArgs& a, const BatchFrame& bf,
+                          const DeviceArena& A, hipStream_t s) {
+    if (halfInput) launch_project_batch_t<true>(deg, a, bf, A, s);
+    else launch_project_batch_t<false>(deg, a, bf, A, s);
+}
+
+void launch_fill_batch(const BatchChunk& chunk, uint32_t first, uint32_t n, BatchViewArgs* dst, uint16_t* blockView,
+                       uint32_t maxBlocks, uint16_t* tileView, uint32_t maxTiles, hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_fill_batch, dim3(1), dim3(256), 0, s, chunk, first, n > kBatchChunk ? kBatchChunk : n, dst,
+                       blockView, maxBlocks, tileView, maxTiles);
+}
+
+template <bool HALF>
 static void launch_project_part_t(uint32_t deg, const void* world, const void* harm, const ProjectArgs& a,
                                   const SlabTable& slabs, const PartitionBuffers& B, const float2* sincos,
                                   const DeviceArena* A, hipStream_t s) {
@@ -1252,7 +1311,14 @@ void launch_scan_blocks(uint32_t nb, const ProjectArgs& a, const DeviceArena& A,
 }
 
 void launch_scatter(const ProjectArgs& a, const DeviceArena& A, hipStream_t s, const uint32_t* devCount,
-                    bool fusedScan, const ViewBatch* vb) {
+                    bool fusedScan, const ViewBatch* vb, const BatchFrame* bf) {
+    if (bf) {
+        if (bf->blocks == 0) return;
+        hipLaunchKernelGGL(k_scatter_batch, dim3(bf->blocks), dim3(kProjectBlock), 0, s, a, bf->args, bf->blockView,
+                           A.renderData, A.bounds, A.tileCounts, A.tileMasks, A.blockSums, A.keys[0], A.vals[0],
+                           A.sincosTable, A.rec, fusedScan ? 1u : 0u, A.header, A.tileQueue);
+        return;
+    }
     if (vb) {
         const uint32_t vblocks = vb->views * vb->blocksPerView;
         if (vblocks == 0) return;

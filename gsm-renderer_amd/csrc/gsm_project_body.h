@@ -1,7 +1,24 @@
-// gsm_project_body.h -- the text of k_project, compiled twice by gsm_kernels.hip: as the single frame's
+// gsm_project_body.h -- the text of k_project, compiled three times by gsm_kernels.hip: as the single frame's
 // kernel (GSM_VIEWS 0: k_project, exactly the kernel it was before batches of views existed; an item is its
-// gaussian id) and as the projection of a batch of views (GSM_VIEWS 1: k_project_views).  No include guard.
-#if GSM_VIEWS
+// gaussian id), as the projection of a batch of views of one scene (GSM_VIEWS 1: k_project_views) and as the
+// projection of a batch of views of different scenes and sizes (GSM_VIEWS 2: k_project_batch).  No include guard.
+#if GSM_VIEWS == 2
+// The projection of a batch of different views (gsm_global_render_batch): block b belongs to view
+// blockView[b] -- uniform per block, one 2-byte load -- and projects gaussians [(b - blockBase) * 256, + 256) of
+// that view's scene under its camera onto its own tile grid; everything the view owns comes from its entry of
+// views[] (BatchViewArgs) by scalar loads, P keeps what the batch shares (the thresholds, the schedule).  The
+// per-gaussian arrays are written at the block's items, b * 256 + thread; the tile tests and counts are those
+// of k_project for that scene, camera and size.
+template <bool HALF, int DEG>
+__global__ __launch_bounds__(kProjectBlock) void k_project_batch(
+    ProjectArgs P, const BatchViewArgs* __restrict__ views, const uint16_t* __restrict__ blockView,
+    GaussianRenderData* __restrict__ outRD, short4* __restrict__ outBounds, BlendRecord* __restrict__ outRec,
+    uint32_t* __restrict__ counts, uint32_t* __restrict__ masks, uint32_t* __restrict__ blockSums,
+    const float2* __restrict__ sincos, const uint16_t* __restrict__ unitCost, uint32_t* __restrict__ unitOrder,
+    uint32_t* __restrict__ costMax) {
+    const void* __restrict__ world = nullptr;  // the block's scene: its view's (below)
+    const void* __restrict__ harm = nullptr;
+#elif GSM_VIEWS
 // The projection of a batch of views (gsm_global_render_views): block b projects gaussians
 // [(b % blocksPerView) * 256, + 256) under view b / blocksPerView -- uniform per block -- whose camera and
 // derived constants come from views[] (ViewArgs); P holds what the batch shares (the frame's tile grid,
@@ -35,7 +52,29 @@ __global__ __launch_bounds__(kProjectBlock) void k_project(
         }
     }
     const uint32_t blk = blockIdx.x - (P.schedUnits ? 1u : 0u);
-#if GSM_VIEWS
+#if GSM_VIEWS == 2
+    // the block's view (uniform: scalar loads) and its first gaussian; items are written at blk * 256 + thread
+    uint32_t gblk;
+    {
+        const BatchViewArgs& V = views[__builtin_amdgcn_readfirstlane((uint32_t)blockView[blk])];
+        gblk = blk - V.blockBase;
+        world = V.world;
+        harm = V.harm;
+        P.cam = V.cam;
+        P.bin = V.bin;
+        P.rowBegin = 0;
+        P.rowEnd = V.bin.tilesY;
+        P.rowStride = 1;
+        P.count = V.count;
+        P.limX = V.limX;
+        P.limY = V.limY;
+        P.focalX = V.focalX;
+        P.focalY = V.focalY;
+        P.maxEig = V.maxEig;
+        P.adjFar = V.adjFar;
+        P.adjDen = V.adjDen;
+    }
+#elif GSM_VIEWS
     // the block's view (uniform: scalar loads) and its first gaussian; items are written at blk * 256 + thread
     const uint32_t view = blk / blocksPerView, gblk = blk - view * blocksPerView;
     {

@@ -278,6 +278,141 @@ gsm_status GlobalRenderer::renderViews(hipStream_t s, const gsm_gaussian_input& 
                     }, nullptr, false, nullptr, &vf);
 }
 
+gsm_status GlobalRenderer::renderBatch(hipStream_t s, const gsm_global_view* views, uint32_t viewCount) {
+    // Every check before anything is enqueued, one kind of check after another over all views (the first
+    // failing kind decides, within it the lowest view): counts, dimensions, tiles, missing buffers, sizes,
+    // sh_components, tile rows.  (The counts of a NULL array cannot be read: that is the missing buffer.)
+    if (viewCount == 0) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
+    if (!views) return GSM_ERR_MISSING_REQUIRED_BUFFER;
+    uint64_t items = 0, allTiles = 0;
+    for (uint32_t v = 0; v < viewCount; ++v) {  // (gsm_global_render's rule per view: an empty scene is a frame)
+        if (views[v].input.gaussian_count > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
+        items += ((uint64_t)views[v].input.gaussian_count + kProjectBlock - 1) / kProjectBlock * kProjectBlock;
+    }
+    if (items > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;  // (the values keep 30 bits of item)
+    for (uint32_t v = 0; v < viewCount; ++v) {
+        const gsm_global_view& V = views[v];
+        if (V.width == 0 || V.height == 0 || V.width > maxWidth_ || V.height > maxHeight_)
+            return GSM_ERR_INVALID_DIMENSIONS;
+        allTiles += tiles_of(V.width, V.height);
+    }
+    if (allTiles > tileCount_ || allTiles > 65535u) return GSM_ERR_INVALID_TILE_COUNT;
+    for (uint32_t v = 0; v < viewCount; ++v) {
+        const gsm_global_view& V = views[v];
+        if (!V.color || (V.input.gaussian_count > 0 && (!V.input.gaussians || !V.input.harmonics)))
+            return GSM_ERR_MISSING_REQUIRED_BUFFER;
+    }
+    for (uint32_t v = 0; v < viewCount; ++v) {  // (everything above passed: what is left of validate_frame is sizes)
+        const gsm_global_view& V = views[v];
+        const gsm_status st = validate_frame(config_, maxGaussians_, maxWidth_, maxHeight_, V.input.gaussian_count,
+                                             true, false, V.width, V.height, V.color, V.color_pitch_bytes, 1, V.depth,
+                                             V.depth_pitch_bytes);
+        if (st != GSM_OK) return st;
+    }
+    for (uint32_t v = 1; v < viewCount; ++v)
+        if (views[v].input.sh_components != views[0].input.sh_components) return GSM_ERR_INVALID_ARGUMENT;
+    if (rowBegin_ != 0 || rowEnd_ != tilesY_ || rowStride_ != 1) return GSM_ERR_UNSUPPORTED;  // (set_tile_rows)
+    if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
+    // the per-view array and the two lookup tables: allocated by the handle's first batch, for the most views
+    // its tile space and its item space hold (every view takes at least one tile; the host copies are reserved
+    // with them, so no later batch allocates)
+    const uint32_t maxBlocks = (uint32_t)(((uint64_t)maxGaussians_ + kProjectBlock - 1) / kProjectBlock);
+    if (!arena_.batchArgs) {
+        const uint32_t mv = std::min(tileCount_, 65535u);
+        BatchViewArgs* args = nullptr;
+        uint16_t *bv = nullptr, *tv = nullptr;
+        gsm_status st = allocs_.alloc((void**)&args, (size_t)mv * sizeof(BatchViewArgs));
+        if (st == GSM_OK) st = allocs_.alloc((void**)&bv, (size_t)maxBlocks * sizeof(uint16_t));
+        if (st == GSM_OK) st = allocs_.alloc((void**)&tv, (size_t)tileCount_ * sizeof(uint16_t));
+        if (st != GSM_OK) return st;
+        batchHost_.reserve(mv);
+        batchSig_.reserve(3 * (size_t)mv);
+        schedBatchSig_.reserve(3 * (size_t)mv);
+        arena_.batchArgs = args;
+        arena_.batchBlockView = bv;
+        arena_.batchTileView = tv;
+        maxBatchViews_ = mv;
+    }
+    (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's)
+    // the host copy of the per-view entries (`views` is consumed before the call returns): each view's own
+    // frameArgs -- the camera terms depend on its width and height -- on its own tile grid, rows [0, tilesY)
+    const uint32_t sh = views[0].input.sh_components;
+    batchHost_.resize(viewCount);
+    batchSig_.clear();
+    uint32_t blockBase = 0, tileBase = 0, countSum = 0;
+    for (uint32_t v = 0; v < viewCount; ++v) {
+        const gsm_global_view& V = views[v];
+        const uint32_t n = V.input.gaussian_count;
+        const ProjectArgs pv = frameArgs(V.camera, V.width, V.height, n, sh);
+        BatchViewArgs& d = batchHost_[v];
+        std::memset(&d, 0, sizeof(d));
+        d.cam = pv.cam;
+        d.limX = pv.limX;
+        d.limY = pv.limY;
+        d.focalX = pv.focalX;
+        d.focalY = pv.focalY;
+        d.maxEig = pv.maxEig;
+        d.adjFar = pv.adjFar;
+        d.adjDen = pv.adjDen;
+        d.count = n;
+        d.bin = pv.bin;
+        d.bin.tilesX = (V.width + kTileWidth - 1) / kTileWidth;
+        d.bin.tilesY = (V.height + kTileHeight - 1) / kTileHeight;
+        d.blockBase = blockBase;
+        d.world = V.input.gaussians;
+        d.harm = V.input.harmonics;
+        d.tg.color = (uint8_t*)V.color;
+        d.tg.depth = (uint8_t*)V.depth;
+        d.tg.colorPitch = V.color_pitch_bytes;
+        d.tg.depthPitch = V.depth ? V.depth_pitch_bytes : 0;
+        d.tg.tileBase = tileBase;
+        d.tg.tilesX = d.bin.tilesX;
+        d.tg.tilesY = d.bin.tilesY;
+        d.tg.width = V.width;
+        d.tg.height = V.height;
+        // the wide stores (16-B colour, 4-B depth pairs) where this view's targets are aligned for them, as
+        // launch_blend decides for a single frame; the bytes are the same either way
+        d.tg.vec = ((((uintptr_t)V.color) & 15u) == 0 && (V.color_pitch_bytes & 15u) == 0 &&
+                    (!V.depth || ((((uintptr_t)V.depth) & 7u) == 0 && (V.depth_pitch_bytes & 7u) == 0)))
+                       ? 1u
+                       : 0u;
+        blockBase += (n + kProjectBlock - 1) / kProjectBlock;
+        tileBase += d.bin.tilesX * d.bin.tilesY;
+        countSum += n;
+        batchSig_.push_back(V.width);
+        batchSig_.push_back(V.height);
+        batchSig_.push_back(n);
+    }
+    for (uint32_t v0 = 0; v0 < viewCount; v0 += kBatchChunk) {
+        BatchChunk c;
+        const uint32_t n = std::min(kBatchChunk, viewCount - v0);
+        std::memset(&c, 0, sizeof(c));
+        std::memcpy(c.v, batchHost_.data() + v0, (size_t)n * sizeof(BatchViewArgs));
+        launch_fill_batch(c, v0, n, arena_.batchArgs, arena_.batchBlockView, maxBlocks, arena_.batchTileView, tileCount_,
+                          s);
+    }
+    // what the batch shares: the thresholds, the capacity and the schedule; count = the batch's gaussians (counters)
+    ProjectArgs a = frameArgs(views[0].camera, views[0].width, views[0].height, countSum, sh);
+    a.bin.tilesX = batchHost_[0].bin.tilesX;
+    a.bin.tilesY = batchHost_[0].bin.tilesY;
+    a.rowBegin = 0;
+    a.rowEnd = a.bin.tilesY;
+    a.rowStride = 1;
+    ViewFrame vf;
+    vf.batchFrame.views = viewCount;
+    vf.batchFrame.blocks = blockBase;
+    vf.batchFrame.tiles = tileBase;
+    vf.batchFrame.args = arena_.batchArgs;
+    vf.batchFrame.blockView = arena_.batchBlockView;
+    vf.batchFrame.tileView = arena_.batchTileView;
+    const uint32_t deg = sh_degree(sh);
+    const bool half = config_.precision == GSM_PRECISION_FLOAT16;
+    return runFrame(s, a, views[0].width, views[0].height, views[0].color, views[0].color_pitch_bytes, views[0].depth,
+                    views[0].depth_pitch_bytes,
+                    [&](const ProjectArgs& pa) { launch_project_batch(half, deg, pa, vf.batchFrame, arena_, s); },
+                    nullptr, false, nullptr, &vf);
+}
+
 gsm_status GlobalRenderer::renderRecords(hipStream_t s, const void* records, uint32_t count, uint32_t width,
                                          uint32_t height, void* color, size_t colorPitch, void* depth,
                                          size_t depthPitch, const uint32_t* devCount, bool preOrdered,
@@ -412,15 +547,23 @@ gsm_status GlobalRenderer::partitionPush(hipStream_t s, uint32_t world, uint32_t
     return GSM_OK;
 }
 
-uint32_t GlobalRenderer::scheduleUnits(hipStream_t s, uint32_t width, uint32_t height, uint32_t views) {
+uint32_t GlobalRenderer::scheduleUnits(hipStream_t s, uint32_t width, uint32_t height, uint32_t views,
+                                       uint32_t batchTiles) {
     // (a batch of views: the units of views * tiles(width, height) tiles; the view count is part of the key, so
-    // a batch neither inherits nor leaves behind a single frame's costs)
-    const uint32_t tiles = views ? views * tiles_of(width, height) : rowCount() * tilesX_;
+    // a batch neither inherits nor leaves behind a single frame's costs.  A batch of different views: the units
+    // of its batchTiles tiles, keyed by its whole signature batchSig_, compared word for word)
+    const uint32_t tiles = batchTiles ? batchTiles : views ? views * tiles_of(width, height) : rowCount() * tilesX_;
     const uint32_t upt = blend_units_per_tile(tiles, dev_.numCUs);
     const uint32_t units = tiles * upt;
-    const uint64_t key = ((uint64_t)upt << 60) ^ ((uint64_t)width << 40) ^ ((uint64_t)height << 20) ^
-                         ((uint64_t)rowStride_ << 30) ^ ((uint64_t)rowBegin_ << 10) ^ rowEnd_;
-    if (key != schedKey_ || views != schedViews_) {  // new geometry: no walks to order by yet (either schedule set)
+    const uint64_t key = batchTiles ? ~0ull
+                                    : ((uint64_t)upt << 60) ^ ((uint64_t)width << 40) ^ ((uint64_t)height << 20) ^
+                                          ((uint64_t)rowStride_ << 30) ^ ((uint64_t)rowBegin_ << 10) ^ rowEnd_;
+    const bool isBatch = batchTiles != 0;
+    bool changed = isBatch != schedBatch_ || key != schedKey_ || views != schedViews_;
+    if (isBatch && !changed) changed = batchSig_ != schedBatchSig_;
+    if (isBatch && changed) schedBatchSig_.assign(batchSig_.begin(), batchSig_.end());  // (reserved: no allocation)
+    schedBatch_ = isBatch;
+    if (changed) {  // new geometry: no walks to order by yet (either schedule set)
         for (const ScheduleSet& t : sched_) {
             if (!t.unitCost) continue;
             hipMemsetAsync(t.unitCost, 0, (size_t)units * sizeof(uint16_t), s);
@@ -444,8 +587,10 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     // for readback; the product path writes neither (the blend reads its records and half lists)
     const bool capture = (profiling & (2 | 16)) != 0;
     // (a batch of views: a.count gaussians per view, every view's items padded to whole blocks)
-    const uint32_t nb = views ? views->batch.views * views->batch.blocksPerView
-                              : (a.count + kProjectBlock - 1) / kProjectBlock;
+    const BatchFrame* batch = views && views->batchFrame.views ? &views->batchFrame : nullptr;
+    const uint32_t nb = batch ? batch->blocks
+                        : views ? views->batch.views * views->batch.blocksPerView
+                                : (a.count + kProjectBlock - 1) / kProjectBlock;
     // GaussianRenderData for readback only when profiling (bits 0, 1), gsm_debug.h
     ProjectArgs fa = a;
     fa.keepRenderData = capture ? 1u : 0u;
@@ -458,7 +603,9 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     // The ordering only needs those costs: one extra workgroup of the projection launch does it
     // (unit_order_block) while the others project (k_project, or k_records_in on the records path;
     // the multi-GPU frame orders them earlier, in its partition projection: preOrdered).
-    const uint32_t units = preOrdered ? 0u : scheduleUnits(s, width, height, views ? views->batch.views : 0u);
+    const uint32_t units = preOrdered ? 0u
+                                      : scheduleUnits(s, width, height, batch ? batch->views : views ? views->batch.views : 0u,
+                                                      batch ? batch->tiles : 0u);
     const bool costOrder = preOrdered ? tuning_.costOrder : units > 0;
     fa.schedUnits = units;
     // (written on every scheduled frame: the blend's remaining-walk priorities read the longest walk too)
@@ -475,7 +622,7 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     const bool fusedScan = tuning_.fusedScan && nb > 0 && nb <= (devCount ? 4u : 1u) * kFusedScanMaxBlocks;
     if (!fusedScan) launch_scan_blocks(nb, a, arena_, s, devCount);
     timer_.record(2, s);
-    launch_scatter(a, arena_, s, devCount, fusedScan, views ? &views->batch : nullptr);
+    launch_scatter(a, arena_, s, devCount, fusedScan, views && !batch ? &views->batch : nullptr, batch);
     if (keep) {  // preserve the unsorted assignment arrays for readback
         hipMemcpyAsync(arena_.keysKeep, arena_.keys[0], (size_t)maxAssignments_ * 4, hipMemcpyDeviceToDevice, s);
         hipMemcpyAsync(arena_.valsKeep, arena_.vals[0], (size_t)maxAssignments_ * 4, hipMemcpyDeviceToDevice, s);
@@ -494,7 +641,14 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     g.width = width;
     g.height = height;
     g.maxAssignments = maxAssignments_;
-    if (views) {  // the frame's own tile grid, one after another in the handle's tile space
+    if (batch) {  // every view on its own grid, one after another in the handle's tile space
+        g.rowBegin = 0;
+        g.rowStride = 1;
+        g.views = batch->views;
+        g.batchTiles = batch->tiles;
+        g.batchArgs = batch->args;
+        g.batchTileView = batch->tileView;
+    } else if (views) {  // the frame's own tile grid, one after another in the handle's tile space
         g.tilesX = a.bin.tilesX;
         g.tilesY = a.bin.tilesY;
         g.rowBegin = 0;

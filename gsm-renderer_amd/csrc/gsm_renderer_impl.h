@@ -28,6 +28,9 @@ class GlobalRenderer {
                            uint32_t viewCount, uint32_t width, uint32_t height, void* color, size_t colorPitch,
                            size_t colorStride, void* depth, size_t depthPitch, size_t depthStride);
 
+    // views of different scenes and sizes in one frame (gsm_global_render_batch)
+    gsm_status renderBatch(hipStream_t stream, const gsm_global_view* views, uint32_t viewCount);
+
     // multi-GPU partition: project ids [first, first+count) and pack the splat
     // records of every tile-row slab they meet; render a slab from the records it received
     gsm_status projectPartition(hipStream_t stream, const gsm_gaussian_input& input,
@@ -94,9 +97,11 @@ class GlobalRenderer {
                           uint32_t shComponents) const;
     // scan, scatter, sort, headers and blend after `front` filled the per-gaussian arrays
     // (views: a batch -- `a` holds what its views share, the targets are view 0's)
+    // (batchFrame.views > 0: a batch of different views -- `a` holds what they share, nothing per view)
     struct ViewFrame {
         ViewBatch batch;
         size_t colorStride = 0, depthStride = 0;
+        BatchFrame batchFrame;
     };
     template <class Front>
     gsm_status runFrame(hipStream_t s, const ProjectArgs& a, uint32_t width, uint32_t height, void* color,
@@ -105,7 +110,10 @@ class GlobalRenderer {
                         const MgArrive* blendArrive = nullptr, const ViewFrame* views = nullptr);
     // the blend schedule's unit count for the current rows, or for a batch of `views` frames (0 when cost
     // order is off), its cost arrays cleared when the geometry or the view count changed
-    uint32_t scheduleUnits(hipStream_t s, uint32_t width, uint32_t height, uint32_t views = 0);
+    // (batchTiles > 0: a batch of different views, keyed by its signature batchSig_ -- the view count and every
+    // view's width, height and count)
+    uint32_t scheduleUnits(hipStream_t s, uint32_t width, uint32_t height, uint32_t views = 0,
+                           uint32_t batchTiles = 0);
     static uint32_t tiles_of(uint32_t width, uint32_t height);  // tiles of a width x height frame
     PartitionBuffers part_;
     uint32_t partCount_ = 0;  // ids of the last partitionCounts
@@ -151,6 +159,11 @@ class GlobalRenderer {
     uint32_t schedViews_ = 0;                 // ... and the view count (0: a single frame)
     std::vector<ViewArgs> viewHost_;          // the last batch's per-view terms (render_views)
     uint32_t maxViews_ = 0;                   // entries of arena_.viewArgs
+    std::vector<BatchViewArgs> batchHost_;    // the last batch's per-view entries (render_batch)
+    uint32_t maxBatchViews_ = 0;              // entries of arena_.batchArgs
+    std::vector<uint32_t> batchSig_;          // this call's batch signature: width, height, count of every view
+    std::vector<uint32_t> schedBatchSig_;     // the signature the unit costs belong to (schedBatch_)
+    bool schedBatch_ = false;                 // the unit costs belong to a batch of different views
 };
 
 }  // namespace gsm

@@ -1,7 +1,20 @@
-// gsm_scatter_body.h -- the text of k_scatter, compiled twice by gsm_kernels.hip: as the single frame's
-// kernel (GSM_VIEWS 0: k_scatter, exactly the kernel it was before batches of views existed) and as the
-// scatter of a batch of views (GSM_VIEWS 1: k_scatter_views).  No include guard.
-#if GSM_VIEWS
+// gsm_scatter_body.h -- the text of k_scatter, compiled three times by gsm_kernels.hip: as the single frame's
+// kernel (GSM_VIEWS 0: k_scatter, exactly the kernel it was before batches of views existed), as the scatter
+// of a batch of views of one scene (GSM_VIEWS 1: k_scatter_views) and as the scatter of a batch of views of
+// different scenes and sizes (GSM_VIEWS 2: k_scatter_batch).  No include guard.
+#if GSM_VIEWS == 2
+// The scatter of a batch of different views (k_project_batch's items): every workgroup holds items
+// of one view (blockView, uniform), the items past that view's count hold no gaussian, a tile id is the view's
+// tileBase + its local tile on the view's own grid, and the rows are [0, tilesY) of that grid.  Slot order within
+// a tile is ascending item = ascending gaussian id, as the single frame's.
+__global__ __launch_bounds__(kProjectBlock) void k_scatter_batch(
+    ProjectArgs P, const BatchViewArgs* __restrict__ views, const uint16_t* __restrict__ blockView,
+    const GaussianRenderData* __restrict__ rd, const short4* __restrict__ bounds,
+    const uint32_t* __restrict__ counts, const uint32_t* __restrict__ masks,
+    const uint32_t* __restrict__ blockOffsets, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+    const float2* __restrict__ sincos, const BlendRecord* __restrict__ rec, uint32_t fusedScan,
+    TileAssignmentHeader* __restrict__ hdr, uint32_t* __restrict__ blendQueue) {
+#elif GSM_VIEWS
 // The scatter of a batch of views (k_project_views' items): every workgroup holds items of one
 // view, the items past the view's count hold no gaussian, and a tile id is view * tilesPerView + the view's
 // local tile.  Slot order within a tile is ascending item = ascending gaussian id, as the single frame's.
@@ -34,7 +47,24 @@ __global__ __launch_bounds__(kProjectBlock) void k_scatter(
     constexpr uint16_t kNoOwner = 0xFFFFu;
     __shared__ uint16_t sOwn[kOwnCap];
     const uint32_t gid = blockIdx.x * kProjectBlock + threadIdx.x;
-#if GSM_VIEWS
+#if GSM_VIEWS == 2
+    // every item of the batch (whole blocks per view); the thread's item holds a gaussian below its view's count
+    const uint32_t n = gridDim.x * kProjectBlock;
+    uint32_t tileBase;
+    bool isItem;
+    {
+        const BatchViewArgs& V = views[__builtin_amdgcn_readfirstlane((uint32_t)blockView[blockIdx.x])];
+        isItem = (blockIdx.x - V.blockBase) * kProjectBlock + threadIdx.x < V.count;
+        tileBase = V.tg.tileBase;
+        P.bin = V.bin;
+        P.rowBegin = 0;
+        P.rowEnd = V.bin.tilesY;
+        P.rowStride = 1;
+        P.count = V.count;
+    }
+#define GSM_TILE_ID(t) (tileBase + (uint32_t)(t))
+#define GSM_IS_ITEM isItem
+#elif GSM_VIEWS
     // every item of the batch (whole blocks per view); the thread's item holds a gaussian below the view's count
     const uint32_t n = gridDim.x * kProjectBlock;
     const uint32_t view = blockIdx.x / blocksPerView;

@@ -140,9 +140,16 @@ struct FrameGeometry {
     // after view v - 1's.  views == 0: a single frame.
     uint32_t views = 0, tilesPerView = 0;
     size_t colorViewStride = 0, depthViewStride = 0;
+    // A batch of views of different scenes and sizes (gsm_global_render_batch): batchTiles > 0
+    // tiles in all, every view on its own grid; the blend reads a unit's view from batchTileView and its
+    // targets, size and grid from that view's entry of batchArgs (BatchViewArgs, device pointers).
+    uint32_t batchTiles = 0;
+    const void* batchArgs = nullptr;
+    const uint16_t* batchTileView = nullptr;
 };
 // tiles the frame's sort and blend cover
 inline uint32_t frame_tiles(const FrameGeometry& g) {
+    if (g.batchTiles) return g.batchTiles;
     return g.views ? g.views * g.tilesPerView : g.rowCount * g.tilesX;
 }
 

@@ -153,6 +153,20 @@ class CameraParams:
                 "focal_y": self.focal_y, "near": self.near, "far": self.far}
 
 
+@dataclass
+class BatchView:
+    """gsm_global_view: one view of GlobalRenderer.render_batch -- its own scene, camera, frame size and targets
+    (depth None: this view writes no depth; pitches None: width * bytes per pixel / width * 2)."""
+    input: GaussianInput
+    camera: CameraParams
+    width: int
+    height: int
+    color: "torch.Tensor"
+    depth: Optional["torch.Tensor"] = None
+    color_pitch: Optional[int] = None
+    depth_pitch: Optional[int] = None
+
+
 # ---------------------------------------------------------------------------
 # ctypes layer
 # ---------------------------------------------------------------------------
@@ -171,6 +185,12 @@ class _Camera(C.Structure):
     _fields_ = [("view", C.c_float * 16), ("proj", C.c_float * 16), ("position", C.c_float * 3),
                 ("focal_x", C.c_float), ("focal_y", C.c_float),
                 ("near_plane", C.c_float), ("far_plane", C.c_float)]
+
+
+class _GlobalView(C.Structure):  # gsm_global_view
+    _fields_ = [("input", _Input), ("camera", _Camera), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("color", C.c_void_p), ("color_pitch_bytes", C.c_size_t),
+                ("depth", C.c_void_p), ("depth_pitch_bytes", C.c_size_t)]
 
 
 class _Counters(C.Structure):
@@ -213,6 +233,7 @@ _SIGNATURES = {
     "gsm_global_render_views": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera), C.c_uint32,
                                  C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
                                  C.c_size_t, C.c_size_t], C.c_int),
+    "gsm_global_render_batch": ([C.c_void_p, C.c_void_p, C.POINTER(_GlobalView), C.c_uint32], C.c_int),
     "gsm_global_render_stereo": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera),
                                   C.POINTER(_Camera), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                   C.c_void_p, C.c_size_t], C.c_int),
@@ -467,6 +488,24 @@ class GlobalRenderer(_Renderer):
         st = _lib().gsm_global_render_views(self._h, _stream_handle(stream), C.byref(inp), cams, n, int(width),
                                             int(height), _ptr(color_texture), cp, cs, _ptr(depth_texture), dp, ds)
         _check(st, "gsm_global_render_views")
+
+    def render_batch(self, views, stream=None):
+        """gsm_global_render_batch: the BatchView list `views` -- different scenes, sizes and targets -- in one
+        frame; every view's bytes equal those of `render` for that view alone.  views None: a NULL array with
+        view_count 1 (the C entry's error path)."""
+        n = 1 if views is None else len(views)
+        arr = None
+        if views is not None:
+            arr = (_GlobalView * max(n, 1))()
+            for g, v in zip(arr, views):
+                g.input = _Input(_ptr(v.input.gaussians), _ptr(v.input.harmonics), int(v.input.gaussian_count),
+                                 int(v.input.sh_components))
+                g.camera = _camera_struct(v.camera)
+                g.width, g.height = int(v.width), int(v.height)
+                g.color, g.depth = _ptr(v.color), _ptr(v.depth)
+                g.color_pitch_bytes = int(v.color_pitch) if v.color_pitch is not None else int(v.width) * self._bpp
+                g.depth_pitch_bytes = int(v.depth_pitch) if v.depth_pitch is not None else int(v.width) * 2
+        _check(_lib().gsm_global_render_batch(self._h, _stream_handle(stream), arr, n), "gsm_global_render_batch")
 
     def project_partition(self, input: GaussianInput, camera: CameraParams, width: int, height: int,
                           first: int, count: int, slab_rows, send, send_capacity: int, send_counts,

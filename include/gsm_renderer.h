@@ -158,6 +158,51 @@ gsm_status gsm_global_render_views(gsm_renderer *renderer, void *stream, const g
                                    void *color, size_t color_pitch_bytes, size_t color_view_stride_bytes,
                                    void *depth, size_t depth_pitch_bytes, size_t depth_view_stride_bytes);
 
+/* One view of a batch (gsm_global_render_batch): its own scene, camera, frame size and targets. */
+typedef struct {
+    gsm_gaussian_input input;      /* this view's scene: device pointers, count, sh_components */
+    gsm_camera_params  camera;
+    uint32_t width, height;        /* this view's frame */
+    void    *color;  size_t color_pitch_bytes;   /* config.color_format, height rows */
+    void    *depth;  size_t depth_pitch_bytes;   /* r16f or NULL (per view) */
+} gsm_global_view;
+#ifdef __cplusplus
+static_assert(sizeof(gsm_global_view) == 224, "gsm_global_view is 224 bytes");
+#else
+_Static_assert(sizeof(gsm_global_view) == 224, "gsm_global_view is 224 bytes");
+#endif
+
+/* Views of different scenes and sizes in one frame (no reference analogue): view_count views,
+ * each with its own input, camera, width x height and targets, rendered by one launch chain over a combined
+ * item and tile space.  Every view's bytes equal those of gsm_global_render for that view alone.  Views may
+ * share or differ in scene, count, size and targets (a side-by-side pair: two views into one target, the
+ * second starting width * bytes-per-pixel into the row, both with the shared pitch), but two views must not
+ * overlap in target memory -- this is not checked.  All views use the handle's precision and colour format
+ * and the same sh_components; depth may be NULL for some views and not for others.
+ * Enqueue-only on `stream`; `views` is host memory and is consumed before the call returns.  Only small
+ * per-view arrays are allocated, by the handle's first batch; nothing per frame after it.
+ *
+ * Checked before anything is enqueued; the first failing check in this order decides, within a check the
+ * lowest view index:
+ *   GSM_ERR_INVALID_GAUSSIAN_COUNT   view_count == 0, a gaussian_count > max_gaussians, or
+ *                                    sum of roundup(gaussian_count, 256) > max_gaussians (a view's items
+ *                                    start on a 256-item boundary; a count of 0 is an empty frame, as for
+ *                                    gsm_global_render);
+ *   GSM_ERR_INVALID_DIMENSIONS       a width or height of zero, or above max_width / max_height;
+ *   GSM_ERR_INVALID_TILE_COUNT       sum of tiles(width, height) exceeds the handle's tile count
+ *                                    (tiles(max_width, max_height), 32 x 16 pixel tiles) or 65535;
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  views NULL (with view_count >= 1: before every other check, since
+ *                                    nothing of it can be read), a view's color NULL, or its gaussians /
+ *                                    harmonics NULL with a count > 0;
+ *   GSM_ERR_INVALID_BUFFER_SIZE      a pitch smaller than a row, or a target or pitch misaligned (colour
+ *                                    4 bytes, depth 2);
+ *   GSM_ERR_INVALID_ARGUMENT         views that differ in sh_components;
+ *   GSM_ERR_UNSUPPORTED              the handle is restricted to tile rows (gsm_global_set_tile_rows).
+ * The assignment capacity (4 * max_gaussians) is shared by the batch: a batch whose views together
+ * exceed it sets the overflow counter (gsm_debug.h), and no parity is promised for that frame. */
+gsm_status gsm_global_render_batch(gsm_renderer *renderer, void *stream,
+                                   const gsm_global_view *views, uint32_t view_count);
+
 /* GlobalRenderer.renderStereo (GlobalRenderer.swift:240-255) calls fatalError for
  * every target; this entry returns GSM_ERR_UNSUPPORTED instead. */
 gsm_status gsm_global_render_stereo(gsm_renderer *renderer, void *stream,
