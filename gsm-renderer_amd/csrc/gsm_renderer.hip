@@ -205,6 +205,38 @@ uint32_t GlobalRenderer::tiles_of(uint32_t width, uint32_t height) {
     return ((width + kTileWidth - 1) / kTileWidth) * ((height + kTileHeight - 1) / kTileHeight);
 }
 
+// What the two batch entries below share on the host.
+// the per-view terms of an entry (ViewArgs, BatchViewArgs): the camera and what projection_uniforms derives from it
+template <class Entry>
+static void set_view_terms(Entry& d, const ProjectArgs& pv) {
+    d.cam = pv.cam;
+    d.limX = pv.limX;
+    d.limY = pv.limY;
+    d.focalX = pv.focalX;
+    d.focalY = pv.focalY;
+    d.maxEig = pv.maxEig;
+    d.adjFar = pv.adjFar;
+    d.adjDen = pv.adjDen;
+}
+
+bool GlobalRenderer::frameSizeOk(uint32_t width, uint32_t height) const {
+    return width != 0 && height != 0 && width <= maxWidth_ && height <= maxHeight_;
+}
+
+bool GlobalRenderer::batchTilesOk(uint64_t allTiles) const { return allTiles <= tileCount_ && allTiles <= 65535u; }
+
+ProjectArgs GlobalRenderer::batchSharedArgs(const gsm_camera_params& camera0, uint32_t width0, uint32_t height0,
+                                            uint32_t count, uint32_t shComponents) const {
+    // what a batch shares: view 0's arguments on that view's own tile grid, rows [0, tilesY)
+    ProjectArgs a = frameArgs(camera0, width0, height0, count, shComponents);
+    a.bin.tilesX = (width0 + kTileWidth - 1) / kTileWidth;
+    a.bin.tilesY = (height0 + kTileHeight - 1) / kTileHeight;
+    a.rowBegin = 0;
+    a.rowEnd = a.bin.tilesY;
+    a.rowStride = 1;
+    return a;
+}
+
 gsm_status GlobalRenderer::renderViews(hipStream_t s, const gsm_gaussian_input& in, const gsm_camera_params* cameras,
                                        uint32_t viewCount, uint32_t width, uint32_t height, void* color,
                                        size_t colorPitch, size_t colorStride, void* depth, size_t depthPitch,
@@ -214,10 +246,9 @@ gsm_status GlobalRenderer::renderViews(hipStream_t s, const gsm_gaussian_input& 
     const uint64_t padded = ((uint64_t)in.gaussian_count + kProjectBlock - 1) / kProjectBlock * kProjectBlock;
     if (viewCount == 0 || (uint64_t)viewCount * padded > maxGaussians_ || in.gaussian_count > maxGaussians_)
         return GSM_ERR_INVALID_GAUSSIAN_COUNT;
-    if (width == 0 || height == 0 || width > maxWidth_ || height > maxHeight_) return GSM_ERR_INVALID_DIMENSIONS;
+    if (!frameSizeOk(width, height)) return GSM_ERR_INVALID_DIMENSIONS;
     const uint32_t T = tiles_of(width, height);
-    const uint64_t allTiles = (uint64_t)viewCount * T;
-    if (allTiles > tileCount_ || allTiles > 65535u) return GSM_ERR_INVALID_TILE_COUNT;
+    if (!batchTilesOk((uint64_t)viewCount * T)) return GSM_ERR_INVALID_TILE_COUNT;
     if (!cameras) return GSM_ERR_MISSING_REQUIRED_BUFFER;
     gsm_status st = validateFrame(in.gaussian_count, !in.gaussians || !in.harmonics, width, height, color, colorPitch,
                                   depth, depthPitch);
@@ -225,7 +256,7 @@ gsm_status GlobalRenderer::renderViews(hipStream_t s, const gsm_gaussian_input& 
     // a view's rows fit in its stride, and every view's first row is as aligned as validate_frame asks of the first
     if (colorStride < (size_t)height * colorPitch || (colorStride & 3u)) return GSM_ERR_INVALID_BUFFER_SIZE;
     if (depth && (depthStride < (size_t)height * depthPitch || (depthStride & 1u))) return GSM_ERR_INVALID_BUFFER_SIZE;
-    if (rowBegin_ != 0 || rowEnd_ != tilesY_ || rowStride_ != 1) return GSM_ERR_UNSUPPORTED;  // (set_tile_rows)
+    if (tileRowsRestricted()) return GSM_ERR_UNSUPPORTED;  // (set_tile_rows)
     // the per-view array: allocated by the first batch, for the most views the handle's tile space holds
     if (!arena_.viewArgs) {
         maxViews_ = std::min(tileCount_, 65535u);
@@ -233,13 +264,7 @@ gsm_status GlobalRenderer::renderViews(hipStream_t s, const gsm_gaussian_input& 
         if (st != GSM_OK) return st;
     }
     (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's)
-    // what the batch shares: view 0's arguments on the frame's own tile grid, rows [0, tilesY)
-    ProjectArgs a = frameArgs(cameras[0], width, height, in.gaussian_count, in.sh_components);
-    a.bin.tilesX = (width + kTileWidth - 1) / kTileWidth;
-    a.bin.tilesY = (height + kTileHeight - 1) / kTileHeight;
-    a.rowBegin = 0;
-    a.rowEnd = a.bin.tilesY;
-    a.rowStride = 1;
+    const ProjectArgs a = batchSharedArgs(cameras[0], width, height, in.gaussian_count, in.sh_components);
     // the host copy of the per-view terms (the cameras are consumed before the call returns), to the device
     // array in kernel-argument chunks
     viewHost_.resize(viewCount);
@@ -247,14 +272,7 @@ gsm_status GlobalRenderer::renderViews(hipStream_t s, const gsm_gaussian_input& 
         const ProjectArgs pv = frameArgs(cameras[v], width, height, in.gaussian_count, in.sh_components);
         ViewArgs& d = viewHost_[v];
         std::memset(&d, 0, sizeof(d));
-        d.cam = pv.cam;
-        d.limX = pv.limX;
-        d.limY = pv.limY;
-        d.focalX = pv.focalX;
-        d.focalY = pv.focalY;
-        d.maxEig = pv.maxEig;
-        d.adjFar = pv.adjFar;
-        d.adjDen = pv.adjDen;
+        set_view_terms(d, pv);
     }
     for (uint32_t v0 = 0; v0 < viewCount; v0 += kViewChunk) {
         ViewChunk c;
@@ -292,11 +310,10 @@ gsm_status GlobalRenderer::renderBatch(hipStream_t s, const gsm_global_view* vie
     if (items > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;  // (the values keep 30 bits of item)
     for (uint32_t v = 0; v < viewCount; ++v) {
         const gsm_global_view& V = views[v];
-        if (V.width == 0 || V.height == 0 || V.width > maxWidth_ || V.height > maxHeight_)
-            return GSM_ERR_INVALID_DIMENSIONS;
+        if (!frameSizeOk(V.width, V.height)) return GSM_ERR_INVALID_DIMENSIONS;
         allTiles += tiles_of(V.width, V.height);
     }
-    if (allTiles > tileCount_ || allTiles > 65535u) return GSM_ERR_INVALID_TILE_COUNT;
+    if (!batchTilesOk(allTiles)) return GSM_ERR_INVALID_TILE_COUNT;
     for (uint32_t v = 0; v < viewCount; ++v) {
         const gsm_global_view& V = views[v];
         if (!V.color || (V.input.gaussian_count > 0 && (!V.input.gaussians || !V.input.harmonics)))
@@ -311,7 +328,7 @@ gsm_status GlobalRenderer::renderBatch(hipStream_t s, const gsm_global_view* vie
     }
     for (uint32_t v = 1; v < viewCount; ++v)
         if (views[v].input.sh_components != views[0].input.sh_components) return GSM_ERR_INVALID_ARGUMENT;
-    if (rowBegin_ != 0 || rowEnd_ != tilesY_ || rowStride_ != 1) return GSM_ERR_UNSUPPORTED;  // (set_tile_rows)
+    if (tileRowsRestricted()) return GSM_ERR_UNSUPPORTED;  // (set_tile_rows)
     if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
     // the per-view array and the two lookup tables: allocated by the handle's first batch, for the most views
     // its tile space and its item space hold (every view takes at least one tile; the host copies are reserved
@@ -346,14 +363,7 @@ gsm_status GlobalRenderer::renderBatch(hipStream_t s, const gsm_global_view* vie
         const ProjectArgs pv = frameArgs(V.camera, V.width, V.height, n, sh);
         BatchViewArgs& d = batchHost_[v];
         std::memset(&d, 0, sizeof(d));
-        d.cam = pv.cam;
-        d.limX = pv.limX;
-        d.limY = pv.limY;
-        d.focalX = pv.focalX;
-        d.focalY = pv.focalY;
-        d.maxEig = pv.maxEig;
-        d.adjFar = pv.adjFar;
-        d.adjDen = pv.adjDen;
+        set_view_terms(d, pv);
         d.count = n;
         d.bin = pv.bin;
         d.bin.tilesX = (V.width + kTileWidth - 1) / kTileWidth;
@@ -392,12 +402,7 @@ gsm_status GlobalRenderer::renderBatch(hipStream_t s, const gsm_global_view* vie
                           s);
     }
     // what the batch shares: the thresholds, the capacity and the schedule; count = the batch's gaussians (counters)
-    ProjectArgs a = frameArgs(views[0].camera, views[0].width, views[0].height, countSum, sh);
-    a.bin.tilesX = batchHost_[0].bin.tilesX;
-    a.bin.tilesY = batchHost_[0].bin.tilesY;
-    a.rowBegin = 0;
-    a.rowEnd = a.bin.tilesY;
-    a.rowStride = 1;
+    const ProjectArgs a = batchSharedArgs(views[0].camera, views[0].width, views[0].height, countSum, sh);
     ViewFrame vf;
     vf.batchFrame.views = viewCount;
     vf.batchFrame.blocks = blockBase;

@@ -115,6 +115,14 @@ class GlobalRenderer {
     uint32_t scheduleUnits(hipStream_t s, uint32_t width, uint32_t height, uint32_t views = 0,
                            uint32_t batchTiles = 0);
     static uint32_t tiles_of(uint32_t width, uint32_t height);  // tiles of a width x height frame
+    // checks and arguments renderViews and renderBatch share: a view's size within the handle's, a batch's
+    // tiles within its tile space and the key's 16-bit field, no set_tile_rows restriction, and the
+    // ProjectArgs of what a batch shares (view 0's, on that view's own grid)
+    bool frameSizeOk(uint32_t width, uint32_t height) const;
+    bool batchTilesOk(uint64_t allTiles) const;
+    bool tileRowsRestricted() const { return rowBegin_ != 0 || rowEnd_ != tilesY_ || rowStride_ != 1; }
+    ProjectArgs batchSharedArgs(const gsm_camera_params& camera0, uint32_t width0, uint32_t height0, uint32_t count,
+                                uint32_t shComponents) const;
     PartitionBuffers part_;
     uint32_t partCount_ = 0;  // ids of the last partitionCounts
     SlabTable partSlabs_{};

@@ -419,3 +419,150 @@ def test_colour_formats_two_views(gsm, cuda, fmt):
         assert np.array_equal(bd[v], d), f"view {v} depth: " + diff(bd[v], d)
     rb.close()
     rs.close()
+
+
+# ---- 12. the entry beside the batch ----
+FW, FH, FN = 96, 48, 1000  # 3 x 3 = 9 tiles, 1024 items per view
+
+
+def front_scene(cuda):
+    from gsm_amd import scenes
+    world, harm, _ = scenes.gen_scene(FN, FW, FH, 1, 0, seed=15)
+    return Scene(cuda, world, harm, 1)
+
+
+def strided_targets(torch, k, cs, ds):
+    return (torch.full((k * cs,), 0xA5, dtype=torch.uint8, device="cuda"),
+            torch.full((k * ds,), 0xA5, dtype=torch.uint8, device="cuda"))
+
+
+def view_bytes(buf, v, stride, rows, pitch):
+    return buf[v * stride: v * stride + rows * pitch].reshape(rows, pitch)
+
+
+def check_strided(buf, stride, pitch, want, what):
+    """Every view's rows equal its single frame; every byte between and after the views is still 0xA5."""
+    buf = buf.cpu().numpy()
+    for v, w in enumerate(want):
+        got = view_bytes(buf, v, stride, FH, pitch)
+        assert np.array_equal(got, w), f"view {v} {what}: " + diff(got, w)
+        assert (buf[v * stride + FH * pitch: (v + 1) * stride] == 0xA5).all(), f"{what} gap after view {v} written"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_depth", [True, False])
+def test_view_strides_that_misalign_later_views(gsm, cuda, with_depth):
+    """Three views whose strides leave view 1's colour target 8 bytes off a 16-byte boundary and views 1 and 2's
+    depth targets 2 and 4 bytes off an 8-byte one: the wide stores must not be taken where a view's target is
+    not aligned for them, and the bytes are the single frame's whichever stores are taken."""
+    from gsm_amd import scenes
+    torch = cuda
+    sc = front_scene(torch)
+    cams = orbit(scenes, FW, FH, (0.0, 8.0, -8.0))
+    cp, dp = FW * 8, FW * 2
+    cs, ds = FH * cp + 8, FH * dp + 2
+    rb, rs = batch_handle(gsm, sc, 3, FW, FH), single_handle(gsm, sc, FW, FH)
+    color, depth = strided_targets(torch, 3, cs, ds)
+    rb.render_views(color, depth if with_depth else None, sc.input(gsm), [gsm.CameraParams.from_dict(c) for c in cams],
+                    FW, FH, color_view_stride=cs, depth_view_stride=ds)
+    torch.cuda.synchronize()
+    singles = [render_single(gsm, torch, rs, sc, c, FW, FH) for c in cams]
+    check_strided(color, cs, cp, [s[0] for s in singles], "colour")
+    if with_depth:
+        check_strided(depth, ds, dp, [s[1] for s in singles], "depth")
+    else:
+        assert (depth == 0xA5).all(), "a batch without a depth target wrote depth"
+    rb.close()
+    rs.close()
+
+
+@pytest.mark.gpu
+def test_views_and_batch_share_a_schedule_harmlessly(gsm, cuda):
+    """render_views, render_batch of the same three views, render_views with other cameras, then one single
+    frame, all on one handle: whatever walk costs a frame finds, the order never changes an image."""
+    from gsm_amd import scenes
+    torch = cuda
+    sc = front_scene(torch)
+    cams_a = orbit(scenes, FW, FH, (0.0, 8.0, -8.0))
+    cams_b = orbit(scenes, FW, FH, (3.0, -11.0, 5.0))
+    cp, dp = FW * 8, FW * 2
+    cs, ds = FH * cp + 16, FH * dp + 8
+    r, rs = batch_handle(gsm, sc, 3, FW, FH), single_handle(gsm, sc, FW, FH)
+    want = {id(c): render_single(gsm, torch, rs, sc, c, FW, FH) for c in cams_a + cams_b}
+
+    def check(color, depth, cams):
+        check_strided(color, cs, cp, [want[id(c)][0] for c in cams], "colour")
+        check_strided(depth, ds, dp, [want[id(c)][1] for c in cams], "depth")
+
+    c1, d1 = strided_targets(torch, 3, cs, ds)
+    r.render_views(c1, d1, sc.input(gsm), [gsm.CameraParams.from_dict(c) for c in cams_a], FW, FH,
+                   color_view_stride=cs, depth_view_stride=ds)
+    c2, d2 = strided_targets(torch, 3, cs, ds)
+    r.render_batch([gsm.BatchView(sc.input(gsm), gsm.CameraParams.from_dict(c), FW, FH, c2[v * cs:], d2[v * ds:])
+                    for v, c in enumerate(cams_a)])
+    c3, d3 = strided_targets(torch, 3, cs, ds)
+    r.render_views(c3, d3, sc.input(gsm), [gsm.CameraParams.from_dict(c) for c in cams_b], FW, FH,
+                   color_view_stride=cs, depth_view_stride=ds)
+    c4, d4, _ = render_single(gsm, torch, r, sc, cams_b[1], FW, FH)
+    torch.cuda.synchronize()
+    check(c1, d1, cams_a)
+    check(c2, d2, cams_a)
+    check(c3, d3, cams_b)
+    assert torch.equal(c1, c2) and torch.equal(d1, d2), "render_views and render_batch of the same views differ"
+    assert np.array_equal(c4, want[id(cams_b[1])][0]) and np.array_equal(d4, want[id(cams_b[1])][1])
+    r.close()
+    rs.close()
+
+
+@pytest.mark.gpu
+def test_counters_after_views_keep_their_meaning(gsm, cuda):
+    from gsm_amd import scenes
+    torch = cuda
+    sc = front_scene(torch)
+    cams = orbit(scenes, FW, FH, (0.0, 8.0, -8.0))
+    rb, rs = batch_handle(gsm, sc, 3, FW, FH), single_handle(gsm, sc, FW, FH)
+    render_batch(gsm, torch, rb, sc, cams, FW, FH)
+    c = rb.counters()
+    assert c["gaussian_count"] == FN, "the scene's count, not the batch's items"
+    assert c["overflow"] == 0
+    assert c["total_assignments"] == sum(render_single(gsm, torch, rs, sc, cam, FW, FH)[2] for cam in cams) > 0
+    rb.close()
+    rs.close()
+
+
+@pytest.mark.gpu
+def test_captured_views_frame_replays_its_own_cameras(gsm, cuda):
+    """The per-view entries travel as kernel arguments: a frame captured into a graph replays the cameras it was
+    captured with, whatever became of the caller's list and whatever the handle rendered since."""
+    from gsm_amd import scenes
+    torch = cuda
+    sc = front_scene(torch)
+    cams = orbit(scenes, FW, FH, (0.0, 8.0))
+    other = orbit(scenes, FW, FH, (-20.0, 25.0))
+    rb, rs = batch_handle(gsm, sc, 2, FW, FH), single_handle(gsm, sc, FW, FH)
+    want = [render_single(gsm, torch, rs, sc, c, FW, FH) for c in cams]
+    color, depth = targets(torch, 2, FW, FH)
+    scratch_c, scratch_d = targets(torch, 2, FW, FH)
+    cps = [gsm.CameraParams.from_dict(c) for c in cams]
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):  # (the handle's first batch allocates: not under capture)
+        rb.render_views(scratch_c, scratch_d, sc.input(gsm), cps, FW, FH, stream=s)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        rb.render_views(color, depth, sc.input(gsm), cps, FW, FH, stream=s)
+    torch.cuda.synchronize()
+    cps[:] = [gsm.CameraParams.from_dict(c) for c in other]
+    rb.render_views(scratch_c, scratch_d, sc.input(gsm), cps, FW, FH)
+    torch.cuda.synchronize()
+    color.fill_(0xA5)
+    depth.fill_(0xA5)
+    g.replay()
+    torch.cuda.synchronize()
+    bc, bd = color.cpu().numpy(), depth.cpu().numpy()
+    for v in range(2):
+        assert np.array_equal(bc[v], want[v][0]), f"view {v} colour: " + diff(bc[v], want[v][0])
+        assert np.array_equal(bd[v], want[v][1]), f"view {v} depth: " + diff(bd[v], want[v][1])
+    del g
+    rb.close()
+    rs.close()

@@ -17,9 +17,11 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gsm-renderer_amd"))
 
-CASES = [  # (name, gaussians, sh components, width, height, precision, view counts)
-    ("50k_sh0_640x360_f32", 50_000, 1, 640, 360, 0, (2, 4, 8)),
-    ("1m_sh3_640x360_f16", 1_000_000, 16, 640, 360, 1, (2, 4)),
+CASES = [  # (name, gaussians, sh components, width, height, precision, view counts, blend kernel to expect or None)
+    ("50k_sh0_640x360_f32", 50_000, 1, 640, 360, 0, (2, 4, 8), None),
+    ("1m_sh3_640x360_f16", 1_000_000, 16, 640, 360, 1, (2, 4), None),
+    # 27 x 460 tiles: the batch takes the pair walk (blend_kernel_kind() 3), which no other workload reaches
+    ("20k_sh0_640x360_f32", 20_000, 1, 640, 360, 0, (27,), 3),
 ]
 
 
@@ -35,7 +37,7 @@ def main():
     from gsm_amd import scenes
 
     results = []
-    for name, n, sh, w, h, prec, ks in CASES:
+    for name, n, sh, w, h, prec, ks, kind in CASES:
         world_np, harm_np, _ = scenes.gen_scene(n, w, h, sh, prec, seed=42)
         world = torch.from_numpy(world_np.view(np.uint8).reshape(-1).copy()).cuda()
         harm = torch.from_numpy(harm_np.view(np.uint8).reshape(-1).copy()).cuda()
@@ -71,6 +73,8 @@ def main():
                 seq()
                 views()
             torch.cuda.synchronize()
+            if kind is not None and batch.blend_kernel_kind() != kind:
+                raise SystemExit(f"{name} x{k}: blend kernel {batch.blend_kernel_kind()}, expected {kind}")
             ta, tb = [], []
             for _ in range(args.blocks):
                 ta.append(block(seq))
