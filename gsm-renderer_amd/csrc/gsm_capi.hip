@@ -95,6 +95,14 @@ gsm_status gsm_global_render_batch(gsm_renderer* r, void* stream, const gsm_glob
     return r->impl->renderBatch((hipStream_t)stream, views, view_count);
 }
 
+gsm_status gsm_global_render_composite(gsm_renderer* r, void* stream, const gsm_global_object* objects,
+                                       uint32_t object_count, uint32_t width, uint32_t height, void* color,
+                                       size_t color_pitch, void* depth, size_t depth_pitch) {
+    if (!r || !r->impl) return GSM_ERR_INVALID_ARGUMENT;
+    return r->impl->renderComposite((hipStream_t)stream, objects, object_count, width, height, color, color_pitch,
+                                    depth, depth_pitch);
+}
+
 gsm_status gsm_global_project_partition(gsm_renderer* r, void* stream, const gsm_gaussian_input* input,
                                         const gsm_camera_params* camera, uint32_t width, uint32_t height,
                                         uint32_t first, uint32_t count, const uint32_t* slab_rows,

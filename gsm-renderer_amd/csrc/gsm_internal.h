@@ -94,6 +94,34 @@ struct BatchFrame {
     const uint16_t* tileView = nullptr;    // device, [tiles]: the view of every tile
 };
 
+// Several posed objects in one frame (gsm_global_render_composite): what differs per object --
+// its camera and the terms projection_uniforms derives from it, its scene and count, and its first block.  The
+// tile grid and the target are the frame's (ProjectArgs, as for the single frame), so the entry holds neither.
+// Object o's items start at 256 * blockBase; an object without gaussians owns no block and no entry.  A
+// projection or scatter block finds its entry in a per-block table: one uniform 2-byte load, then scalar loads.
+struct ComposeObjectArgs {
+    CameraUniforms cam;
+    float limX, limY, focalX, focalY, maxEig, adjFar, adjDen;
+    uint32_t count;  // gaussians of this object's scene
+    const void* world;
+    const void* harm;
+    uint32_t blockBase, pad[3];
+};
+static_assert(sizeof(ComposeObjectArgs) == 272 && sizeof(ComposeObjectArgs) < sizeof(BatchViewArgs),
+              "ComposeObjectArgs: 17 16-B words");
+// the array is filled by kernel arguments, kComposeChunk entries per launch (a kernel argument block holds 4 KiB)
+constexpr uint32_t kComposeChunk = 14;
+struct ComposeChunk {
+    ComposeObjectArgs v[kComposeChunk];
+};
+struct ComposeFrame {
+    uint32_t objects = 0;  // objects of the call (> 0: the frame is a composite), empty ones included
+    uint32_t entries = 0;  // objects with gaussians: entries of args
+    uint32_t blocks = 0;   // projection / scatter blocks: sum of ceil(count_o / 256)
+    const ComposeObjectArgs* args = nullptr;   // device, [entries]
+    const uint16_t* blockObject = nullptr;     // device, [blocks]: the entry of every block
+};
+
 // Multi-GPU partition: tile-row boundaries of the slabs, and the 48-byte
 // record a slab owner receives per gaussian (GaussianRenderData + blend record + tile rect).
 constexpr uint32_t kMaxSlabs = 16;
@@ -271,6 +299,8 @@ struct DeviceArena {
     BatchViewArgs* batchArgs = nullptr;        // [maxBatchViews] per-view entries (render_batch; lazily)
     uint16_t* batchBlockView = nullptr;        // [ceil(maxG / 256)] the view of every projection block of a batch
     uint16_t* batchTileView = nullptr;         // [tileCount] the view of every tile of a batch
+    ComposeObjectArgs* composeArgs = nullptr;  // [min(ceil(maxG / 256), 65535)] per-object entries (render_composite; lazily)
+    uint16_t* composeBlockObject = nullptr;    // [ceil(maxG / 256)] the entry of every projection block of a composite
     uint16_t* expTable = nullptr;              // [65536]
     float2* sincosTable = nullptr;             // [kSincosEntries + 256]: sin/cos, then the byte table (det_byte_lut_entry)
 };
@@ -344,6 +374,15 @@ void launch_project_batch(bool halfInput, uint32_t shDegree, const ProjectArgs& 
                           const DeviceArena& A, hipStream_t stream);
 void launch_fill_batch(const BatchChunk& chunk, uint32_t first, uint32_t n, BatchViewArgs* dst, uint16_t* blockView,
                        uint32_t maxBlocks, uint16_t* tileView, uint32_t maxTiles, hipStream_t stream);
+// several posed objects on the frame's own tile grid (k_project_compose): every block's scene,
+// count and camera terms come from its object's entry; `args` holds the frame's (the grid, the rows, the
+// thresholds, the capacity, the schedule).  launch_fill_compose writes entries [first, first + n) of the device
+// array from `chunk` (n <= kComposeChunk) and those objects' ranges of the block table (at most maxBlocks
+// entries of it are written, whatever the entries say).
+void launch_project_compose(bool halfInput, uint32_t shDegree, const ProjectArgs& args, const ComposeFrame& cf,
+                            const DeviceArena& A, hipStream_t stream);
+void launch_fill_compose(const ComposeChunk& chunk, uint32_t first, uint32_t n, ComposeObjectArgs* dst,
+                         uint16_t* blockObject, uint32_t maxBlocks, hipStream_t stream);
 // exclusive scan of the per-block sums, total + clamp into the header (GlobalShaders.metal:685-712)
 // project gaussians [0, a.count) of world/harm (already offset to the rank's range) and pack
 // the records of each slab's gaussians into `send` (slab-major, ascending id), counts to sendCounts
@@ -376,9 +415,10 @@ void launch_scan_sums(uint32_t* sums, uint32_t nb, uint32_t cap, TileAssignmentH
 // workgroup adds up the counts before its own, workgroup 0 also the total (header, blend queue)
 // views (nullable): a batch's items (k_scatter_views): tile ids v * tilesPerView + local tile
 // batch (nullable): a batch of different views (k_scatter_batch): tile ids tileBase of the view + local tile
+// compose (nullable): a composite's items (k_scatter_compose): the frame's own tile ids
 void launch_scatter(const ProjectArgs& args, const DeviceArena& A, hipStream_t stream,
                     const uint32_t* devCount = nullptr, bool fusedScan = false, const ViewBatch* views = nullptr,
-                    const BatchFrame* batch = nullptr);
+                    const BatchFrame* batch = nullptr, const ComposeFrame* compose = nullptr);
 // the blend's half-tile lists from the sorted values (skip flags, k_scatter), tiles [tileBegin, +numTiles)
 void launch_half_lists(const uint32_t* sortedVals, uint32_t tileBegin, uint32_t numTiles, const DeviceArena& A,
                        uint32_t tileCount, hipStream_t stream);

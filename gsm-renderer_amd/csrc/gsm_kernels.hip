@@ -307,6 +307,9 @@ __device__ __forceinline__ float2 band_of(const BlendRecordA& ra, short4 r, cons
 #define GSM_VIEWS 2
 #include "gsm_project_body.h"
 #undef GSM_VIEWS
+#define GSM_VIEWS 3
+#include "gsm_project_body.h"
+#undef GSM_VIEWS
 
 // entries [first, first + n) of the per-view array from a kernel argument (plain vector stores): the host's
 // copy of the cameras is consumed when the frame is enqueued, so the call needs no staging buffer that a
@@ -337,6 +340,24 @@ __global__ __launch_bounds__(256) void k_fill_batch(BatchChunk chunk, uint32_t f
         const uint32_t t0 = min(V.tg.tileBase, maxTiles);
         const uint32_t t1 = min(V.tg.tileBase + V.tg.tilesX * V.tg.tilesY, maxTiles);
         for (uint32_t i = t0 + threadIdx.x; i < t1; i += 256u) tileView[i] = view;
+    }
+}
+
+// The same for a composite (gsm_global_render_composite): entries [first, first + n) of the
+// per-object array, and those objects' ranges of the block table -- entry e owns blocks [blockBase, + ceil(count
+// / 256)) of blockObject.  No tile table: the objects share the frame's tiles.
+__global__ __launch_bounds__(256) void k_fill_compose(ComposeChunk chunk, uint32_t first, uint32_t n,
+                                                      ComposeObjectArgs* __restrict__ dst,
+                                                      uint16_t* __restrict__ blockObject, uint32_t maxBlocks) {
+    constexpr uint32_t kWords = sizeof(ComposeObjectArgs) / 4u;
+    const uint32_t* src = (const uint32_t*)&chunk;
+    for (uint32_t i = threadIdx.x; i < n * kWords; i += 256u) ((uint32_t*)(dst + first))[i] = src[i];
+    for (uint32_t k = 0; k < n; ++k) {
+        const ComposeObjectArgs& V = chunk.v[k];
+        const uint16_t entry = (uint16_t)(first + k);
+        const uint32_t b0 = min(V.blockBase, maxBlocks);
+        const uint32_t b1 = min(V.blockBase + (V.count + kProjectBlock - 1u) / kProjectBlock, maxBlocks);
+        for (uint32_t i = b0 + threadIdx.x; i < b1; i += 256u) blockObject[i] = entry;
     }
 }
 
@@ -1028,6 +1049,9 @@ __device__ __forceinline__ uint64_t block_sum_prefix(const uint32_t* __restrict_
 #define GSM_VIEWS 2
 #include "gsm_scatter_body.h"
 #undef GSM_VIEWS
+#define GSM_VIEWS 3
+#include "gsm_scatter_body.h"
+#undef GSM_VIEWS
 
 __global__ __launch_bounds__(256) void k_tile_starts(const uint32_t* __restrict__ sortedKeys,
                                                      const TileAssignmentHeader* __restrict__ hdr,
@@ -1218,6 +1242,36 @@ void launch_fill_batch(const BatchChunk& chunk, uint32_t first, uint32_t n, Batc
 }
 
 template <bool HALF>
+static void launch_project_compose_t(uint32_t deg, const ProjectArgs& a, const ComposeFrame& cf, const DeviceArena& A,
+                                     hipStream_t s) {
+    if (cf.blocks == 0 && a.schedUnits == 0) return;  // (an empty composite still orders its blend units)
+#define GSM_LAUNCH_PROJC(D)                                                                                            \
+    hipLaunchKernelGGL((k_project_compose<HALF, D>), dim3(cf.blocks + (a.schedUnits ? 1u : 0u)), dim3(kProjectBlock), \
+                       0, s, a, cf.args, cf.blockObject, A.renderData, A.bounds, A.rec, A.tileCounts, A.tileMasks,     \
+                       A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax)
+    switch (deg) {
+        case 0: GSM_LAUNCH_PROJC(0); break;
+        case 1: GSM_LAUNCH_PROJC(1); break;
+        case 2: GSM_LAUNCH_PROJC(2); break;
+        default: GSM_LAUNCH_PROJC(3); break;
+    }
+#undef GSM_LAUNCH_PROJC
+}
+
+void launch_project_compose(bool halfInput, uint32_t deg, const ProjectArgs& a, const ComposeFrame& cf,
+                            const DeviceArena& A, hipStream_t s) {
+    if (halfInput) launch_project_compose_t<true>(deg, a, cf, A, s);
+    else launch_project_compose_t<false>(deg, a, cf, A, s);
+}
+
+void launch_fill_compose(const ComposeChunk& chunk, uint32_t first, uint32_t n, ComposeObjectArgs* dst,
+                         uint16_t* blockObject, uint32_t maxBlocks, hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_fill_compose, dim3(1), dim3(256), 0, s, chunk, first, n > kComposeChunk ? kComposeChunk : n,
+                       dst, blockObject, maxBlocks);
+}
+
+template <bool HALF>
 static void launch_project_part_t(uint32_t deg, const void* world, const void* harm, const ProjectArgs& a,
                                   const SlabTable& slabs, const PartitionBuffers& B, const float2* sincos,
                                   const DeviceArena* A, hipStream_t s) {
@@ -1311,7 +1365,14 @@ void launch_scan_blocks(uint32_t nb, const ProjectArgs& a, const DeviceArena& A,
 }
 
 void launch_scatter(const ProjectArgs& a, const DeviceArena& A, hipStream_t s, const uint32_t* devCount,
-                    bool fusedScan, const ViewBatch* vb, const BatchFrame* bf) {
+                    bool fusedScan, const ViewBatch* vb, const BatchFrame* bf, const ComposeFrame* cf) {
+    if (cf) {
+        if (cf->blocks == 0) return;
+        hipLaunchKernelGGL(k_scatter_compose, dim3(cf->blocks), dim3(kProjectBlock), 0, s, a, cf->args,
+                           cf->blockObject, A.renderData, A.bounds, A.tileCounts, A.tileMasks, A.blockSums, A.keys[0],
+                           A.vals[0], A.sincosTable, A.rec, fusedScan ? 1u : 0u, A.header, A.tileQueue);
+        return;
+    }
     if (bf) {
         if (bf->blocks == 0) return;
         hipLaunchKernelGGL(k_scatter_batch, dim3(bf->blocks), dim3(kProjectBlock), 0, s, a, bf->args, bf->blockView,

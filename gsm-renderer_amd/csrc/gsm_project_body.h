@@ -1,8 +1,25 @@
-// gsm_project_body.h -- the text of k_project, compiled three times by gsm_kernels.hip: as the single frame's
+// gsm_project_body.h -- the text of k_project, compiled four times by gsm_kernels.hip: as the single frame's
 // kernel (GSM_VIEWS 0: k_project, exactly the kernel it was before batches of views existed; an item is its
-// gaussian id), as the projection of a batch of views of one scene (GSM_VIEWS 1: k_project_views) and as the
-// projection of a batch of views of different scenes and sizes (GSM_VIEWS 2: k_project_batch).  No include guard.
-#if GSM_VIEWS == 2
+// gaussian id), as the projection of a batch of views of one scene (GSM_VIEWS 1: k_project_views), as the
+// projection of a batch of views of different scenes and sizes (GSM_VIEWS 2: k_project_batch) and as the
+// projection of several posed objects into one frame (GSM_VIEWS 3: k_project_compose).  No include guard.
+#if GSM_VIEWS == 3
+// The projection of a composite (gsm_global_render_composite): block b belongs to the object of
+// entry blockObject[b] -- uniform per block, one 2-byte load -- and projects gaussians [(b - blockBase) * 256,
+// + 256) of that object's scene under that object's camera onto the frame's own tile grid.  The scene, the count
+// and the camera terms come from the entry (ComposeObjectArgs) by scalar loads; the grid, the rows and the
+// thresholds stay P's, as the single frame's.  The per-gaussian arrays are written at the block's items, b * 256
+// + thread; the tile tests and counts are those of k_project for that scene and camera.
+template <bool HALF, int DEG>
+__global__ __launch_bounds__(kProjectBlock) void k_project_compose(
+    ProjectArgs P, const ComposeObjectArgs* __restrict__ objects, const uint16_t* __restrict__ blockObject,
+    GaussianRenderData* __restrict__ outRD, short4* __restrict__ outBounds, BlendRecord* __restrict__ outRec,
+    uint32_t* __restrict__ counts, uint32_t* __restrict__ masks, uint32_t* __restrict__ blockSums,
+    const float2* __restrict__ sincos, const uint16_t* __restrict__ unitCost, uint32_t* __restrict__ unitOrder,
+    uint32_t* __restrict__ costMax) {
+    const void* __restrict__ world = nullptr;  // the block's scene: its object's (below)
+    const void* __restrict__ harm = nullptr;
+#elif GSM_VIEWS == 2
 // The projection of a batch of different views (gsm_global_render_batch): block b belongs to view
 // blockView[b] -- uniform per block, one 2-byte load -- and projects gaussians [(b - blockBase) * 256, + 256) of
 // that view's scene under its camera onto its own tile grid; everything the view owns comes from its entry of
@@ -52,7 +69,25 @@ __global__ __launch_bounds__(kProjectBlock) void k_project(
         }
     }
     const uint32_t blk = blockIdx.x - (P.schedUnits ? 1u : 0u);
-#if GSM_VIEWS == 2
+#if GSM_VIEWS == 3
+    // the block's object (uniform: scalar loads) and its first gaussian; items are written at blk * 256 + thread
+    uint32_t gblk;
+    {
+        const ComposeObjectArgs& V = objects[__builtin_amdgcn_readfirstlane((uint32_t)blockObject[blk])];
+        gblk = blk - V.blockBase;
+        world = V.world;
+        harm = V.harm;
+        P.cam = V.cam;
+        P.count = V.count;
+        P.limX = V.limX;
+        P.limY = V.limY;
+        P.focalX = V.focalX;
+        P.focalY = V.focalY;
+        P.maxEig = V.maxEig;
+        P.adjFar = V.adjFar;
+        P.adjDen = V.adjDen;
+    }
+#elif GSM_VIEWS == 2
     // the block's view (uniform: scalar loads) and its first gaussian; items are written at blk * 256 + thread
     uint32_t gblk;
     {

@@ -418,6 +418,105 @@ gsm_status GlobalRenderer::renderBatch(hipStream_t s, const gsm_global_view* vie
                     nullptr, false, nullptr, &vf);
 }
 
+gsm_status GlobalRenderer::renderComposite(hipStream_t s, const gsm_global_object* objects, uint32_t objectCount,
+                                           uint32_t width, uint32_t height, void* color, size_t colorPitch,
+                                           void* depth, size_t depthPitch) {
+    // Every check before anything is enqueued, one kind of check after another over all objects (the first
+    // failing kind decides, within it the lowest object): counts, dimensions, missing buffers, sizes,
+    // sh_components, tile rows.  (The counts of a NULL array cannot be read: that is the missing buffer.)
+    if (objectCount == 0) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
+    if (!objects) return GSM_ERR_MISSING_REQUIRED_BUFFER;
+    if (objectCount > 65535u) return GSM_ERR_INVALID_GAUSSIAN_COUNT;  // (a block's entry is a 16-bit index)
+    uint64_t items = 0;
+    uint32_t countSum = 0, entries = 0;
+    for (uint32_t o = 0; o < objectCount; ++o) {
+        const uint32_t n = objects[o].input.gaussian_count;
+        if (n > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
+        items += ((uint64_t)n + kProjectBlock - 1) / kProjectBlock * kProjectBlock;
+        entries += n ? 1u : 0u;
+    }
+    if (items > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;  // (the values keep 30 bits of item)
+    if (!frameSizeOk(width, height)) return GSM_ERR_INVALID_DIMENSIONS;
+    if (!color) return GSM_ERR_MISSING_REQUIRED_BUFFER;
+    for (uint32_t o = 0; o < objectCount; ++o) {
+        const gsm_gaussian_input& in = objects[o].input;
+        if (in.gaussian_count > 0 && (!in.gaussians || !in.harmonics)) return GSM_ERR_MISSING_REQUIRED_BUFFER;
+        countSum += in.gaussian_count;  // (<= items <= max_gaussians)
+    }
+    // (everything above passed: what is left of validate_frame is the pitches and the alignment)
+    gsm_status st = validate_frame(config_, maxGaussians_, maxWidth_, maxHeight_, countSum, true, false, width, height,
+                                   color, colorPitch, 1, depth, depthPitch);
+    if (st != GSM_OK) return st;
+    for (uint32_t o = 1; o < objectCount; ++o)
+        if (objects[o].input.sh_components != objects[0].input.sh_components) return GSM_ERR_INVALID_ARGUMENT;
+    if (tileRowsRestricted()) return GSM_ERR_UNSUPPORTED;  // (set_tile_rows)
+    if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
+    // the per-object array and the block table: allocated by the handle's first composite, for the most objects
+    // with gaussians its item space holds (each takes at least one block; the host copies are reserved with
+    // them, so no later composite allocates)
+    const uint32_t maxBlocks = (uint32_t)(((uint64_t)maxGaussians_ + kProjectBlock - 1) / kProjectBlock);
+    const uint32_t maxEntries = std::min(maxBlocks, 65535u);
+    if (!arena_.composeArgs) {
+        ComposeObjectArgs* args = nullptr;
+        uint16_t* bo = nullptr;
+        st = allocs_.alloc((void**)&args, (size_t)maxEntries * sizeof(ComposeObjectArgs));
+        if (st == GSM_OK) st = allocs_.alloc((void**)&bo, (size_t)maxBlocks * sizeof(uint16_t));
+        if (st != GSM_OK) return st;
+        composeHost_.reserve(maxEntries);
+        composeSig_.reserve(2 + 65535u);
+        schedComposeSig_.reserve(2 + 65535u);
+        arena_.composeArgs = args;
+        arena_.composeBlockObject = bo;
+    }
+    (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's)
+    // the host copy of the entries (`objects` is consumed before the call returns): each object's own frameArgs
+    // -- its camera on the frame's size -- for the objects that have gaussians; the signature takes every object
+    const uint32_t sh = objects[0].input.sh_components;
+    composeHost_.clear();
+    composeSig_.clear();
+    composeSig_.push_back(width);
+    composeSig_.push_back(height);
+    uint32_t blockBase = 0;
+    for (uint32_t o = 0; o < objectCount; ++o) {
+        const gsm_global_object& O = objects[o];
+        const uint32_t n = O.input.gaussian_count;
+        composeSig_.push_back(n);
+        if (n == 0) continue;  // (no block, no entry)
+        const ProjectArgs po = frameArgs(O.camera, width, height, n, sh);
+        ComposeObjectArgs d;
+        std::memset(&d, 0, sizeof(d));
+        set_view_terms(d, po);
+        d.count = n;
+        d.world = O.input.gaussians;
+        d.harm = O.input.harmonics;
+        d.blockBase = blockBase;
+        composeHost_.push_back(d);
+        blockBase += (n + kProjectBlock - 1) / kProjectBlock;
+    }
+    for (uint32_t e0 = 0; e0 < entries; e0 += kComposeChunk) {
+        ComposeChunk c;
+        const uint32_t n = std::min(kComposeChunk, entries - e0);
+        std::memset(&c, 0, sizeof(c));
+        std::memcpy(c.v, composeHost_.data() + e0, (size_t)n * sizeof(ComposeObjectArgs));
+        launch_fill_compose(c, e0, n, arena_.composeArgs, arena_.composeBlockObject, maxBlocks, s);
+    }
+    // the frame's arguments are the single frame's: the handle's tile grid and rows, the thresholds, the capacity
+    // and the schedule; count = the composite's gaussians (counters).  (Not batchSharedArgs: that puts a batch on
+    // view 0's own grid, and a composite stays on the handle's, as gsm_global_render does.)
+    const ProjectArgs a = frameArgs(objects[0].camera, width, height, countSum, sh);
+    ViewFrame vf;
+    vf.compose.objects = objectCount;
+    vf.compose.entries = entries;
+    vf.compose.blocks = blockBase;
+    vf.compose.args = arena_.composeArgs;
+    vf.compose.blockObject = arena_.composeBlockObject;
+    const uint32_t deg = sh_degree(sh);
+    const bool half = config_.precision == GSM_PRECISION_FLOAT16;
+    return runFrame(s, a, width, height, color, colorPitch, depth, depthPitch,
+                    [&](const ProjectArgs& pa) { launch_project_compose(half, deg, pa, vf.compose, arena_, s); },
+                    nullptr, false, nullptr, &vf);
+}
+
 gsm_status GlobalRenderer::renderRecords(hipStream_t s, const void* records, uint32_t count, uint32_t width,
                                          uint32_t height, void* color, size_t colorPitch, void* depth,
                                          size_t depthPitch, const uint32_t* devCount, bool preOrdered,
@@ -553,18 +652,23 @@ gsm_status GlobalRenderer::partitionPush(hipStream_t s, uint32_t world, uint32_t
 }
 
 uint32_t GlobalRenderer::scheduleUnits(hipStream_t s, uint32_t width, uint32_t height, uint32_t views,
-                                       uint32_t batchTiles) {
+                                       uint32_t batchTiles, bool compose) {
     // (a batch of views: the units of views * tiles(width, height) tiles; the view count is part of the key, so
     // a batch neither inherits nor leaves behind a single frame's costs.  A batch of different views: the units
     // of its batchTiles tiles, keyed by its whole signature batchSig_, compared word for word)
     const uint32_t tiles = batchTiles ? batchTiles : views ? views * tiles_of(width, height) : rowCount() * tilesX_;
     const uint32_t upt = blend_units_per_tile(tiles, dev_.numCUs);
     const uint32_t units = tiles * upt;
-    const uint64_t key = batchTiles ? ~0ull
+    // (a composite: the single frame's units, keyed by its whole signature composeSig_, so it neither inherits
+    // walk costs from a render / render_views / render_batch of the handle nor leaves any to one)
+    const uint64_t key = compose ? ~1ull : batchTiles ? ~0ull
                                     : ((uint64_t)upt << 60) ^ ((uint64_t)width << 40) ^ ((uint64_t)height << 20) ^
                                           ((uint64_t)rowStride_ << 30) ^ ((uint64_t)rowBegin_ << 10) ^ rowEnd_;
     const bool isBatch = batchTiles != 0;
-    bool changed = isBatch != schedBatch_ || key != schedKey_ || views != schedViews_;
+    bool changed = isBatch != schedBatch_ || compose != schedCompose_ || key != schedKey_ || views != schedViews_;
+    if (compose && !changed) changed = composeSig_ != schedComposeSig_;
+    if (compose && changed) schedComposeSig_.assign(composeSig_.begin(), composeSig_.end());  // (reserved: no allocation)
+    schedCompose_ = compose;
     if (isBatch && !changed) changed = batchSig_ != schedBatchSig_;
     if (isBatch && changed) schedBatchSig_.assign(batchSig_.begin(), batchSig_.end());  // (reserved: no allocation)
     schedBatch_ = isBatch;
@@ -593,7 +697,10 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     const bool capture = (profiling & (2 | 16)) != 0;
     // (a batch of views: a.count gaussians per view, every view's items padded to whole blocks)
     const BatchFrame* batch = views && views->batchFrame.views ? &views->batchFrame : nullptr;
-    const uint32_t nb = batch ? batch->blocks
+    // (a composite: the objects' items padded to whole blocks, everything from the scan on the single frame's)
+    const ComposeFrame* comp = views && views->compose.objects ? &views->compose : nullptr;
+    if (comp) views = nullptr;
+    const uint32_t nb = comp ? comp->blocks : batch ? batch->blocks
                         : views ? views->batch.views * views->batch.blocksPerView
                                 : (a.count + kProjectBlock - 1) / kProjectBlock;
     // GaussianRenderData for readback only when profiling (bits 0, 1), gsm_debug.h
@@ -601,6 +708,7 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     fa.keepRenderData = capture ? 1u : 0u;
     keptRenderData_ = fa.keepRenderData != 0;
     lastCount_ = a.count;
+    lastItems_ = comp ? comp->blocks * (uint32_t)kProjectBlock : a.count;
     lastWidth_ = width;
     lastHeight_ = height;
     // Blend schedule: the units ordered by the walk lengths the previous frame of the same
@@ -610,7 +718,7 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     // the multi-GPU frame orders them earlier, in its partition projection: preOrdered).
     const uint32_t units = preOrdered ? 0u
                                       : scheduleUnits(s, width, height, batch ? batch->views : views ? views->batch.views : 0u,
-                                                      batch ? batch->tiles : 0u);
+                                                      batch ? batch->tiles : 0u, comp != nullptr);
     const bool costOrder = preOrdered ? tuning_.costOrder : units > 0;
     fa.schedUnits = units;
     // (written on every scheduled frame: the blend's remaining-walk priorities read the longest walk too)
@@ -627,7 +735,7 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     const bool fusedScan = tuning_.fusedScan && nb > 0 && nb <= (devCount ? 4u : 1u) * kFusedScanMaxBlocks;
     if (!fusedScan) launch_scan_blocks(nb, a, arena_, s, devCount);
     timer_.record(2, s);
-    launch_scatter(a, arena_, s, devCount, fusedScan, views && !batch ? &views->batch : nullptr, batch);
+    launch_scatter(a, arena_, s, devCount, fusedScan, views && !batch ? &views->batch : nullptr, batch, comp);
     if (keep) {  // preserve the unsorted assignment arrays for readback
         hipMemcpyAsync(arena_.keysKeep, arena_.keys[0], (size_t)maxAssignments_ * 4, hipMemcpyDeviceToDevice, s);
         hipMemcpyAsync(arena_.valsKeep, arena_.vals[0], (size_t)maxAssignments_ * 4, hipMemcpyDeviceToDevice, s);
@@ -733,7 +841,8 @@ gsm_status GlobalRenderer::debugCopy(int which, void* dst, size_t bytes, size_t*
     gsm_debug_counters c;
     gsm_status st = counters(&c);
     if (st != GSM_OK) return st;
-    const size_t n = lastCount_, tot = c.total_assignments;
+    // (the per-gaussian arrays are indexed by item: after a composite, 256 per block of every object)
+    const size_t n = lastItems_, tot = c.total_assignments;
     const void* src = nullptr;
     size_t full = 0;
     switch (which) {

@@ -31,6 +31,12 @@ class GlobalRenderer {
     // views of different scenes and sizes in one frame (gsm_global_render_batch)
     gsm_status renderBatch(hipStream_t stream, const gsm_global_view* views, uint32_t viewCount);
 
+    // several posed objects in one frame over one tile space and one target (gsm_global_render_composite,
+    // DESIGN.md 19)
+    gsm_status renderComposite(hipStream_t stream, const gsm_global_object* objects, uint32_t objectCount,
+                               uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
+                               size_t depthPitch);
+
     // multi-GPU partition: project ids [first, first+count) and pack the splat
     // records of every tile-row slab they meet; render a slab from the records it received
     gsm_status projectPartition(hipStream_t stream, const gsm_gaussian_input& input,
@@ -98,10 +104,12 @@ class GlobalRenderer {
     // scan, scatter, sort, headers and blend after `front` filled the per-gaussian arrays
     // (views: a batch -- `a` holds what its views share, the targets are view 0's)
     // (batchFrame.views > 0: a batch of different views -- `a` holds what they share, nothing per view)
+    // (compose.objects > 0: a composite -- `a` is the frame's, as a single frame's; only the items differ)
     struct ViewFrame {
         ViewBatch batch;
         size_t colorStride = 0, depthStride = 0;
         BatchFrame batchFrame;
+        ComposeFrame compose;
     };
     template <class Front>
     gsm_status runFrame(hipStream_t s, const ProjectArgs& a, uint32_t width, uint32_t height, void* color,
@@ -112,8 +120,10 @@ class GlobalRenderer {
     // order is off), its cost arrays cleared when the geometry or the view count changed
     // (batchTiles > 0: a batch of different views, keyed by its signature batchSig_ -- the view count and every
     // view's width, height and count)
+    // (compose: a composite, on the single frame's units, keyed by its signature composeSig_ -- the size, the
+    // object count and every object's count)
     uint32_t scheduleUnits(hipStream_t s, uint32_t width, uint32_t height, uint32_t views = 0,
-                           uint32_t batchTiles = 0);
+                           uint32_t batchTiles = 0, bool compose = false);
     static uint32_t tiles_of(uint32_t width, uint32_t height);  // tiles of a width x height frame
     // checks and arguments renderViews and renderBatch share: a view's size within the handle's, a batch's
     // tiles within its tile space and the key's 16-bit field, no set_tile_rows restriction, and the
@@ -158,6 +168,7 @@ class GlobalRenderer {
     int lastBlendKernel_ = 0;  // gsm_blend_kernel of the last enqueued frame (gsm_global_debug_blend_kernel)
     bool keptRenderData_ = false;  // the last frame wrote GaussianRenderData for readback
     uint32_t lastCount_ = 0, lastWidth_ = 0, lastHeight_ = 0;
+    uint32_t lastItems_ = 0;  // entries of the last frame's per-gaussian arrays (a composite: 256 per block)
     const uint32_t* sortedKeys_ = nullptr;
     const uint32_t* sortedVals_ = nullptr;
     const uint32_t* unsortedKeys_ = nullptr;
@@ -172,6 +183,10 @@ class GlobalRenderer {
     std::vector<uint32_t> batchSig_;          // this call's batch signature: width, height, count of every view
     std::vector<uint32_t> schedBatchSig_;     // the signature the unit costs belong to (schedBatch_)
     bool schedBatch_ = false;                 // the unit costs belong to a batch of different views
+    std::vector<ComposeObjectArgs> composeHost_;  // the last composite's per-object entries (render_composite)
+    std::vector<uint32_t> composeSig_;        // this call's composite signature: width, height, every object's count
+    std::vector<uint32_t> schedComposeSig_;   // the signature the unit costs belong to (schedCompose_)
+    bool schedCompose_ = false;               // the unit costs belong to a composite
 };
 
 }  // namespace gsm

@@ -1,8 +1,21 @@
-// gsm_scatter_body.h -- the text of k_scatter, compiled three times by gsm_kernels.hip: as the single frame's
+// gsm_scatter_body.h -- the text of k_scatter, compiled four times by gsm_kernels.hip: as the single frame's
 // kernel (GSM_VIEWS 0: k_scatter, exactly the kernel it was before batches of views existed), as the scatter
-// of a batch of views of one scene (GSM_VIEWS 1: k_scatter_views) and as the scatter of a batch of views of
-// different scenes and sizes (GSM_VIEWS 2: k_scatter_batch).  No include guard.
-#if GSM_VIEWS == 2
+// of a batch of views of one scene (GSM_VIEWS 1: k_scatter_views), as the scatter of a batch of views of
+// different scenes and sizes (GSM_VIEWS 2: k_scatter_batch) and as the scatter of several posed objects into
+// one frame (GSM_VIEWS 3: k_scatter_compose).  No include guard.
+#if GSM_VIEWS == 3
+// The scatter of a composite (k_project_compose's items): every workgroup holds items of one object
+// (blockObject, uniform), the items past that object's count hold no gaussian, and a tile id is the frame's own
+// (no base: all objects share one tile space and one target).  Slot order within a tile and depth is ascending
+// item = ascending object, then ascending gaussian id.
+__global__ __launch_bounds__(kProjectBlock) void k_scatter_compose(
+    ProjectArgs P, const ComposeObjectArgs* __restrict__ objects, const uint16_t* __restrict__ blockObject,
+    const GaussianRenderData* __restrict__ rd, const short4* __restrict__ bounds,
+    const uint32_t* __restrict__ counts, const uint32_t* __restrict__ masks,
+    const uint32_t* __restrict__ blockOffsets, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+    const float2* __restrict__ sincos, const BlendRecord* __restrict__ rec, uint32_t fusedScan,
+    TileAssignmentHeader* __restrict__ hdr, uint32_t* __restrict__ blendQueue) {
+#elif GSM_VIEWS == 2
 // The scatter of a batch of different views (k_project_batch's items): every workgroup holds items
 // of one view (blockView, uniform), the items past that view's count hold no gaussian, a tile id is the view's
 // tileBase + its local tile on the view's own grid, and the rows are [0, tilesY) of that grid.  Slot order within
@@ -47,7 +60,18 @@ __global__ __launch_bounds__(kProjectBlock) void k_scatter(
     constexpr uint16_t kNoOwner = 0xFFFFu;
     __shared__ uint16_t sOwn[kOwnCap];
     const uint32_t gid = blockIdx.x * kProjectBlock + threadIdx.x;
-#if GSM_VIEWS == 2
+#if GSM_VIEWS == 3
+    // every item of the composite (whole blocks per object); the thread's item holds a gaussian below its
+    // object's count
+    const uint32_t n = gridDim.x * kProjectBlock;
+    bool isItem;
+    {
+        const ComposeObjectArgs& V = objects[__builtin_amdgcn_readfirstlane((uint32_t)blockObject[blockIdx.x])];
+        isItem = (blockIdx.x - V.blockBase) * kProjectBlock + threadIdx.x < V.count;
+    }
+#define GSM_TILE_ID(t) ((uint32_t)(t))
+#define GSM_IS_ITEM isItem
+#elif GSM_VIEWS == 2
     // every item of the batch (whole blocks per view); the thread's item holds a gaussian below its view's count
     const uint32_t n = gridDim.x * kProjectBlock;
     uint32_t tileBase;

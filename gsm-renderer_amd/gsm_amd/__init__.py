@@ -167,6 +167,14 @@ class BatchView:
     depth_pitch: Optional[int] = None
 
 
+@dataclass
+class SceneObject:
+    """gsm_global_object: one object of GlobalRenderer.render_composite -- a resident scene and the frame's camera
+    as seen from that scene's own space (scenes.object_camera(camera, model) for a model matrix)."""
+    input: GaussianInput
+    camera: CameraParams
+
+
 # ---------------------------------------------------------------------------
 # ctypes layer
 # ---------------------------------------------------------------------------
@@ -191,6 +199,10 @@ class _GlobalView(C.Structure):  # gsm_global_view
     _fields_ = [("input", _Input), ("camera", _Camera), ("width", C.c_uint32), ("height", C.c_uint32),
                 ("color", C.c_void_p), ("color_pitch_bytes", C.c_size_t),
                 ("depth", C.c_void_p), ("depth_pitch_bytes", C.c_size_t)]
+
+
+class _GlobalObject(C.Structure):  # gsm_global_object
+    _fields_ = [("input", _Input), ("camera", _Camera)]
 
 
 class _Counters(C.Structure):
@@ -234,6 +246,8 @@ _SIGNATURES = {
                                  C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
                                  C.c_size_t, C.c_size_t], C.c_int),
     "gsm_global_render_batch": ([C.c_void_p, C.c_void_p, C.POINTER(_GlobalView), C.c_uint32], C.c_int),
+    "gsm_global_render_composite": ([C.c_void_p, C.c_void_p, C.POINTER(_GlobalObject), C.c_uint32, C.c_uint32,
+                                     C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t], C.c_int),
     "gsm_global_render_stereo": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera),
                                   C.POINTER(_Camera), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                   C.c_void_p, C.c_size_t], C.c_int),
@@ -506,6 +520,25 @@ class GlobalRenderer(_Renderer):
                 g.color_pitch_bytes = int(v.color_pitch) if v.color_pitch is not None else int(v.width) * self._bpp
                 g.depth_pitch_bytes = int(v.depth_pitch) if v.depth_pitch is not None else int(v.width) * 2
         _check(_lib().gsm_global_render_batch(self._h, _stream_handle(stream), arr, n), "gsm_global_render_batch")
+
+    def render_composite(self, color_texture, depth_texture, objects, width: int, height: int, stream=None,
+                         color_pitch: Optional[int] = None, depth_pitch: Optional[int] = None):
+        """gsm_global_render_composite: the SceneObject list `objects` -- resident scenes, each under its own
+        pose given as a camera -- sorted and blended together into one width x height frame.  objects None: a
+        NULL array with object_count 1 (the C entry's error path)."""
+        n = 1 if objects is None else len(objects)
+        arr = None
+        if objects is not None:
+            arr = (_GlobalObject * max(n, 1))()
+            for g, o in zip(arr, objects):
+                g.input = _Input(_ptr(o.input.gaussians), _ptr(o.input.harmonics), int(o.input.gaussian_count),
+                                 int(o.input.sh_components))
+                g.camera = _camera_struct(o.camera)
+        cp = color_pitch if color_pitch is not None else int(width) * self._bpp
+        dp = depth_pitch if depth_pitch is not None else int(width) * 2
+        st = _lib().gsm_global_render_composite(self._h, _stream_handle(stream), arr, n, int(width), int(height),
+                                                _ptr(color_texture), cp, _ptr(depth_texture), dp)
+        _check(st, "gsm_global_render_composite")
 
     def project_partition(self, input: GaussianInput, camera: CameraParams, width: int, height: int,
                           first: int, count: int, slab_rows, send, send_capacity: int, send_counts,

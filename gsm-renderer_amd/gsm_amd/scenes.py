@@ -64,6 +64,26 @@ def orbit_camera(width: int, height: int, angle_deg: float, pivot_z: float = 5.5
     return cam
 
 
+def object_camera(cam: dict, model) -> dict:
+    """The camera `cam` as seen from the space of an object with model matrix `model` (4x4, column-major flat
+    like scene_transform: object space -> world space), for GlobalRenderer.render_composite: view * M and
+    M^-1 * position, computed in float64 and rounded once to float32; everything else of `cam` unchanged.
+    Exact for a rotation, a translation and a uniform scale (the gaussians' scales stay in object space)."""
+    M = np.asarray(model, np.float64).reshape(4, 4).T  # column-major flat -> the matrix
+    out = dict(cam)
+    out["proj"] = np.asarray(cam["proj"], np.float32).reshape(-1).copy()
+    if np.array_equal(M, np.eye(4)):  # the camera's own words (a product's sums would turn a -0 into +0)
+        out["view"] = np.asarray(cam["view"], np.float32).reshape(-1).copy()
+        out["position"] = np.asarray(cam["position"], np.float32).reshape(-1).copy()
+        return out
+    V = np.asarray(cam["view"], np.float64).reshape(4, 4).T
+    p = np.append(np.asarray(cam["position"], np.float64).reshape(3), 1.0)
+    q = np.linalg.inv(M) @ p
+    out["view"] = (V @ M).T.reshape(-1).astype(np.float32)
+    out["position"] = (q[:3] / q[3]).astype(np.float32)
+    return out
+
+
 def _f16_bits(x: np.ndarray) -> np.ndarray:
     return np.asarray(x, np.float32).astype(np.float16).view(np.uint16)
 

@@ -203,6 +203,71 @@ _Static_assert(sizeof(gsm_global_view) == 224, "gsm_global_view is 224 bytes");
 gsm_status gsm_global_render_batch(gsm_renderer *renderer, void *stream,
                                    const gsm_global_view *views, uint32_t view_count);
 
+/* One object of a composite (gsm_global_render_composite): a resident scene and the frame's camera as seen
+ * from that scene's own space. */
+typedef struct {
+    gsm_gaussian_input input;      /* this object's scene: device pointers, count, sh_components */
+    gsm_camera_params  camera;     /* the frame's camera in this object's space (below) */
+} gsm_global_object;
+#ifdef __cplusplus
+static_assert(sizeof(gsm_global_object) == 184, "gsm_global_object is 184 bytes");
+#else
+_Static_assert(sizeof(gsm_global_object) == 184, "gsm_global_object is 184 bytes");
+#endif
+
+/* Several posed scenes composed into one frame (no reference analogue): object_count objects,
+ * each a resident scene with its own pose, rendered by one launch chain into one width x height target.  The
+ * splats of all objects are sorted and blended together, so objects interleave in depth per tile as the
+ * gaussians of one scene do.
+ *
+ * The pose is a camera.  Object o is projected exactly as gsm_global_render would project it with
+ * objects[o].camera; the device sees cameras only, and no arithmetic is added to the numeric contract.  For an
+ * object with model matrix M (object space -> world space) under the frame's camera (view, proj, position) the
+ * caller passes
+ *     view_o = view * M,   position_o = M^-1 * position,   proj, near_plane and far_plane unchanged,
+ * so the spherical-harmonics view directions are taken in the object's own frame.  That is exact for a rotation,
+ * a translation and a uniform scale.  The gaussians' scales, and the cull of scales below 0.0005, are in object
+ * space: M does not rescale them.  For an M that is no similarity the object is whatever the projection gives
+ * for view * M.
+ *
+ * Order.  The frame is the Global frame of the concatenated objects: one assignment list sorted by
+ * (tile, 16-bit depth); equal keys keep ascending object index, then ascending gaussian id.  With one camera
+ * for all objects the bytes equal those of gsm_global_render of the concatenated buffers.
+ *
+ * Layout.  Object o's items start at 256 * B_o, B_o = sum over u < o of ceil(count_u / 256); an object with
+ * count 0 owns no block.  All objects use the handle's tile grid and the one target, as gsm_global_render does
+ * for width x height.  After a captured composite gsm_global_debug_copy returns the per-gaussian buffers
+ * (render data, bounds, tile counts) indexed by item -- 256 entries per block of the composite, 256 * sum over
+ * o of ceil(count_o / 256) in all -- and the sort values hold items.  Unspecified in those buffers: every entry
+ * at or past its object's count, and, as after gsm_global_render, the render data of a culled gaussian (one
+ * whose bounds are empty: only visible gaussians write render data).
+ *
+ * Enqueue-only on `stream`; `objects` is host memory and is consumed before the call returns.  Only small
+ * per-object arrays are allocated, by the handle's first composite; nothing per frame after it.  All objects
+ * use the handle's precision and colour format.
+ *
+ * Checked before anything is enqueued; the first failing check in this order decides, within a check the
+ * lowest object index:
+ *   GSM_ERR_INVALID_GAUSSIAN_COUNT   object_count == 0 or > 65535, a gaussian_count > max_gaussians, or
+ *                                    sum of roundup(gaussian_count, 256) > max_gaussians (all counts 0 is an
+ *                                    empty frame: the clear value everywhere);
+ *   GSM_ERR_INVALID_DIMENSIONS       width or height zero, or above max_width / max_height;
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  objects NULL (with object_count >= 1: before every other check, since
+ *                                    nothing of it can be read), color NULL, or an object's gaussians /
+ *                                    harmonics NULL with a count > 0;
+ *   GSM_ERR_INVALID_BUFFER_SIZE      a pitch smaller than a row, or a target or pitch misaligned (colour
+ *                                    4 bytes, depth 2);
+ *   GSM_ERR_INVALID_ARGUMENT         objects that differ in sh_components;
+ *   GSM_ERR_UNSUPPORTED              the handle is restricted to tile rows (gsm_global_set_tile_rows).
+ * The assignment capacity (4 * max_gaussians) is shared by the objects: a composite that exceeds it sets the
+ * overflow counter (gsm_debug.h), and no parity is promised for that frame.  The counters report the
+ * composite; gaussian_count is the sum of the objects' counts. */
+gsm_status gsm_global_render_composite(gsm_renderer *renderer, void *stream,
+                                       const gsm_global_object *objects, uint32_t object_count,
+                                       uint32_t width, uint32_t height,
+                                       void *color, size_t color_pitch_bytes,
+                                       void *depth_r16f, size_t depth_pitch_bytes);
+
 /* GlobalRenderer.renderStereo (GlobalRenderer.swift:240-255) calls fatalError for
  * every target; this entry returns GSM_ERR_UNSUPPORTED instead. */
 gsm_status gsm_global_render_stereo(gsm_renderer *renderer, void *stream,
