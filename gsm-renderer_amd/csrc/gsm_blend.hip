@@ -92,15 +92,37 @@ __device__ __forceinline__ void blend_wave_sync() {
 // The records of the walk's current 64-entry batch are staged in LDS and read back with uniform
 // addresses (one ds_read_b128 + one ds_read_b32 broadcast per entry) instead of 5 v_readlane;
 // 2-entry pipeline groups at P = 2 (4-entry groups measured no gain).
+// the pick walk (k_blend_px_pick): `item` becomes a pixel's pick where its weight w exceeds the heaviest so far.
+// Two fp16 compares: the earliest entry wins ties, a weight of zero or NaN never wins.
+__device__ __forceinline__ void pick_update(h2& best, uint32_t (&pk)[2], h2 w, uint32_t item) {
+    if (w.x > best.x) {
+        best.x = w.x;
+        pk[0] = item;
+    }
+    if (w.y > best.y) {
+        best.y = w.y;
+        pk[1] = item;
+    }
+}
+
+#define GSM_BLEND_PICK 0
 #define GSM_BLEND_VIEWS 0
 #include "gsm_blend_px_body.h"
 #undef GSM_BLEND_VIEWS
+#undef GSM_BLEND_PICK
+#define GSM_BLEND_PICK 1
+#define GSM_BLEND_VIEWS 0
+#include "gsm_blend_px_body.h"
+#undef GSM_BLEND_VIEWS
+#undef GSM_BLEND_PICK
+#define GSM_BLEND_PICK 0
 #define GSM_BLEND_VIEWS 1
 #include "gsm_blend_px_body.h"
 #undef GSM_BLEND_VIEWS
 #define GSM_BLEND_VIEWS 2
 #include "gsm_blend_px_body.h"
 #undef GSM_BLEND_VIEWS
+#undef GSM_BLEND_PICK
 
 
 int blend_pairs_per_lane(uint32_t numTiles, int numCUs) {
@@ -132,7 +154,8 @@ static int blend_waves_per_wg(uint32_t numTiles, int numCUs) {
 // SIMD (flags bit 2), later units' priority rising with the age of their walk (flags bit 1).
 int launch_blend(const FrameGeometry& g, const DeviceArena& A, void* color,
                   size_t colorPitch, void* depth, size_t depthPitch, int numCUs, bool costOrder, int colorFormat,
-                  hipStream_t s, int wavesOverride, int claim, const MgArrive* arrive, bool pairs) {
+                  hipStream_t s, int wavesOverride, int claim, const MgArrive* arrive, bool pairs, void* pick,
+                  size_t pickPitch) {
     // local tile ids: tile t = k * tilesX + tx of the renderer's row k (pixel row rowBegin + k * rowStride)
     // (a batch of views: views * tilesPerView tiles, every rule below takes the batch's count)
     const uint32_t numTiles = frame_tiles(g);
@@ -156,6 +179,32 @@ int launch_blend(const FrameGeometry& g, const DeviceArena& A, void* color,
     // per wave (r05, k_blend_pw).  The pairs cut the VALU work (-10 %) but halve the waves walking: a gain
     // where the walk is VALU-bound (config 3: blend 370 -> 327 us), a loss where it is bound by its
     // longest units and latency (config 2: 121 -> 129-147 us at every split tried).
+    // A pick frame: the single frame's walk that also writes the pick target -- quadrant or
+    // half-tile units by the rule above, no compaction, no pair walk.  (Whole frames of one GPU only: the host
+    // refuses tile rows, and no batch or gathered frame has a pick entry.)
+    if (pick) {
+        const uint32_t punits = numTiles * (4u / (uint32_t)P);
+        uint32_t pgrid = (punits + (uint32_t)waves - 1) / (uint32_t)waves;
+        if (pgrid > (uint32_t)numCUs) pgrid = (uint32_t)numCUs;
+        const int pflags = flags | (((((uintptr_t)pick) & 7u) == 0 && (pickPitch & 7u) == 0) ? 8192 : 0);
+#define GSM_LAUNCH_BLEND_PICK(NTH, PP)                                                                                \
+    hipLaunchKernelGGL((k_blend_px_pick<NTH, PP, false>), dim3(pgrid), dim3(NTH), 0, s, A.tileStart, A.rec,          \
+                       A.expTable, A.tileQueue, numTiles, g.tilesX, g.width, g.height, (uint8_t*)color, colorPitch,  \
+                       (uint8_t*)depth, depthPitch, (uint8_t*)pick, pickPitch, pflags,                               \
+                       costOrder ? A.unitOrder : nullptr, A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1],    \
+                       A.halfCount, g.tileCount, A.costMax)
+        if (P == 1) {
+            if (waves == 16) GSM_LAUNCH_BLEND_PICK(1024, 1);
+            else if (waves == 12) GSM_LAUNCH_BLEND_PICK(768, 1);
+            else GSM_LAUNCH_BLEND_PICK(512, 1);
+        } else {
+            if (waves == 16) GSM_LAUNCH_BLEND_PICK(1024, 2);
+            else if (waves == 12) GSM_LAUNCH_BLEND_PICK(768, 2);
+            else GSM_LAUNCH_BLEND_PICK(512, 2);
+        }
+#undef GSM_LAUNCH_BLEND_PICK
+        return P == 1 ? GSM_BLEND_KERNEL_QUADRANT : GSM_BLEND_KERNEL_HALF_TILE;
+    }
     if (pairs && P == 2 && !arrive && waves == 16) {
         launch_blend_pw(g, A, color, colorPitch, depth, depthPitch, numCUs, costOrder, colorFormat, s, waves);
         return GSM_BLEND_KERNEL_PAIR_WALK;

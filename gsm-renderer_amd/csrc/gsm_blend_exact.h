@@ -45,10 +45,13 @@ __device__ __forceinline__ bool batch_depth_nonfinite(uint32_t recB) {
 // half-tile layout: a 4x2 group on lanes 2g, 2g + 1); P = 1: a 16x8 quadrant, lane = one pixel pair
 // (a group on a lane quad).  stA / stB: the wave's 64-entry LDS record stage.  write(px, py, A, R, G,
 // B, D) stores the pixel pair (px, py), (px + 1, py).
-template <int P, typename Write>
+// PICK (k_blend_px_pick): the walk also tracks, per pixel, the item (list value) of the heaviest
+// weight w = alpha * T among the entries the group blends -- the earliest on ties, never a zero or a NaN -- and
+// write takes the pair's two picks after D.  stI: the wave's 64-entry LDS stage of the items.
+template <int P, bool PICK = false, typename Write>
 __device__ __forceinline__ void walk_unit_exact(const uint32_t* __restrict__ lst, uint32_t count, const BlendRecord* __restrict__ rec,
                                 const uint16_t* tbl, uint4* stA, uint32_t* stB, uint32_t ux, uint32_t uy,
-                                uint32_t thrBits, Write&& write) {
+                                uint32_t thrBits, Write&& write, uint32_t* stI = nullptr) {
     static_assert(P == 1 || P == 2, "quadrant or half-tile units");
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t offX, offY0, offY1;
@@ -73,6 +76,13 @@ __device__ __forceinline__ void walk_unit_exact(const uint32_t* __restrict__ lst
         T[q] = ONE;
         R[q] = G[q] = B[q] = D[q] = ZERO;
     }
+    xh2 best[P];
+    uint32_t pk[P][2];
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+        best[q] = ZERO;
+        pk[q][0] = pk[q][1] = 0xFFFFFFFFu;  // GSM_PICK_NONE
+    }
     bool alive = true;
     const uint32_t last = count - 1u;
     const uint4 pad = make_uint4(x_u32(xh2{(xh1)(float)ux, (xh1)(float)uy}), 0u, 0u, 0u);
@@ -89,6 +99,7 @@ __device__ __forceinline__ void walk_unit_exact(const uint32_t* __restrict__ lst
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         stA[lane] = a;
         stB[lane] = b;
+        if constexpr (PICK) stI[lane] = gi;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -137,6 +148,17 @@ __device__ __forceinline__ void walk_unit_exact(const uint32_t* __restrict__ lst
 #pragma unroll
                 for (int q = 0; q < P; ++q) {
                     const xh2 w = ac[q] * T[q];  // (GlobalShaders.metal:1137-1149)
+                    if constexpr (PICK) {
+                        const uint32_t item = stI[j];
+                        if (w.x > best[q].x) {
+                            best[q].x = w.x;
+                            pk[q][0] = item;
+                        }
+                        if (w.y > best[q].y) {
+                            best[q].y = w.y;
+                            pk[q][1] = item;
+                        }
+                    }
                     T[q] = T[q] * om[q];
                     R[q] = __builtin_elementwise_fma(x_lo(rgv), w, R[q]);
                     G[q] = __builtin_elementwise_fma(x_hi(rgv), w, G[q]);
@@ -147,8 +169,15 @@ __device__ __forceinline__ void walk_unit_exact(const uint32_t* __restrict__ lst
         }
         if (__ballot(alive) == 0ull) break;
     }
-    write(ux + offX, uy + offY0, ONE - T[0], R[0], G[0], B[0], D[0]);
-    if (P == 2) write(ux + offX, uy + offY1, ONE - T[P - 1], R[P - 1], G[P - 1], B[P - 1], D[P - 1]);
+    if constexpr (PICK) {
+        write(ux + offX, uy + offY0, ONE - T[0], R[0], G[0], B[0], D[0], pk[0][0], pk[0][1]);
+        if (P == 2)
+            write(ux + offX, uy + offY1, ONE - T[P - 1], R[P - 1], G[P - 1], B[P - 1], D[P - 1], pk[P - 1][0],
+                  pk[P - 1][1]);
+    } else {
+        write(ux + offX, uy + offY0, ONE - T[0], R[0], G[0], B[0], D[0]);
+        if (P == 2) write(ux + offX, uy + offY1, ONE - T[P - 1], R[P - 1], G[P - 1], B[P - 1], D[P - 1]);
+    }
 }
 
 }  // namespace blend_exact

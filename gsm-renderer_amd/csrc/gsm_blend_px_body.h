@@ -7,7 +7,30 @@
 // A batch's tile t belongs to view t / tilesPerView, whose targets start that many view strides after the
 // first view's; the unit's pixel coordinates are the view's own (the fp16 half(x), half(y) of the quadratic
 // form see the single frame's values), and nothing else of the walk knows what a view is.  No include guard.
-#if GSM_BLEND_VIEWS == 2
+// A fourth time with GSM_BLEND_PICK 1 (GSM_BLEND_VIEWS 0): k_blend_px_pick, the single frame's walk that also
+// tracks, per pixel, the item of its heaviest contribution w = alpha * T and writes it to a third target
+// (gsm_global_render_pick, gsm_global_render_composite_pick).  Whole frames on one GPU, quadrant
+// or half-tile units, no compaction.
+#if !GSM_BLEND_PICK
+#define GSM_PICK_PARAMS
+#define GSM_PICK_ARGS(q)
+#endif
+#if GSM_BLEND_PICK
+#define GSM_PICK_PARAMS , uint32_t pk0, uint32_t pk1  // the pixel pair's picks travel with its colour
+#define GSM_PICK_ARGS(q) , pk[q][0], pk[q][1]
+template <int NT, int P, bool COMPACT = false>
+__global__ __launch_bounds__(NT) void k_blend_px_pick(
+    const uint32_t* __restrict__ tileStart, const BlendRecord* __restrict__ rec,
+    const uint16_t* __restrict__ expTable, uint32_t* __restrict__ queue, uint32_t numTiles, uint32_t tilesX,
+    uint32_t W, uint32_t H, uint8_t* __restrict__ color, size_t colorPitch, uint8_t* __restrict__ depth,
+    size_t depthPitch, uint8_t* __restrict__ pickOut, size_t pickPitch, int flags,
+    const uint32_t* __restrict__ order, uint16_t* __restrict__ unitCost, unsigned long long* __restrict__ trace,
+    const uint32_t* __restrict__ half0, const uint32_t* __restrict__ half1, const uint32_t* __restrict__ halfCount,
+    uint32_t tileCount, uint32_t* __restrict__ costMax) {
+    static_assert(!COMPACT, "the pick walk keeps its unit layout");
+    constexpr uint32_t tileBegin = 0, rowBegin = 0, rowStride = 1;  // whole frames on one GPU: no tile rows, no gather
+    const MgArrive arrive{};
+#elif GSM_BLEND_VIEWS == 2
 // the blend of a batch of different views (gsm_global_render_batch): numTiles = the sum of the views' tiles
 template <int NT, int P, bool COMPACT = false>
 __global__ __launch_bounds__(NT) void k_blend_px_batch(
@@ -61,9 +84,14 @@ __global__ __launch_bounds__(NT) void k_blend_px(
     constexpr uint32_t UNROLL = NG;
     const bool agePrio = (flags & 2) != 0;
     __shared__ __attribute__((aligned(16))) uint16_t tbl[65536];
+#if !GSM_BLEND_PICK
     __shared__ uint32_t cscr[NW][16];  // compaction: the alive groups of each wave, in order
+#endif
     __shared__ __attribute__((aligned(16))) uint4 lrecA[NW][64];  // current batch records
     __shared__ uint32_t lrecB[NW][64];
+#if GSM_BLEND_PICK
+    __shared__ uint32_t litem[NW][64];  // the staged batch's items (the list values), next to their records
+#endif
     __shared__ uint32_t exitCount;  // a gathered multi-GPU frame: waves of this workgroup past their last unit
     if (threadIdx.x == 0) exitCount = 0;
     GSM_EXP_TABLE_TO_LDS(NT, expTable, tbl);
@@ -79,7 +107,7 @@ __global__ __launch_bounds__(NT) void k_blend_px(
     auto st32 = [&](uint8_t* p, uint32_t v) { *(uint32_t*)p = v; };
     auto std32 = [&](uint8_t* p, uint32_t v) { *(uint32_t*)p = v; };
     auto std16 = [&](uint8_t* p, uint16_t v) { *(uint16_t*)p = v; };
-    auto write_pair = [&](uint32_t px, uint32_t py, h2 Av, h2 Rq, h2 Gq, h2 Bq, h2 Dq) {
+    auto write_pair = [&](uint32_t px, uint32_t py, h2 Av, h2 Rq, h2 Gq, h2 Bq, h2 Dq GSM_PICK_PARAMS) {
         if (py >= H) return;
         uint8_t* crow = color + (size_t)py * colorPitch;
         // integer packing (extracting .y of a half2 via __builtin_bit_cast miscompiled)
@@ -142,6 +170,16 @@ __global__ __launch_bounds__(NT) void k_blend_px(
                 if (px + 1 < W) std16(depth + (size_t)py * depthPitch + (size_t)(px + 1) * 2, (uint16_t)(ud >> 16));
             }
         }
+#if GSM_BLEND_PICK
+        // the pick pair: one 8-byte store where the target is aligned for it (flags bit 13; px is even)
+        uint8_t* prow = pickOut + (size_t)py * pickPitch + (size_t)px * 4;
+        if ((flags & 8192) && px + 1 < W) {
+            *(uint2*)prow = make_uint2(pk0, pk1);
+        } else {
+            if (px < W) st32(prow, pk0);
+            if (px + 1 < W) st32(prow + 4, pk1);
+        }
+#endif
     };
     // pixel pair k of this lane sits at (px[k], py[k]) and (px[k] + 1, py[k]) inside the unit
     uint32_t offX[P], offY[P];
@@ -243,6 +281,16 @@ __global__ __launch_bounds__(NT) void k_blend_px(
             T[k] = ONE;
             R[k] = G[k] = B[k] = D[k] = ZERO;
         }
+#if GSM_BLEND_PICK
+        // per pixel: the heaviest weight so far (+0: a weight of zero or NaN never wins) and its item
+        h2 best[P];
+        uint32_t pk[P][2];
+#pragma unroll
+        for (int k = 0; k < P; ++k) {
+            best[k] = ZERO;
+            pk[k][0] = pk[k][1] = GSM_PICK_NONE;
+        }
+#endif
         // the unit met a record of inf / NaN fp16 depth: walked again exactly at its end (gsm_blend_exact.h)
         bool exactD = false;
         if (count > 0) {
@@ -270,6 +318,10 @@ __global__ __launch_bounds__(NT) void k_blend_px(
             uint4 mA = *(const uint4*)(rec + gi2);
             uint32_t mB = rec[gi2].b;
             uint32_t nI = lst[min(192u + lane, last)];
+#if GSM_BLEND_PICK
+            uint32_t iN = gi1, iM = gi2;  // the items of batches nA and mA (lanes past the end: alpha 0, never picked)
+            uint32_t itc[U], itn[U];
+#endif
             if (claimMode == 0 || (claimMode == 2 && expWalk <= 64u)) claim();
             if (lane >= count) {
                 bA = pad;
@@ -285,7 +337,9 @@ __global__ __launch_bounds__(NT) void k_blend_px(
             uint32_t rgc[U], bdc[U], rgn[U], bdn[U], opn[U];
             u16x2 en[U][P];  // next group's exp table words (d16 loads into both halves)
             bool alive = true;
+#if !GSM_BLEND_PICK
             uint32_t eC = 0, b0C = 0;  // compaction: next entry, its batch base
+#endif
             // p = ((dx*dx)*cxx + (dy*dy)*cyy) + (dx*dy)*cxy2 (GlobalShaders.metal:1115-1122);
             // the dy terms are computed once for the lane's rows, at P = 2 the dx terms once for its
             // two columns (the same operations per pixel, fewer of them per lane)
@@ -306,6 +360,9 @@ __global__ __launch_bounds__(NT) void k_blend_px(
             };
             lrecA[wv][lane] = bA;
             lrecB[wv][lane] = bB;
+#if GSM_BLEND_PICK
+            litem[wv][lane] = gi0;
+#endif
             blend_wave_sync();
             // prime group 0
 #pragma unroll
@@ -315,6 +372,9 @@ __global__ __launch_bounds__(NT) void k_blend_px(
                 quadform(__builtin_amdgcn_readlane(bA.x, k), __builtin_amdgcn_readlane(bA.y, k), r2, pq);
                 rgc[k] = __builtin_amdgcn_readlane(bA.w, k);
                 bdc[k] = __builtin_amdgcn_readlane(bB, k);
+#if GSM_BLEND_PICK
+                itc[k] = __builtin_amdgcn_readlane(gi0, k);
+#endif
 #pragma unroll
                 for (int q = 0; q < P; ++q) {
                     // a = min(opacity * exp(-0.5h * p), 0.99h) (GlobalShaders.metal:1124-1131)
@@ -332,6 +392,9 @@ __global__ __launch_bounds__(NT) void k_blend_px(
                         if (nb) {  // every entry of this batch was read: stage the next one
                             lrecA[wv][lane] = nA;
                             lrecB[wv][lane] = nB;
+#if GSM_BLEND_PICK
+                            litem[wv][lane] = iN;
+#endif
                             blend_wave_sync();
                             exactD = exactD || blend_exact::batch_depth_nonfinite(nB);
                         }
@@ -344,6 +407,9 @@ __global__ __launch_bounds__(NT) void k_blend_px(
                             quadform(ra.x, ra.y, ra.z, pq);
                             rgn[k] = ra.w;
                             bdn[k] = lrecB[wv][j];
+#if GSM_BLEND_PICK
+                            itn[k] = litem[wv][j];
+#endif
 #pragma unroll
                             for (int q = 0; q < P; ++q) {
                                 // raw table words: first used in stage 3, after the current
@@ -378,6 +444,9 @@ __global__ __launch_bounds__(NT) void k_blend_px(
 #pragma unroll
                             for (int q = 0; q < P; ++q) {
                                 const h2 w = ac[k][q] * T[q];  // (GlobalShaders.metal:1137-1149)
+#if GSM_BLEND_PICK
+                                pick_update(best[q], pk[q], w, itc[k]);  // (T before this entry's update)
+#endif
                                 T[q] = T[q] * om[k][q];
                                 R[q] = blend_acc(R[q], splat_lo(rgv), w);
                                 G[q] = blend_acc(G[q], splat_hi(rgv), w);
@@ -394,6 +463,7 @@ __global__ __launch_bounds__(NT) void k_blend_px(
                             nproc = g1;
                             goto unit_done;
                         }
+#if !GSM_BLEND_PICK
                         // at most 16 of the 32 groups alive: continue them one pixel pair per lane
                         // (two 32-bit counts: a 64-bit popcount's compare goes to the VALU)
                         if (COMPACT && (uint32_t)__builtin_popcount((uint32_t)am & 0x55555555u) +
@@ -402,6 +472,7 @@ __global__ __launch_bounds__(NT) void k_blend_px(
                             b0C = b0;
                             goto compact_phase;
                         }
+#endif
                     }
                     // stage 3: the next group's alphas
 #pragma unroll
@@ -414,6 +485,9 @@ __global__ __launch_bounds__(NT) void k_blend_px(
                         }
                         rgc[k] = rgn[k];
                         bdc[k] = bdn[k];
+#if GSM_BLEND_PICK
+                        itc[k] = itn[k];
+#endif
                     }
                 }
                 if (topPrio) {
@@ -430,8 +504,13 @@ __global__ __launch_bounds__(NT) void k_blend_px(
                 nB = mv ? mB : 0u;
                 mA = *(const uint4*)(rec + nI);
                 mB = rec[nI].b;
+#if GSM_BLEND_PICK
+                iN = iM;
+                iM = nI;
+#endif
                 nI = lst[min(b0 + 256u + lane, last)];
             }
+#if !GSM_BLEND_PICK
         compact_phase:
             if constexpr (COMPACT) {
                 // Groups that broke keep their pixels: written now, in the half-tile layout.
@@ -570,6 +649,7 @@ __global__ __launch_bounds__(NT) void k_blend_px(
                 if (valid1) write_pair(px1, py1, ONE - T1, R1, G1, B1, D1);
                 goto unit_end;
             }
+#endif
         unit_done:;
         } else {
             if (claimMode != 1) claim();
@@ -577,11 +657,18 @@ __global__ __launch_bounds__(NT) void k_blend_px(
         // write (GlobalShaders.metal:1152-1186); empty tiles keep the clear colour (0,0,0,1)
 #pragma unroll
         for (int q = 0; q < P; ++q)
-            write_pair(ux + offX[q], uy + offY[q], (full > 0) ? (ONE - T[q]) : ONE, R[q], G[q], B[q], D[q]);
+            write_pair(ux + offX[q], uy + offY[q], (full > 0) ? (ONE - T[q]) : ONE, R[q], G[q], B[q], D[q] GSM_PICK_ARGS(q));
+#if !GSM_BLEND_PICK
     unit_end:
+#endif
         if (exactD)  // (rare: a record of inf / NaN fp16 depth; every pixel of the unit is written again)
+#if GSM_BLEND_PICK
+            blend_exact::walk_unit_exact<P, true>((hsel ? half1 : half0) + start, count, rec, tbl, lrecA[wv], lrecB[wv],
+                                                  ux, uy, thrBits, write_pair, litem[wv]);
+#else
             blend_exact::walk_unit_exact<P>((hsel ? half1 : half0) + start, count, rec, tbl, lrecA[wv], lrecB[wv], ux,
                                             uy, thrBits, write_pair);
+#endif
         if (unitCost && lane == 0) unitCost[u] = (uint16_t)min(nproc, 65535u);
         waveMax = max(waveMax, min(nproc, 65535u));
         if (trace && lane == 0) {
@@ -613,3 +700,5 @@ __global__ __launch_bounds__(NT) void k_blend_px(
         }
     }
 }
+#undef GSM_PICK_PARAMS
+#undef GSM_PICK_ARGS

@@ -101,10 +101,16 @@ class StageTimer {
 // ---- frame ----
 // What a frame call refuses, in this precedence: count, dimensions, missing buffer, buffer size.
 // widthFactor: frames a row of the colour target holds (2: side by side).  depth may be null.
+// pick (nullable): a pick frame's third target (one uint32_t per pixel, required like colour); it joins the
+// missing-buffer row and the buffer-size row.
+struct PickTarget {
+    void* pixels;
+    size_t pitch;
+};
 gsm_status validate_frame(const gsm_renderer_config& cfg, uint32_t maxGaussians, uint32_t maxWidth,
                           uint32_t maxHeight, uint32_t count, bool allowEmpty, bool inputMissing, uint32_t width,
                           uint32_t height, const void* color, size_t colorPitch, uint32_t widthFactor,
-                          const void* depth, size_t depthPitch);
+                          const void* depth, size_t depthPitch, const PickTarget* pick = nullptr);
 
 // The per-frame terms of projectCovariance2D (GaussianShared.h:340-355), the same fp32 operations
 // in the same order as the reference repeats per gaussian: part of the numeric contract.

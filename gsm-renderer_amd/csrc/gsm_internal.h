@@ -427,10 +427,13 @@ void launch_headers(const uint32_t* sortedKeys, const FrameGeometry& geo, const 
                     hipStream_t stream);
 // front-to-back fp16 blend + clear (GlobalShaders.metal:140-154, 1030-1187); returns the kernel it
 // launched (gsm_blend_kernel, include/gsm_debug.h; 0 for an empty frame)
+// pick (nullable): a pick frame's third target, one uint32_t per pixel (k_blend_px_pick) -- a
+// single frame or a composite over the handle's whole tile grid
 int launch_blend(const FrameGeometry& geo, const DeviceArena& A,
                   void* color, size_t colorPitch, void* depth, size_t depthPitch, int numCUs,
                   bool costOrder, int colorFormat, hipStream_t stream, int waves = 0, int claim = 1,
-                  const MgArrive* arrive = nullptr, bool pairs = false);
+                  const MgArrive* arrive = nullptr, bool pairs = false, void* pick = nullptr,
+                  size_t pickPitch = 0);
 // k_blend_pw (gsm_blend_pw.hip): two half-tile units per wave, one GPU's frame
 void launch_blend_pw(const FrameGeometry& g, const DeviceArena& A, void* color, size_t colorPitch, void* depth,
                      size_t depthPitch, int numCUs, bool costOrder, int colorFormat, hipStream_t s, int waves);

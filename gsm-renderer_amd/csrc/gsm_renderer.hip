@@ -175,9 +175,9 @@ ProjectArgs GlobalRenderer::frameArgs(const gsm_camera_params& camp, uint32_t wi
 
 gsm_status GlobalRenderer::validateFrame(uint32_t count, bool inputMissing, uint32_t width, uint32_t height,
                                          const void* color, size_t colorPitch, const void* depth,
-                                         size_t depthPitch) const {
+                                         size_t depthPitch, const PickTarget* pick) const {
     const gsm_status st = validate_frame(config_, maxGaussians_, maxWidth_, maxHeight_, count, true, inputMissing,
-                                         width, height, color, colorPitch, 1, depth, depthPitch);
+                                         width, height, color, colorPitch, 1, depth, depthPitch, pick);
     if (st != GSM_OK) return st;
     if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
     return GSM_OK;
@@ -186,9 +186,61 @@ gsm_status GlobalRenderer::validateFrame(uint32_t count, bool inputMissing, uint
 gsm_status GlobalRenderer::render(hipStream_t s, const gsm_gaussian_input& in,
                                   const gsm_camera_params& camp, uint32_t width, uint32_t height,
                                   void* color, size_t colorPitch, void* depth, size_t depthPitch) {
+    return renderFrame(s, in, camp, width, height, color, colorPitch, depth, depthPitch, nullptr);
+}
+
+gsm_status GlobalRenderer::renderPick(hipStream_t s, const gsm_gaussian_input& in, const gsm_camera_params& camp,
+                                      uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
+                                      size_t depthPitch, void* pick, size_t pickPitch) {
+    const PickTarget pt{pick, pickPitch};
+    return renderFrame(s, in, camp, width, height, color, colorPitch, depth, depthPitch, &pt);
+}
+
+gsm_status GlobalRenderer::renderCompositePick(hipStream_t s, const gsm_global_object* objects, uint32_t objectCount,
+                                               uint32_t width, uint32_t height, void* color, size_t colorPitch,
+                                               void* depth, size_t depthPitch, void* pick, size_t pickPitch) {
+    const PickTarget pt{pick, pickPitch};
+    return composeFrame(s, objects, objectCount, width, height, color, colorPitch, depth, depthPitch, &pt);
+}
+
+gsm_status GlobalRenderer::pickOwner(const uint32_t* items, uint32_t n, uint32_t* object, uint32_t* gaussian) const {
+    if (!lastPick_) return GSM_ERR_RENDER_FAILED;  // (the handle's last enqueued frame wrote no pick target)
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t item = items[i];
+        uint32_t obj = GSM_PICK_NONE, id = GSM_PICK_NONE;
+        if (item != GSM_PICK_NONE && item < lastItems_) {
+            if (!lastPickComposite_) {  // (lastItems_ = the input's count)
+                obj = 0;
+                id = item;
+            } else {
+                // the entry whose blocks hold the item (DESIGN.md 19's layout: entries ascend in blockBase)
+                const uint32_t block = item / (uint32_t)kProjectBlock;
+                size_t lo = 0, hi = composeHost_.size();
+                while (hi - lo > 1) {
+                    const size_t mid = (lo + hi) / 2;
+                    if (composeHost_[mid].blockBase <= block) lo = mid;
+                    else hi = mid;
+                }
+                const uint32_t local = item - composeHost_[lo].blockBase * (uint32_t)kProjectBlock;
+                if (local < composeHost_[lo].count) {
+                    obj = composeObject_[lo];
+                    id = local;
+                }
+            }
+        }
+        object[i] = obj;
+        gaussian[i] = id;
+    }
+    return GSM_OK;
+}
+
+gsm_status GlobalRenderer::renderFrame(hipStream_t s, const gsm_gaussian_input& in, const gsm_camera_params& camp,
+                                       uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
+                                       size_t depthPitch, const PickTarget* pick) {
     gsm_status st = validateFrame(in.gaussian_count, !in.gaussians || !in.harmonics, width, height, color,
-                                  colorPitch, depth, depthPitch);
+                                  colorPitch, depth, depthPitch, pick);
     if (st != GSM_OK) return st;
+    if (pick && tileRowsRestricted()) return GSM_ERR_UNSUPPORTED;  // (set_tile_rows: a pick frame is a whole frame)
     // the projection's tile tests walk contiguous rows; interleaved row sets come from the records
     // path only (gsm_multigpu)
     if (rowStride_ != 1) return GSM_ERR_INVALID_ARGUMENT;
@@ -198,7 +250,7 @@ gsm_status GlobalRenderer::render(hipStream_t s, const gsm_gaussian_input& in,
     return runFrame(s, a, width, height, color, colorPitch, depth, depthPitch,
                     [&](const ProjectArgs& pa) {
                         launch_project(half, deg, in.gaussians, in.harmonics, pa, arena_, s);
-                    });
+                    }, nullptr, false, nullptr, nullptr, pick);
 }
 
 uint32_t GlobalRenderer::tiles_of(uint32_t width, uint32_t height) {
@@ -421,6 +473,12 @@ gsm_status GlobalRenderer::renderBatch(hipStream_t s, const gsm_global_view* vie
 gsm_status GlobalRenderer::renderComposite(hipStream_t s, const gsm_global_object* objects, uint32_t objectCount,
                                            uint32_t width, uint32_t height, void* color, size_t colorPitch,
                                            void* depth, size_t depthPitch) {
+    return composeFrame(s, objects, objectCount, width, height, color, colorPitch, depth, depthPitch, nullptr);
+}
+
+gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* objects, uint32_t objectCount,
+                                        uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
+                                        size_t depthPitch, const PickTarget* pick) {
     // Every check before anything is enqueued, one kind of check after another over all objects (the first
     // failing kind decides, within it the lowest object): counts, dimensions, missing buffers, sizes,
     // sh_components, tile rows.  (The counts of a NULL array cannot be read: that is the missing buffer.)
@@ -437,7 +495,7 @@ gsm_status GlobalRenderer::renderComposite(hipStream_t s, const gsm_global_objec
     }
     if (items > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;  // (the values keep 30 bits of item)
     if (!frameSizeOk(width, height)) return GSM_ERR_INVALID_DIMENSIONS;
-    if (!color) return GSM_ERR_MISSING_REQUIRED_BUFFER;
+    if (!color || (pick && !pick->pixels)) return GSM_ERR_MISSING_REQUIRED_BUFFER;
     for (uint32_t o = 0; o < objectCount; ++o) {
         const gsm_gaussian_input& in = objects[o].input;
         if (in.gaussian_count > 0 && (!in.gaussians || !in.harmonics)) return GSM_ERR_MISSING_REQUIRED_BUFFER;
@@ -445,7 +503,7 @@ gsm_status GlobalRenderer::renderComposite(hipStream_t s, const gsm_global_objec
     }
     // (everything above passed: what is left of validate_frame is the pitches and the alignment)
     gsm_status st = validate_frame(config_, maxGaussians_, maxWidth_, maxHeight_, countSum, true, false, width, height,
-                                   color, colorPitch, 1, depth, depthPitch);
+                                   color, colorPitch, 1, depth, depthPitch, pick);
     if (st != GSM_OK) return st;
     for (uint32_t o = 1; o < objectCount; ++o)
         if (objects[o].input.sh_components != objects[0].input.sh_components) return GSM_ERR_INVALID_ARGUMENT;
@@ -463,6 +521,7 @@ gsm_status GlobalRenderer::renderComposite(hipStream_t s, const gsm_global_objec
         if (st == GSM_OK) st = allocs_.alloc((void**)&bo, (size_t)maxBlocks * sizeof(uint16_t));
         if (st != GSM_OK) return st;
         composeHost_.reserve(maxEntries);
+        composeObject_.reserve(maxEntries);
         composeSig_.reserve(2 + 65535u);
         schedComposeSig_.reserve(2 + 65535u);
         arena_.composeArgs = args;
@@ -473,6 +532,7 @@ gsm_status GlobalRenderer::renderComposite(hipStream_t s, const gsm_global_objec
     // -- its camera on the frame's size -- for the objects that have gaussians; the signature takes every object
     const uint32_t sh = objects[0].input.sh_components;
     composeHost_.clear();
+    composeObject_.clear();
     composeSig_.clear();
     composeSig_.push_back(width);
     composeSig_.push_back(height);
@@ -491,6 +551,7 @@ gsm_status GlobalRenderer::renderComposite(hipStream_t s, const gsm_global_objec
         d.harm = O.input.harmonics;
         d.blockBase = blockBase;
         composeHost_.push_back(d);
+        composeObject_.push_back(o);  // (pickOwner: the entry's object index of the call)
         blockBase += (n + kProjectBlock - 1) / kProjectBlock;
     }
     for (uint32_t e0 = 0; e0 < entries; e0 += kComposeChunk) {
@@ -514,7 +575,7 @@ gsm_status GlobalRenderer::renderComposite(hipStream_t s, const gsm_global_objec
     const bool half = config_.precision == GSM_PRECISION_FLOAT16;
     return runFrame(s, a, width, height, color, colorPitch, depth, depthPitch,
                     [&](const ProjectArgs& pa) { launch_project_compose(half, deg, pa, vf.compose, arena_, s); },
-                    nullptr, false, nullptr, &vf);
+                    nullptr, false, nullptr, &vf, pick);
 }
 
 gsm_status GlobalRenderer::renderRecords(hipStream_t s, const void* records, uint32_t count, uint32_t width,
@@ -652,7 +713,7 @@ gsm_status GlobalRenderer::partitionPush(hipStream_t s, uint32_t world, uint32_t
 }
 
 uint32_t GlobalRenderer::scheduleUnits(hipStream_t s, uint32_t width, uint32_t height, uint32_t views,
-                                       uint32_t batchTiles, bool compose) {
+                                       uint32_t batchTiles, bool compose, bool pick) {
     // (a batch of views: the units of views * tiles(width, height) tiles; the view count is part of the key, so
     // a batch neither inherits nor leaves behind a single frame's costs.  A batch of different views: the units
     // of its batchTiles tiles, keyed by its whole signature batchSig_, compared word for word)
@@ -665,7 +726,10 @@ uint32_t GlobalRenderer::scheduleUnits(hipStream_t s, uint32_t width, uint32_t h
                                     : ((uint64_t)upt << 60) ^ ((uint64_t)width << 40) ^ ((uint64_t)height << 20) ^
                                           ((uint64_t)rowStride_ << 30) ^ ((uint64_t)rowBegin_ << 10) ^ rowEnd_;
     const bool isBatch = batchTiles != 0;
-    bool changed = isBatch != schedBatch_ || compose != schedCompose_ || key != schedKey_ || views != schedViews_;
+    // (a pick frame walks without compaction or pairs: its costs are its own, either way round)
+    bool changed = isBatch != schedBatch_ || compose != schedCompose_ || key != schedKey_ || views != schedViews_ ||
+                   pick != schedPick_;
+    schedPick_ = pick;
     if (compose && !changed) changed = composeSig_ != schedComposeSig_;
     if (compose && changed) schedComposeSig_.assign(composeSig_.begin(), composeSig_.end());  // (reserved: no allocation)
     schedCompose_ = compose;
@@ -688,7 +752,7 @@ template <class Front>
 gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_t width, uint32_t height,
                                     void* color, size_t colorPitch, void* depth, size_t depthPitch,
                                     Front&& front, const uint32_t* devCount, bool preOrdered,
-                                    const MgArrive* blendArrive, const ViewFrame* views) {
+                                    const MgArrive* blendArrive, const ViewFrame* views, const PickTarget* pick) {
     (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's: the launches below are checked)
     const int profiling = timer_.flags();
     const bool keep = (profiling & 2) != 0;
@@ -711,6 +775,8 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     lastItems_ = comp ? comp->blocks * (uint32_t)kProjectBlock : a.count;
     lastWidth_ = width;
     lastHeight_ = height;
+    lastPick_ = pick != nullptr;
+    lastPickComposite_ = pick && comp;
     // Blend schedule: the units ordered by the walk lengths the previous frame of the same
     // geometry measured (the image does not depend on the order, only the load balance does).
     // The ordering only needs those costs: one extra workgroup of the projection launch does it
@@ -718,7 +784,7 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     // the multi-GPU frame orders them earlier, in its partition projection: preOrdered).
     const uint32_t units = preOrdered ? 0u
                                       : scheduleUnits(s, width, height, batch ? batch->views : views ? views->batch.views : 0u,
-                                                      batch ? batch->tiles : 0u, comp != nullptr);
+                                                      batch ? batch->tiles : 0u, comp != nullptr, pick != nullptr);
     const bool costOrder = preOrdered ? tuning_.costOrder : units > 0;
     fa.schedUnits = units;
     // (written on every scheduled frame: the blend's remaining-walk priorities read the longest walk too)
@@ -813,7 +879,7 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     timer_.record(5, s, true);
     lastBlendKernel_ = launch_blend(g, arena_, color, colorPitch, depth, depthPitch, dev_.numCUs, costOrder,
                  (int)config_.color_format, s, tuning_.blendWaves, tuning_.blendClaim, blendArrive,
-                 tuning_.blendPairs);
+                 tuning_.blendPairs, pick ? pick->pixels : nullptr, pick ? pick->pitch : 0);
     timer_.record(6, s, true);
     timer_.frameDone();
     if (hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;

@@ -229,6 +229,8 @@ class _LocalCounters(C.Structure):
                 ("overflow", C.c_uint32)]
 
 
+PICK_NONE = 0xFFFFFFFF  # include/gsm_renderer.h GSM_PICK_NONE
+
 _LIB = None
 
 # every function include/gsm_renderer.h and include/gsm_debug.h declare, with ctypes signature
@@ -248,6 +250,13 @@ _SIGNATURES = {
     "gsm_global_render_batch": ([C.c_void_p, C.c_void_p, C.POINTER(_GlobalView), C.c_uint32], C.c_int),
     "gsm_global_render_composite": ([C.c_void_p, C.c_void_p, C.POINTER(_GlobalObject), C.c_uint32, C.c_uint32,
                                      C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t], C.c_int),
+    "gsm_global_render_pick": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera), C.c_uint32,
+                                C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                C.c_size_t], C.c_int),
+    "gsm_global_render_composite_pick": ([C.c_void_p, C.c_void_p, C.POINTER(_GlobalObject), C.c_uint32, C.c_uint32,
+                                          C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                          C.c_size_t], C.c_int),
+    "gsm_global_pick_owner": ([C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int),
     "gsm_global_render_stereo": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera),
                                   C.POINTER(_Camera), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                   C.c_void_p, C.c_size_t], C.c_int),
@@ -520,6 +529,52 @@ class GlobalRenderer(_Renderer):
                 g.color_pitch_bytes = int(v.color_pitch) if v.color_pitch is not None else int(v.width) * self._bpp
                 g.depth_pitch_bytes = int(v.depth_pitch) if v.depth_pitch is not None else int(v.width) * 2
         _check(_lib().gsm_global_render_batch(self._h, _stream_handle(stream), arr, n), "gsm_global_render_batch")
+
+    def render_pick(self, color_texture, depth_texture, pick_texture, input: GaussianInput, camera: CameraParams,
+                    width: int, height: int, stream=None, color_pitch: Optional[int] = None,
+                    depth_pitch: Optional[int] = None, pick_pitch: Optional[int] = None):
+        """gsm_global_render_pick: `render` plus a pick target -- an int32 / uint32 tensor of shape (H, W), or
+        pitched -- that receives, per pixel, the gaussian id of the heaviest contribution (PICK_NONE: none)."""
+        inp = _Input(_ptr(input.gaussians), _ptr(input.harmonics), int(input.gaussian_count),
+                     int(input.sh_components))
+        cam = _camera_struct(camera)
+        cp = color_pitch if color_pitch is not None else int(width) * self._bpp
+        dp = depth_pitch if depth_pitch is not None else int(width) * 2
+        pp = pick_pitch if pick_pitch is not None else int(width) * 4
+        st = _lib().gsm_global_render_pick(self._h, _stream_handle(stream), C.byref(inp), C.byref(cam), int(width),
+                                           int(height), _ptr(color_texture), cp, _ptr(depth_texture), dp,
+                                           _ptr(pick_texture), pp)
+        _check(st, "gsm_global_render_pick")
+
+    def render_composite_pick(self, color_texture, depth_texture, pick_texture, objects, width: int, height: int,
+                              stream=None, color_pitch: Optional[int] = None, depth_pitch: Optional[int] = None,
+                              pick_pitch: Optional[int] = None):
+        """gsm_global_render_composite_pick: `render_composite` plus a pick target that receives, per pixel, the
+        composite's item of the heaviest contribution (pick_owner maps items to objects and gaussian ids)."""
+        n = 1 if objects is None else len(objects)
+        arr = None
+        if objects is not None:
+            arr = (_GlobalObject * max(n, 1))()
+            for g, o in zip(arr, objects):
+                g.input = _Input(_ptr(o.input.gaussians), _ptr(o.input.harmonics), int(o.input.gaussian_count),
+                                 int(o.input.sh_components))
+                g.camera = _camera_struct(o.camera)
+        cp = color_pitch if color_pitch is not None else int(width) * self._bpp
+        dp = depth_pitch if depth_pitch is not None else int(width) * 2
+        pp = pick_pitch if pick_pitch is not None else int(width) * 4
+        st = _lib().gsm_global_render_composite_pick(self._h, _stream_handle(stream), arr, n, int(width),
+                                                     int(height), _ptr(color_texture), cp, _ptr(depth_texture), dp,
+                                                     _ptr(pick_texture), pp)
+        _check(st, "gsm_global_render_composite_pick")
+
+    def pick_owner(self, items):
+        """gsm_global_pick_owner: items of the last enqueued pick frame (any integer array, host) ->
+        (objects, gaussians), uint32 arrays of its shape; PICK_NONE where an item names nothing."""
+        it = np.ascontiguousarray(np.asarray(items).astype(np.uint32, copy=False))
+        obj, gid = np.empty(it.shape, np.uint32), np.empty(it.shape, np.uint32)
+        st = _lib().gsm_global_pick_owner(self._h, it.ctypes.data, int(it.size), obj.ctypes.data, gid.ctypes.data)
+        _check(st, "gsm_global_pick_owner")
+        return obj, gid
 
     def render_composite(self, color_texture, depth_texture, objects, width: int, height: int, stream=None,
                          color_pitch: Optional[int] = None, depth_pitch: Optional[int] = None):

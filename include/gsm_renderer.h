@@ -268,6 +268,51 @@ gsm_status gsm_global_render_composite(gsm_renderer *renderer, void *stream,
                                        void *color, size_t color_pitch_bytes,
                                        void *depth_r16f, size_t depth_pitch_bytes);
 
+/* A per-pixel pick target (no reference analogue): gsm_global_render and
+ * gsm_global_render_composite with a third target that answers "which splat is under this pixel?".
+ *
+ * Colour and depth: their bytes equal those of the plain entry for the same arguments.
+ *
+ * Pick target: height rows of pick_pitch_bytes, one uint32_t per pixel.  Every pixel of width x height is
+ * written every frame (the caller does not clear it); bytes of a row past 4 * width are not touched.
+ *
+ * Pick value.  Walk the pixel's tile list front to back as the blend does.  For every entry the pixel's 4x2
+ * group blends -- reached before the group's saturation break, and not skipped because the group's eight
+ * alphas are all zero -- take the fp16 weight w = alpha * T, with T the pixel's transmittance before that
+ * entry.  The pick is the item of the heaviest w: the earliest entry wins ties, and a weight of zero or NaN
+ * never wins.  A pixel of an empty tile, or one that no entry reaches with w > 0, holds GSM_PICK_NONE.
+ *
+ * Items.  For gsm_global_render_pick the item is the gaussian id.  For gsm_global_render_composite_pick it is
+ * the item of the composite's layout, 256 * B_o + id (above); gsm_global_pick_owner maps it back.
+ *
+ * Checks: the plain entry's, in its order, with the pick target joining the rows it belongs to --
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  also: pick NULL;
+ *   GSM_ERR_INVALID_BUFFER_SIZE      also: pick_pitch_bytes < 4 * width, or the pointer or the pitch not
+ *                                    4-byte aligned;
+ *   GSM_ERR_UNSUPPORTED              (both entries, after every other check) the handle is restricted to tile
+ *                                    rows (gsm_global_set_tile_rows).
+ * Enqueue-only and capturable like the plain entries; nothing is allocated per frame.  gsm_global_render_views,
+ * gsm_global_render_batch, the DepthFirst and Local renderers and the multi-GPU frame have no pick entry. */
+#define GSM_PICK_NONE 0xFFFFFFFFu
+gsm_status gsm_global_render_pick(gsm_renderer *renderer, void *stream, const gsm_gaussian_input *input,
+                                  const gsm_camera_params *camera, uint32_t width, uint32_t height,
+                                  void *color, size_t color_pitch_bytes, void *depth_r16f,
+                                  size_t depth_pitch_bytes, void *pick_r32u, size_t pick_pitch_bytes);
+gsm_status gsm_global_render_composite_pick(gsm_renderer *renderer, void *stream,
+                                            const gsm_global_object *objects, uint32_t object_count,
+                                            uint32_t width, uint32_t height,
+                                            void *color, size_t color_pitch_bytes,
+                                            void *depth_r16f, size_t depth_pitch_bytes,
+                                            void *pick_r32u, size_t pick_pitch_bytes);
+
+/* Items of the handle's last enqueued pick frame -> (object index of that call, gaussian id within the
+ * object); after gsm_global_render_pick the object is 0.  Host work only: no device work, no sync (the items
+ * are the caller's copy of pick pixels).  GSM_PICK_NONE, an item at or past the frame's items and an item at
+ * or past its object's count give GSM_PICK_NONE in both outputs.  GSM_ERR_RENDER_FAILED when the handle's last
+ * enqueued frame was not a pick frame; GSM_ERR_INVALID_ARGUMENT for a NULL array with n > 0. */
+gsm_status gsm_global_pick_owner(gsm_renderer *renderer, const uint32_t *items, uint32_t n,
+                                 uint32_t *object, uint32_t *gaussian);
+
 /* GlobalRenderer.renderStereo (GlobalRenderer.swift:240-255) calls fatalError for
  * every target; this entry returns GSM_ERR_UNSUPPORTED instead. */
 gsm_status gsm_global_render_stereo(gsm_renderer *renderer, void *stream,
