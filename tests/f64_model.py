@@ -144,7 +144,19 @@ def rotation_from_quaternion(q):
     return np.eye(3)[None] + 2.0 * r[:, None, None] * K + 2.0 * (K @ K)  # Rodrigues, |q| = 1
 
 
-def project(world, harm, sh_components, cam, w, h, color_space=0, renderer="global"):
+def ink_margin(op, det, depth, near, far):
+    """Signed margin of the ink cull: opacity * 2 pi sqrt(det) against the threshold times the depth factor
+    (1 - saturate((0.02 far - depth) / (0.02 far - near))^2); no cull where the factor is zero."""
+    with np.errstate(all="ignore"):
+        ink = op * 2.0 * PI * np.sqrt(np.maximum(det, 1e-12))
+        far_adj = far * 0.02
+        depth_factor = 1.0 - np.clip((far_adj - depth) / (far_adj - near), 0.0, 1.0) ** 2
+        return np.where(depth_factor * TOTAL_INK_THRESHOLD > 0,
+                        ink / np.maximum(depth_factor * TOTAL_INK_THRESHOLD, 1e-300) - 1.0, 1.0)
+
+
+def project(world, harm, sh_components, cam, w, h, color_space=0, renderer="global", scene_transform=None,
+            sh_center=None):
     """Every gaussian of the scene through the reference's projection, in float64.
 
     Returns a dict of arrays over all n gaussians (culled ones included; their later fields may hold
@@ -153,10 +165,21 @@ def project(world, harm, sh_components, cam, w, h, color_space=0, renderer="glob
     A dx^2 + 2 B dx dy + C dy^2), color [n,3], opacity, extent [n,2], margins {name: signed distance to the
     cull threshold, positive = kept}, margin (their minimum), visible, repair.
     renderer: "global" culls on the screen rectangle; "local" culls past the far plane and on an empty
-    tile rectangle instead."""
+    tile rectangle instead; "depthfirst" maps ndc to the screen without the half-pixel shift and culls past
+    the far plane and on the screen rectangle (one eye of the DepthFirst frames).
+    scene_transform (column-major flat 4x4, scene -> world) moves the positions and multiplies the scales by
+    the length of its first column; its rotation does not turn the covariance and the SH direction is taken
+    from the untransformed position (both the reference's choices).  sh_center: the point the SH direction
+    is taken from, the camera position by default."""
     n = len(world)
     k = max(int(sh_components), 1)
     pos, scale, quat, op = unpack_world(world)
+    scene_pos, model_scale = pos, scale
+    if scene_transform is not None:
+        S = _mat(scene_transform)
+        pos = (np.concatenate([pos, np.ones((n, 1))], 1) @ S.T)[:, :3]
+        scale = scale * np.linalg.norm(S[:3, 0])
+    shift = 0.0 if renderer == "depthfirst" else 0.5
     V, P = _mat(cam["view"]), _mat(cam["proj"])
     near, far = float(cam["near"]), float(cam["far"])
     W, H = float(w), float(h)
@@ -166,7 +189,8 @@ def project(world, harm, sh_components, cam, w, h, color_space=0, renderer="glob
         depth = clip[:, 3]
         ndc = clip[:, :2] / depth[:, None]
         # pixel centres sit at integers: ndc -1 is the left edge of pixel 0, i.e. -0.5
-        mean = (ndc + 1.0) * 0.5 * np.array([W, H]) - 0.5
+        # (the DepthFirst frames leave the shift out: ndc -1 is coordinate 0)
+        mean = (ndc + 1.0) * 0.5 * np.array([W, H]) - shift
 
         R = rotation_from_quaternion(quat)
         cov3d = R @ (scale[:, :, None] ** 2 * np.transpose(R, (0, 2, 1)))
@@ -203,21 +227,19 @@ def project(world, harm, sh_components, cam, w, h, color_space=0, renderer="glob
             (lam2 * MAX_AXIS_RATIO ** 2 < lam1) | (det < 1e-8)
 
         m = {}
-        m["scale"] = scale.max(1) / MIN_SCALE - 1.0
+        m["scale"] = model_scale.max(1) / MIN_SCALE - 1.0  # (the scale as stored, before a scene transform)
         m["near"] = depth / near - 1.0
         m["alpha"] = op / ALPHA_THRESHOLD - 1.0
-        if renderer == "global":
-            radius = 3.0 * sigma[:, 0]
-        else:
+        if renderer == "local":
             radius = 3.0 * np.ceil(sigma[:, 0])
+        else:
+            radius = 3.0 * sigma[:, 0]
         m["radius"] = radius / MIN_RADIUS - 1.0
-        ink = op * 2.0 * PI * np.sqrt(np.maximum(det, 1e-12))
-        far_adj = far * 0.02
-        depth_factor = 1.0 - np.clip((far_adj - depth) / (far_adj - near), 0.0, 1.0) ** 2
-        m["ink"] = np.where(depth_factor * TOTAL_INK_THRESHOLD > 0,
-                            ink / np.maximum(depth_factor * TOTAL_INK_THRESHOLD, 1e-300) - 1.0, 1.0)
+        m["ink"] = ink_margin(op, det, depth, near, far)
         lo, hi = mean - extent, mean + extent
-        if renderer == "global":
+        if renderer == "depthfirst":
+            m["far"] = 1.0 - depth / far
+        if renderer in ("global", "depthfirst"):
             # kept while the rectangle reaches into [0, W] x [0, H]; in units of the frame's longer side
             m["screen"] = np.minimum(np.minimum(hi[:, 0], W - lo[:, 0]),
                                      np.minimum(hi[:, 1], H - lo[:, 1])) / max(W, H)
@@ -241,7 +263,8 @@ def project(world, harm, sh_components, cam, w, h, color_space=0, renderer="glob
         margin = np.min(np.stack(list(m.values()), 1), 1)
         visible = margin > 0.0
 
-        dirs = np.asarray(cam["position"], np.float64)[None] - pos
+        center = cam["position"] if sh_center is None else sh_center
+        dirs = np.asarray(center, np.float64)[None] - scene_pos
         dirs = dirs / np.linalg.norm(dirs, axis=1, keepdims=True)
         coef = unpack_harmonics(harm, n, k)
         if k == 1:
@@ -252,7 +275,7 @@ def project(world, harm, sh_components, cam, w, h, color_space=0, renderer="glob
         if color_space == 1:
             color = srgb_decode(color)
 
-    return dict(view=view4[:, :3], depth=depth, mean=mean, cov3d=cov3d, cov2d=np.stack([a, b, d], 1),
+    return dict(view=view4[:, :3], depth=depth, mean=mean, cov3d=cov3d, cov2d=np.stack([a, b, d], 1), det=det,
                 sigma=sigma, theta=theta, conic=conic, color=color, opacity=op, extent=extent,
                 margins=m, margin=margin, visible=visible, repair=repair)
 
@@ -316,14 +339,21 @@ def depth_order(depth, ids=None) -> np.ndarray:
 # ---------------------------------------------------------------------------------------------------
 # compositing
 # ---------------------------------------------------------------------------------------------------
-def _alphas(rec, ids, px, py, alpha_max):
-    """alpha [k, p] of gaussians ids at the pixels (px, py), exact exp."""
+def _power_terms(rec, ids, px, py):
+    """The three terms [k, p] of the quadratic form A dx^2 + 2 B dx dy + C dy^2 of gaussians ids at (px, py)."""
     dx = px[None, :] - rec["mean"][ids, 0][:, None]
     dy = py[None, :] - rec["mean"][ids, 1][:, None]
     A, B, C = (rec["conic"][ids, i][:, None] for i in range(3))
-    power = A * dx * dx + 2.0 * B * dx * dy + C * dy * dy
+    return A * dx * dx, 2.0 * B * dx * dy, C * dy * dy
+
+
+def _alphas(rec, ids, px, py, alpha_max, r2_max=None):
+    """alpha [k, p] of gaussians ids at the pixels (px, py), exact exp; zero where the quadratic form
+    exceeds r2_max, if one is given."""
+    power = sum(_power_terms(rec, ids, px, py))
     with np.errstate(over="ignore", invalid="ignore"):
-        return np.minimum(rec["opacity"][ids][:, None] * np.exp(-0.5 * power), alpha_max)
+        alpha = np.minimum(rec["opacity"][ids][:, None] * np.exp(-0.5 * power), alpha_max)
+    return alpha if r2_max is None else np.where(power > r2_max, 0.0, alpha)
 
 
 def _composite(rec, ids, alpha, live, rules):
@@ -351,11 +381,13 @@ def _composite(rec, ids, alpha, live, rules):
     return rgb, out_alpha, dep, unsure
 
 
-def blend_lists(records, lists, tile_w, tile_h, w, h, clear, rules) -> dict:
+def blend_lists(records, lists, tile_w, tile_h, w, h, clear, rules, on_tile=None) -> dict:
     """Front-to-back compositing of each tile's list.  lists: iterable of (tile index, gaussian ids in blend
     order); tiles are numbered row-major over ceil(w / tile_w) columns.  A pixel group (rules['group'], in
     pixels) stops before the first entry at which the largest transmittance among its pixels is below
-    rules['break_below'].  Pixels outside every listed tile hold `clear` (depth 0).
+    rules['break_below'].  Pixels outside every listed tile hold `clear` (depth 0).  rules['r2_max'], if
+    present, is the quadratic form beyond which alpha is zero.  on_tile(tile, ids, xs, ys, alpha, live) is
+    called for every non-empty list with the [entries, pixels] arrays of that tile.
     Returns color [h,w,3], alpha [h,w], depth [h,w], covered [h,w] (inside a listed tile) and depth_unsure."""
     tiles_x = (w + tile_w - 1) // tile_w
     color = np.empty((h, w, 3))
@@ -374,7 +406,7 @@ def blend_lists(records, lists, tile_w, tile_h, w, h, clear, rules) -> dict:
         if len(ids) == 0:
             continue
         # the shaders form pixel coordinates in half precision
-        a = _alphas(records, ids, round_h(xs), round_h(ys), rules["alpha_max"])
+        a = _alphas(records, ids, round_h(xs), round_h(ys), rules["alpha_max"], rules.get("r2_max"))
         T_before = np.ones_like(a)
         np.cumprod(1.0 - a[:-1], axis=0, out=T_before[1:])
         group = ((ys - y0) // gh) * (tile_w // gw) + (xs - x0) // gw
@@ -383,6 +415,8 @@ def blend_lists(records, lists, tile_w, tile_h, w, h, clear, rules) -> dict:
             gmax[:, g] = T_before[:, group == g].max(1)
         live = (gmax >= rules["break_below"])[:, group]
         # T is non-increasing, so `live` is a prefix of the list; entries past it do not change T
+        if on_tile is not None:
+            on_tile(tile, ids, xs, ys, a, live)
         rgb, al, dep, uns = _composite(records, ids, a, live, rules)
         inside = (xs < w) & (ys < h)
         color[ys[inside], xs[inside]] = rgb[inside]
