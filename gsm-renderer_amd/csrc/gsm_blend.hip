@@ -105,6 +105,32 @@ __device__ __forceinline__ void pick_update(h2& best, uint32_t (&pk)[2], h2 w, u
     }
 }
 
+// the occluded walk (k_blend_px_occ).  A pixel is closed from the first entry on whose fp16 depth
+// lies behind its limit Z: H(Z) < H(dep).  The depths the projection keeps are positive (clip.w > near_plane > 0),
+// so their fp16 bits order like their values, and the comparison becomes one on 16-bit integers: the pair's limits
+// are held as keys k with "open at dep" == bits(dep) < k --
+//   Z NaN: 0x7FFF (open at every depth);  Z >= +0 (inf included): bits(Z) + 1;  Z = -0: 1;  Z < 0: 0 (never open).
+// (A record of inf or NaN depth sends the unit to the exact rewalk, which compares in fp16: gsm_blend_exact.h.)
+__device__ __forceinline__ uint32_t occ_limit_key(uint32_t b) {
+    const uint32_t m = b & 0x7FFFu;
+    if (m > 0x7C00u) return 0x7FFFu;
+    if (b & 0x8000u) return m == 0u ? 1u : 0u;
+    return m + 1u;
+}
+__device__ __forceinline__ uint32_t occ_limit_keys(uint32_t z2) {
+    return occ_limit_key(z2 & 0xFFFFu) | (occ_limit_key(z2 >> 16) << 16);
+}
+// 0xFFFF in the half of every pixel of the pair that is open at the depth of the staged record word `bd`
+// (depth in its high half): v_pk_sub_i16 with the depth in both halves, v_pk_ashrrev_i16 by 15.  Both operands
+// lie in [0, 0x7FFF]: the difference cannot wrap.
+typedef short i16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t occ_open_mask(uint32_t bd, uint32_t keys) {
+    const i16x2 d = __builtin_bit_cast(i16x2, bd);
+    const i16x2 m = (i16x2{d.y, d.y} - __builtin_bit_cast(i16x2, keys)) >> i16x2{15, 15};
+    return __builtin_bit_cast(uint32_t, m);
+}
+
+#define GSM_BLEND_OCCLUDE 0
 #define GSM_BLEND_PICK 0
 #define GSM_BLEND_VIEWS 0
 #include "gsm_blend_px_body.h"
@@ -122,6 +148,12 @@ __device__ __forceinline__ void pick_update(h2& best, uint32_t (&pk)[2], h2 w, u
 #define GSM_BLEND_VIEWS 2
 #include "gsm_blend_px_body.h"
 #undef GSM_BLEND_VIEWS
+#undef GSM_BLEND_OCCLUDE
+#define GSM_BLEND_OCCLUDE 1
+#define GSM_BLEND_VIEWS 0
+#include "gsm_blend_px_body.h"
+#undef GSM_BLEND_VIEWS
+#undef GSM_BLEND_OCCLUDE
 #undef GSM_BLEND_PICK
 
 
@@ -155,7 +187,7 @@ static int blend_waves_per_wg(uint32_t numTiles, int numCUs) {
 int launch_blend(const FrameGeometry& g, const DeviceArena& A, void* color,
                   size_t colorPitch, void* depth, size_t depthPitch, int numCUs, bool costOrder, int colorFormat,
                   hipStream_t s, int wavesOverride, int claim, const MgArrive* arrive, bool pairs, void* pick,
-                  size_t pickPitch) {
+                  size_t pickPitch, const void* occluder, size_t occluderPitch, const uint32_t* sortedVals) {
     // local tile ids: tile t = k * tilesX + tx of the renderer's row k (pixel row rowBegin + k * rowStride)
     // (a batch of views: views * tilesPerView tiles, every rule below takes the batch's count)
     const uint32_t numTiles = frame_tiles(g);
@@ -203,6 +235,33 @@ int launch_blend(const FrameGeometry& g, const DeviceArena& A, void* color,
             else GSM_LAUNCH_BLEND_PICK(512, 2);
         }
 #undef GSM_LAUNCH_BLEND_PICK
+        return P == 1 ? GSM_BLEND_KERNEL_QUADRANT : GSM_BLEND_KERNEL_HALF_TILE;
+    }
+    // An occluded frame: the same units and the same rules, the walk cut at the occluder -- no
+    // compaction, no pair walk; whole frames of one GPU only.  It walks the tiles' whole sorted runs (sortedVals,
+    // the values with their skip flags), which the host makes the sort keep for such a frame.
+    if (occluder) {
+        if (!sortedVals) return 0;  // (the host passes them with every occluder)
+        const uint32_t ounits = numTiles * (4u / (uint32_t)P);
+        uint32_t ogrid = (ounits + (uint32_t)waves - 1) / (uint32_t)waves;
+        if (ogrid > (uint32_t)numCUs) ogrid = (uint32_t)numCUs;
+        const int oflags = flags | (((((uintptr_t)occluder) & 7u) == 0 && (occluderPitch & 7u) == 0) ? 16384 : 0);
+#define GSM_LAUNCH_BLEND_OCC(NTH, PP)                                                                                 \
+    hipLaunchKernelGGL((k_blend_px_occ<NTH, PP, false>), dim3(ogrid), dim3(NTH), 0, s, A.tileStart, A.rec,           \
+                       A.expTable, A.tileQueue, numTiles, g.tilesX, g.width, g.height, (uint8_t*)color, colorPitch,  \
+                       (uint8_t*)depth, depthPitch, (const uint8_t*)occluder, occluderPitch, oflags,                 \
+                       costOrder ? A.unitOrder : nullptr, A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1],    \
+                       A.halfCount, g.tileCount, A.costMax, sortedVals)
+        if (P == 1) {
+            if (waves == 16) GSM_LAUNCH_BLEND_OCC(1024, 1);
+            else if (waves == 12) GSM_LAUNCH_BLEND_OCC(768, 1);
+            else GSM_LAUNCH_BLEND_OCC(512, 1);
+        } else {
+            if (waves == 16) GSM_LAUNCH_BLEND_OCC(1024, 2);
+            else if (waves == 12) GSM_LAUNCH_BLEND_OCC(768, 2);
+            else GSM_LAUNCH_BLEND_OCC(512, 2);
+        }
+#undef GSM_LAUNCH_BLEND_OCC
         return P == 1 ? GSM_BLEND_KERNEL_QUADRANT : GSM_BLEND_KERNEL_HALF_TILE;
     }
     if (pairs && P == 2 && !arrive && waves == 16) {

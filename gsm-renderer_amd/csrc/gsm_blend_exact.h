@@ -48,10 +48,15 @@ __device__ __forceinline__ bool batch_depth_nonfinite(uint32_t recB) {
 // PICK (k_blend_px_pick): the walk also tracks, per pixel, the item (list value) of the heaviest
 // weight w = alpha * T among the entries the group blends -- the earliest on ties, never a zero or a NaN -- and
 // write takes the pair's two picks after D.  stI: the wave's 64-entry LDS stage of the items.
-template <int P, bool PICK = false, typename Write>
+// OCC (k_blend_px_occ): limits(px, py) gives the fp16 limits of a pixel pair (packed bits).  A pixel
+// is closed from the first entry on whose depth lies behind its limit, H(Z) < H(dep) -- fp16 compares, false for
+// a NaN on either side: its alpha is +0 from that entry on, and the group break takes its T as +0.  lst is then the
+// tile's whole sorted run (an entry a half list drops can still close a pixel), its values masked by idMask.
+template <int P, bool PICK = false, bool OCC = false, typename Write, typename Limits = int>
 __device__ __forceinline__ void walk_unit_exact(const uint32_t* __restrict__ lst, uint32_t count, const BlendRecord* __restrict__ rec,
                                 const uint16_t* tbl, uint4* stA, uint32_t* stB, uint32_t ux, uint32_t uy,
-                                uint32_t thrBits, Write&& write, uint32_t* stI = nullptr) {
+                                uint32_t thrBits, Write&& write, uint32_t* stI = nullptr, Limits limits = 0,
+                                uint32_t idMask = 0xFFFFFFFFu) {
     static_assert(P == 1 || P == 2, "quadrant or half-tile units");
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t offX, offY0, offY1;
@@ -83,11 +88,23 @@ __device__ __forceinline__ void walk_unit_exact(const uint32_t* __restrict__ lst
         best[q] = ZERO;
         pk[q][0] = pk[q][1] = 0xFFFFFFFFu;  // GSM_PICK_NONE
     }
+    xh2 Z[P];
+    uint32_t open[P];  // 0xFFFF in the half of every pixel that is not closed
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+        Z[q] = ZERO;
+        open[q] = 0xFFFFFFFFu;
+    }
+    if constexpr (OCC) {
+        Z[0] = x_h2(limits(ux + offX, uy + offY0));
+        if (P == 2) Z[P - 1] = x_h2(limits(ux + offX, uy + offY1));
+    }
     bool alive = true;
     const uint32_t last = count - 1u;
     const uint4 pad = make_uint4(x_u32(xh2{(xh1)(float)ux, (xh1)(float)uy}), 0u, 0u, 0u);
     for (uint32_t b0 = 0; b0 < count; b0 += 64u) {
-        const uint32_t gi = lst[min(b0 + lane, last)];
+        uint32_t gi = lst[min(b0 + lane, last)];
+        if constexpr (OCC) gi &= idMask;
         uint4 a = *(const uint4*)(rec + gi);
         uint32_t b = rec[gi].b;
         if (b0 + lane >= count) {
@@ -106,9 +123,10 @@ __device__ __forceinline__ void walk_unit_exact(const uint32_t* __restrict__ lst
         const uint32_t n = min(64u, count - b0);
         for (uint32_t j = 0; j < n; ++j) {
             // group break before the entry (GlobalShaders.metal:1086-1088): max T of the 4x2 group
-            xu16x2 tm = __builtin_bit_cast(xu16x2, T[0]);
+            xu16x2 tm = __builtin_bit_cast(xu16x2, OCC ? (x_u32(T[0]) & open[0]) : x_u32(T[0]));
 #pragma unroll
-            for (int q = 1; q < P; ++q) tm = __builtin_elementwise_max(tm, __builtin_bit_cast(xu16x2, T[q]));
+            for (int q = 1; q < P; ++q)
+                tm = __builtin_elementwise_max(tm, __builtin_bit_cast(xu16x2, OCC ? (x_u32(T[q]) & open[q]) : x_u32(T[q])));
             const uint32_t tb = __builtin_bit_cast(uint32_t, tm);
             uint32_t gm = max(tb & 0xFFFFu, tb >> 16);
             gm = x_dpp_max<0xB1>(gm);
@@ -138,6 +156,12 @@ __device__ __forceinline__ void walk_unit_exact(const uint32_t* __restrict__ lst
                 const xh2 ek = x_h2((uint32_t)tbl[pb & 0xFFFFu] | ((uint32_t)tbl[pb >> 16] << 16));
                 // a = min(opacity * exp(-0.5h * p), 0.99h) (GlobalShaders.metal:1124-1131)
                 ac[q] = __builtin_elementwise_min(x_hi(oc) * ek, C099);
+                if constexpr (OCC) {
+                    const xh1 dep = x_h2(bd).y;
+                    if (Z[q].x < dep) open[q] &= 0xFFFF0000u;
+                    if (Z[q].y < dep) open[q] &= 0x0000FFFFu;
+                    ac[q] = x_h2(x_u32(ac[q]) & open[q]);
+                }
                 om[q] = ONE - ac[q];
                 nz |= x_u32(ac[q]) & 0x7FFF7FFFu;
             }

@@ -11,6 +11,18 @@
 // tracks, per pixel, the item of its heaviest contribution w = alpha * T and writes it to a third target
 // (gsm_global_render_pick, gsm_global_render_composite_pick).  Whole frames on one GPU, quadrant
 // or half-tile units, no compaction.
+// A fifth time with GSM_BLEND_OCCLUDE 1 (GSM_BLEND_VIEWS 0, GSM_BLEND_PICK 0): k_blend_px_occ, the single frame's
+// walk cut, pixel by pixel, at the depth of an opaque surface the caller gives as a float image
+// (gsm_global_render_occluded, gsm_global_render_composite_occluded).  The same units as the pick
+// walk: whole frames on one GPU, no compaction.  It walks the tile's whole sorted run, not the half lists: an
+// entry that a half list drops (alpha 0 on the whole half) blends nothing, but it can close a pixel, and the
+// group break of the entries after it sees that pixel's transmittance as +0.
+#define GSM_BLEND_NOCOMPACT (GSM_BLEND_PICK || GSM_BLEND_OCCLUDE)
+#if GSM_BLEND_OCCLUDE
+#define GSM_LIST_ID(v) ((v) & kGidMask)  // the sorted run's values carry the half-tile skip flags
+#else
+#define GSM_LIST_ID(v) (v)
+#endif
 #if !GSM_BLEND_PICK
 #define GSM_PICK_PARAMS
 #define GSM_PICK_ARGS(q)
@@ -30,6 +42,37 @@ __global__ __launch_bounds__(NT) void k_blend_px_pick(
     static_assert(!COMPACT, "the pick walk keeps its unit layout");
     constexpr uint32_t tileBegin = 0, rowBegin = 0, rowStride = 1;  // whole frames on one GPU: no tile rows, no gather
     const MgArrive arrive{};
+#elif GSM_BLEND_OCCLUDE
+template <int NT, int P, bool COMPACT = false>
+__global__ __launch_bounds__(NT) void k_blend_px_occ(
+    const uint32_t* __restrict__ tileStart, const BlendRecord* __restrict__ rec,
+    const uint16_t* __restrict__ expTable, uint32_t* __restrict__ queue, uint32_t numTiles, uint32_t tilesX,
+    uint32_t W, uint32_t H, uint8_t* __restrict__ color, size_t colorPitch, uint8_t* __restrict__ depth,
+    size_t depthPitch, const uint8_t* __restrict__ occIn, size_t occPitch, int flags,
+    const uint32_t* __restrict__ order, uint16_t* __restrict__ unitCost, unsigned long long* __restrict__ trace,
+    const uint32_t* __restrict__ half0, const uint32_t* __restrict__ half1, const uint32_t* __restrict__ halfCount,
+    uint32_t tileCount, uint32_t* __restrict__ costMax, const uint32_t* __restrict__ sortedVals) {
+    static_assert(!COMPACT, "the occluded walk keeps its unit layout");
+    constexpr uint32_t tileBegin = 0, rowBegin = 0, rowStride = 1;  // whole frames on one GPU: no tile rows, no gather
+    const MgArrive arrive{};
+    // the limits of the pixel pair (px, py), (px + 1, py): the occluder's two floats as packed fp16 bits (one
+    // round-to-nearest-even conversion each, denormals kept); +inf for a pixel outside the frame, which is not
+    // read.  One 8-byte load where the occluder is aligned for it (flags bit 14; px is even).
+    auto load_limits = [&](uint32_t px, uint32_t py) -> uint32_t {
+        float z0 = __builtin_inff(), z1 = __builtin_inff();
+        if (py < H) {
+            const uint8_t* zrow = occIn + (size_t)py * occPitch + (size_t)px * 4;
+            if ((flags & 16384) && px + 1 < W) {
+                const float2 z = *(const float2*)zrow;
+                z0 = z.x;
+                z1 = z.y;
+            } else {
+                if (px < W) z0 = *(const float*)zrow;
+                if (px + 1 < W) z1 = *(const float*)(zrow + 4);
+            }
+        }
+        return as_u32(h2{(h1)z0, (h1)z1});
+    };
 #elif GSM_BLEND_VIEWS == 2
 // the blend of a batch of different views (gsm_global_render_batch): numTiles = the sum of the views' tiles
 template <int NT, int P, bool COMPACT = false>
@@ -84,7 +127,7 @@ __global__ __launch_bounds__(NT) void k_blend_px(
     constexpr uint32_t UNROLL = NG;
     const bool agePrio = (flags & 2) != 0;
     __shared__ __attribute__((aligned(16))) uint16_t tbl[65536];
-#if !GSM_BLEND_PICK
+#if !GSM_BLEND_NOCOMPACT
     __shared__ uint32_t cscr[NW][16];  // compaction: the alive groups of each wave, in order
 #endif
     __shared__ __attribute__((aligned(16))) uint4 lrecA[NW][64];  // current batch records
@@ -259,7 +302,11 @@ __global__ __launch_bounds__(NT) void k_blend_px(
         const uint32_t start = __builtin_amdgcn_readfirstlane(tileStart[tile]);
         const uint32_t full = __builtin_amdgcn_readfirstlane(tileStart[tile + 1]) - start;
         const uint32_t hsel = part & 1u;
+#if GSM_BLEND_OCCLUDE
+        const uint32_t count = full;  // (the tile's whole run, above)
+#else
         const uint32_t count = __builtin_amdgcn_readfirstlane(halfCount[hsel * tileCount + tile]);
+#endif
         unsigned long long tStart = 0;
         if (trace) tStart = __builtin_amdgcn_s_memrealtime();
         uint32_t nproc = 0;
@@ -294,11 +341,26 @@ __global__ __launch_bounds__(NT) void k_blend_px(
         // the unit met a record of inf / NaN fp16 depth: walked again exactly at its end (gsm_blend_exact.h)
         bool exactD = false;
         if (count > 0) {
+#if GSM_BLEND_OCCLUDE
+            // the pairs' limits, loaded once and held as packed keys (occ_limit_keys); Tm: T with the halves of the
+            // closed pixels zeroed, what the group break sees (nothing is closed before the first entry)
+            uint32_t zk[P], Tm[P];
+#pragma unroll
+            for (int k = 0; k < P; ++k) {
+                zk[k] = occ_limit_keys(load_limits(ux + offX[k], uy + offY[k]));
+                Tm[k] = as_u32(ONE);
+            }
+            uint32_t oc[U][P];  // the current group's open masks, per entry and pixel pair
+#endif
             h2 X[P], Yv;  // Yv: the lane's (up to) two rows
 #pragma unroll
             for (int k = 0; k < P; ++k) X[k] = h2{(h1)(float)(ux + offX[k]), (h1)(float)(ux + offX[k] + 1u)};
             Yv = h2{(h1)(float)(uy + offY[0]), (h1)(float)(uy + offY[P - 1])};
+#if GSM_BLEND_OCCLUDE
+            const uint32_t* lst = sortedVals + start;
+#else
             const uint32_t* lst = (hsel ? half1 : half0) + start;
+#endif
             // Batch registers: lane l of bA/bB holds list entry b0 + l, nA/nB entry b0 + 64 + l,
             // mA/mB entry b0 + 128 + l, nI the index of entry b0 + 192 + l.  Loads are
             // unpredicated (clamped index) and issued one batch ahead of their first use, so
@@ -308,16 +370,16 @@ __global__ __launch_bounds__(NT) void k_blend_px(
             // gives p = 0, alpha = 0 exactly, which leaves T, C and the break state unchanged.
             const uint32_t last = count - 1u;
             const uint4 pad = make_uint4(as_u32(h2{(h1)(float)ux, (h1)(float)uy}), 0u, 0u, 0u);
-            const uint32_t gi0 = lst[min(lane, last)];
-            const uint32_t gi1 = lst[min(64u + lane, last)];
-            const uint32_t gi2 = lst[min(128u + lane, last)];
+            const uint32_t gi0 = GSM_LIST_ID(lst[min(lane, last)]);
+            const uint32_t gi1 = GSM_LIST_ID(lst[min(64u + lane, last)]);
+            const uint32_t gi2 = GSM_LIST_ID(lst[min(128u + lane, last)]);
             uint4 bA = *(const uint4*)(rec + gi0);
             uint32_t bB = rec[gi0].b;
             uint4 nA = *(const uint4*)(rec + gi1);
             uint32_t nB = rec[gi1].b;
             uint4 mA = *(const uint4*)(rec + gi2);
             uint32_t mB = rec[gi2].b;
-            uint32_t nI = lst[min(192u + lane, last)];
+            uint32_t nI = GSM_LIST_ID(lst[min(192u + lane, last)]);
 #if GSM_BLEND_PICK
             uint32_t iN = gi1, iM = gi2;  // the items of batches nA and mA (lanes past the end: alpha 0, never picked)
             uint32_t itc[U], itn[U];
@@ -337,7 +399,7 @@ __global__ __launch_bounds__(NT) void k_blend_px(
             uint32_t rgc[U], bdc[U], rgn[U], bdn[U], opn[U];
             u16x2 en[U][P];  // next group's exp table words (d16 loads into both halves)
             bool alive = true;
-#if !GSM_BLEND_PICK
+#if !GSM_BLEND_NOCOMPACT
             uint32_t eC = 0, b0C = 0;  // compaction: next entry, its batch base
 #endif
             // p = ((dx*dx)*cxx + (dy*dy)*cyy) + (dx*dy)*cxy2 (GlobalShaders.metal:1115-1122);
@@ -379,6 +441,10 @@ __global__ __launch_bounds__(NT) void k_blend_px(
                 for (int q = 0; q < P; ++q) {
                     // a = min(opacity * exp(-0.5h * p), 0.99h) (GlobalShaders.metal:1124-1131)
                     ac[k][q] = __builtin_elementwise_min(splat_hi(as_h2(r2)) * lookup2(tbl, pq[q]), C099);
+#if GSM_BLEND_OCCLUDE
+                    oc[k][q] = occ_open_mask(bdc[k], zk[q]);
+                    ac[k][q] = as_h2(as_u32(ac[k][q]) & oc[k][q]);  // (a select: +0 whatever the alpha was)
+#endif
                     om[k][q] = ONE - ac[k][q];
                 }
             }
@@ -426,9 +492,15 @@ __global__ __launch_bounds__(NT) void k_blend_px(
                         // group break (GlobalShaders.metal:1086-1088): max T of the 4x2 group
                         // T >= 0, so the u16 bit patterns order like the values (v_pk_max_u16,
                         // no canonicalising of the fp16 inputs)
+#if GSM_BLEND_OCCLUDE
+                        u16x2 tm = __builtin_bit_cast(u16x2, Tm[0]);  // (a closed pixel counts as T = +0)
+#pragma unroll
+                        for (int q = 1; q < P; ++q) tm = __builtin_elementwise_max(tm, __builtin_bit_cast(u16x2, Tm[q]));
+#else
                         u16x2 tm = __builtin_bit_cast(u16x2, T[0]);
 #pragma unroll
                         for (int q = 1; q < P; ++q) tm = __builtin_elementwise_max(tm, __builtin_bit_cast(u16x2, T[q]));
+#endif
                         const uint32_t tb = __builtin_bit_cast(uint32_t, tm);
                         uint32_t gm = max(tb & 0xFFFFu, tb >> 16);
                         if (P == 1) gm = quad_max_u32(gm);
@@ -448,6 +520,9 @@ __global__ __launch_bounds__(NT) void k_blend_px(
                                 pick_update(best[q], pk[q], w, itc[k]);  // (T before this entry's update)
 #endif
                                 T[q] = T[q] * om[k][q];
+#if GSM_BLEND_OCCLUDE
+                                Tm[q] = as_u32(T[q]) & oc[k][q];  // (the list ascends in depth: closed stays closed)
+#endif
                                 R[q] = blend_acc(R[q], splat_lo(rgv), w);
                                 G[q] = blend_acc(G[q], splat_hi(rgv), w);
                                 B[q] = blend_acc(B[q], splat_lo(bdv), w);
@@ -463,7 +538,7 @@ __global__ __launch_bounds__(NT) void k_blend_px(
                             nproc = g1;
                             goto unit_done;
                         }
-#if !GSM_BLEND_PICK
+#if !GSM_BLEND_NOCOMPACT
                         // at most 16 of the 32 groups alive: continue them one pixel pair per lane
                         // (two 32-bit counts: a 64-bit popcount's compare goes to the VALU)
                         if (COMPACT && (uint32_t)__builtin_popcount((uint32_t)am & 0x55555555u) +
@@ -481,6 +556,12 @@ __global__ __launch_bounds__(NT) void k_blend_px(
                         for (int q = 0; q < P; ++q) {
                             const h2 ek = __builtin_bit_cast(h2, en[k][q]);
                             ac[k][q] = __builtin_elementwise_min(splat_hi(as_h2(opn[k])) * ek, C099);
+#if GSM_BLEND_OCCLUDE
+                            // the cut: the alpha of a pixel whose limit lies before this entry's depth becomes +0
+                            // (and its 1 - a below 1)
+                            oc[k][q] = occ_open_mask(bdn[k], zk[q]);
+                            ac[k][q] = as_h2(as_u32(ac[k][q]) & oc[k][q]);
+#endif
                             om[k][q] = ONE - ac[k][q];
                         }
                         rgc[k] = rgn[k];
@@ -508,9 +589,9 @@ __global__ __launch_bounds__(NT) void k_blend_px(
                 iN = iM;
                 iM = nI;
 #endif
-                nI = lst[min(b0 + 256u + lane, last)];
+                nI = GSM_LIST_ID(lst[min(b0 + 256u + lane, last)]);
             }
-#if !GSM_BLEND_PICK
+#if !GSM_BLEND_NOCOMPACT
         compact_phase:
             if constexpr (COMPACT) {
                 // Groups that broke keep their pixels: written now, in the half-tile layout.
@@ -658,11 +739,14 @@ __global__ __launch_bounds__(NT) void k_blend_px(
 #pragma unroll
         for (int q = 0; q < P; ++q)
             write_pair(ux + offX[q], uy + offY[q], (full > 0) ? (ONE - T[q]) : ONE, R[q], G[q], B[q], D[q] GSM_PICK_ARGS(q));
-#if !GSM_BLEND_PICK
+#if !GSM_BLEND_NOCOMPACT
     unit_end:
 #endif
         if (exactD)  // (rare: a record of inf / NaN fp16 depth; every pixel of the unit is written again)
-#if GSM_BLEND_PICK
+#if GSM_BLEND_OCCLUDE
+            blend_exact::walk_unit_exact<P, false, true>(sortedVals + start, count, rec, tbl, lrecA[wv], lrecB[wv], ux,
+                                                         uy, thrBits, write_pair, nullptr, load_limits, kGidMask);
+#elif GSM_BLEND_PICK
             blend_exact::walk_unit_exact<P, true>((hsel ? half1 : half0) + start, count, rec, tbl, lrecA[wv], lrecB[wv],
                                                   ux, uy, thrBits, write_pair, litem[wv]);
 #else
@@ -702,3 +786,5 @@ __global__ __launch_bounds__(NT) void k_blend_px(
 }
 #undef GSM_PICK_PARAMS
 #undef GSM_PICK_ARGS
+#undef GSM_BLEND_NOCOMPACT
+#undef GSM_LIST_ID

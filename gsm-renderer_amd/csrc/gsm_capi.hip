@@ -121,6 +121,24 @@ gsm_status gsm_global_render_composite_pick(gsm_renderer* r, void* stream, const
                                         color_pitch, depth, depth_pitch, pick, pick_pitch);
 }
 
+gsm_status gsm_global_render_occluded(gsm_renderer* r, void* stream, const gsm_gaussian_input* input,
+                                      const gsm_camera_params* camera, uint32_t width, uint32_t height, void* color,
+                                      size_t color_pitch, void* depth, size_t depth_pitch, const void* occluder,
+                                      size_t occluder_pitch) {
+    if (!r || !r->impl || !input || !camera) return GSM_ERR_INVALID_ARGUMENT;
+    return r->impl->renderOccluded((hipStream_t)stream, *input, *camera, width, height, color, color_pitch, depth,
+                                   depth_pitch, occluder, occluder_pitch);
+}
+
+gsm_status gsm_global_render_composite_occluded(gsm_renderer* r, void* stream, const gsm_global_object* objects,
+                                                uint32_t object_count, uint32_t width, uint32_t height, void* color,
+                                                size_t color_pitch, void* depth, size_t depth_pitch,
+                                                const void* occluder, size_t occluder_pitch) {
+    if (!r || !r->impl) return GSM_ERR_INVALID_ARGUMENT;
+    return r->impl->renderCompositeOccluded((hipStream_t)stream, objects, object_count, width, height, color,
+                                            color_pitch, depth, depth_pitch, occluder, occluder_pitch);
+}
+
 gsm_status gsm_global_pick_owner(gsm_renderer* r, const uint32_t* items, uint32_t n, uint32_t* object,
                                  uint32_t* gaussian) {
     if (!r || !r->impl || (n > 0 && (!items || !object || !gaussian))) return GSM_ERR_INVALID_ARGUMENT;

@@ -107,10 +107,17 @@ struct PickTarget {
     void* pixels;
     size_t pitch;
 };
+// occluder (nullable): an occluded frame's depth image (one float per pixel, read only, required like colour); it
+// joins the same two rows.
+struct OccluderSource {
+    const void* pixels;
+    size_t pitch;
+};
 gsm_status validate_frame(const gsm_renderer_config& cfg, uint32_t maxGaussians, uint32_t maxWidth,
                           uint32_t maxHeight, uint32_t count, bool allowEmpty, bool inputMissing, uint32_t width,
                           uint32_t height, const void* color, size_t colorPitch, uint32_t widthFactor,
-                          const void* depth, size_t depthPitch, const PickTarget* pick = nullptr);
+                          const void* depth, size_t depthPitch, const PickTarget* pick = nullptr,
+                          const OccluderSource* occluder = nullptr);
 
 // The per-frame terms of projectCovariance2D (GaussianShared.h:340-355), the same fp32 operations
 // in the same order as the reference repeats per gaussian: part of the numeric contract.

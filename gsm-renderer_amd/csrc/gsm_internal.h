@@ -429,11 +429,15 @@ void launch_headers(const uint32_t* sortedKeys, const FrameGeometry& geo, const 
 // launched (gsm_blend_kernel, include/gsm_debug.h; 0 for an empty frame)
 // pick (nullable): a pick frame's third target, one uint32_t per pixel (k_blend_px_pick) -- a
 // single frame or a composite over the handle's whole tile grid
+// occluder (nullable, not together with pick): an occluded frame's depth image, one float per pixel
+// (k_blend_px_occ) -- the same frames; sortedVals: the frame's sorted values, which that walk reads
+// in place of the half-tile lists
 int launch_blend(const FrameGeometry& geo, const DeviceArena& A,
                   void* color, size_t colorPitch, void* depth, size_t depthPitch, int numCUs,
                   bool costOrder, int colorFormat, hipStream_t stream, int waves = 0, int claim = 1,
                   const MgArrive* arrive = nullptr, bool pairs = false, void* pick = nullptr,
-                  size_t pickPitch = 0);
+                  size_t pickPitch = 0, const void* occluder = nullptr, size_t occluderPitch = 0,
+                  const uint32_t* sortedVals = nullptr);
 // k_blend_pw (gsm_blend_pw.hip): two half-tile units per wave, one GPU's frame
 void launch_blend_pw(const FrameGeometry& g, const DeviceArena& A, void* color, size_t colorPitch, void* depth,
                      size_t depthPitch, int numCUs, bool costOrder, int colorFormat, hipStream_t s, int waves);

@@ -175,9 +175,10 @@ ProjectArgs GlobalRenderer::frameArgs(const gsm_camera_params& camp, uint32_t wi
 
 gsm_status GlobalRenderer::validateFrame(uint32_t count, bool inputMissing, uint32_t width, uint32_t height,
                                          const void* color, size_t colorPitch, const void* depth,
-                                         size_t depthPitch, const PickTarget* pick) const {
+                                         size_t depthPitch, const PickTarget* pick,
+                                         const OccluderSource* occluder) const {
     const gsm_status st = validate_frame(config_, maxGaussians_, maxWidth_, maxHeight_, count, true, inputMissing,
-                                         width, height, color, colorPitch, 1, depth, depthPitch, pick);
+                                         width, height, color, colorPitch, 1, depth, depthPitch, pick, occluder);
     if (st != GSM_OK) return st;
     if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
     return GSM_OK;
@@ -201,6 +202,22 @@ gsm_status GlobalRenderer::renderCompositePick(hipStream_t s, const gsm_global_o
                                                void* depth, size_t depthPitch, void* pick, size_t pickPitch) {
     const PickTarget pt{pick, pickPitch};
     return composeFrame(s, objects, objectCount, width, height, color, colorPitch, depth, depthPitch, &pt);
+}
+
+gsm_status GlobalRenderer::renderOccluded(hipStream_t s, const gsm_gaussian_input& in, const gsm_camera_params& camp,
+                                          uint32_t width, uint32_t height, void* color, size_t colorPitch,
+                                          void* depth, size_t depthPitch, const void* occluder,
+                                          size_t occluderPitch) {
+    const OccluderSource os{occluder, occluderPitch};
+    return renderFrame(s, in, camp, width, height, color, colorPitch, depth, depthPitch, nullptr, &os);
+}
+
+gsm_status GlobalRenderer::renderCompositeOccluded(hipStream_t s, const gsm_global_object* objects,
+                                                   uint32_t objectCount, uint32_t width, uint32_t height, void* color,
+                                                   size_t colorPitch, void* depth, size_t depthPitch,
+                                                   const void* occluder, size_t occluderPitch) {
+    const OccluderSource os{occluder, occluderPitch};
+    return composeFrame(s, objects, objectCount, width, height, color, colorPitch, depth, depthPitch, nullptr, &os);
 }
 
 gsm_status GlobalRenderer::pickOwner(const uint32_t* items, uint32_t n, uint32_t* object, uint32_t* gaussian) const {
@@ -236,11 +253,12 @@ gsm_status GlobalRenderer::pickOwner(const uint32_t* items, uint32_t n, uint32_t
 
 gsm_status GlobalRenderer::renderFrame(hipStream_t s, const gsm_gaussian_input& in, const gsm_camera_params& camp,
                                        uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                                       size_t depthPitch, const PickTarget* pick) {
+                                       size_t depthPitch, const PickTarget* pick, const OccluderSource* occluder) {
     gsm_status st = validateFrame(in.gaussian_count, !in.gaussians || !in.harmonics, width, height, color,
-                                  colorPitch, depth, depthPitch, pick);
+                                  colorPitch, depth, depthPitch, pick, occluder);
     if (st != GSM_OK) return st;
-    if (pick && tileRowsRestricted()) return GSM_ERR_UNSUPPORTED;  // (set_tile_rows: a pick frame is a whole frame)
+    // (set_tile_rows: a pick frame and an occluded frame are whole frames)
+    if ((pick || occluder) && tileRowsRestricted()) return GSM_ERR_UNSUPPORTED;
     // the projection's tile tests walk contiguous rows; interleaved row sets come from the records
     // path only (gsm_multigpu)
     if (rowStride_ != 1) return GSM_ERR_INVALID_ARGUMENT;
@@ -250,7 +268,7 @@ gsm_status GlobalRenderer::renderFrame(hipStream_t s, const gsm_gaussian_input& 
     return runFrame(s, a, width, height, color, colorPitch, depth, depthPitch,
                     [&](const ProjectArgs& pa) {
                         launch_project(half, deg, in.gaussians, in.harmonics, pa, arena_, s);
-                    }, nullptr, false, nullptr, nullptr, pick);
+                    }, nullptr, false, nullptr, nullptr, pick, occluder);
 }
 
 uint32_t GlobalRenderer::tiles_of(uint32_t width, uint32_t height) {
@@ -478,7 +496,7 @@ gsm_status GlobalRenderer::renderComposite(hipStream_t s, const gsm_global_objec
 
 gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* objects, uint32_t objectCount,
                                         uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                                        size_t depthPitch, const PickTarget* pick) {
+                                        size_t depthPitch, const PickTarget* pick, const OccluderSource* occluder) {
     // Every check before anything is enqueued, one kind of check after another over all objects (the first
     // failing kind decides, within it the lowest object): counts, dimensions, missing buffers, sizes,
     // sh_components, tile rows.  (The counts of a NULL array cannot be read: that is the missing buffer.)
@@ -495,7 +513,7 @@ gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* 
     }
     if (items > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;  // (the values keep 30 bits of item)
     if (!frameSizeOk(width, height)) return GSM_ERR_INVALID_DIMENSIONS;
-    if (!color || (pick && !pick->pixels)) return GSM_ERR_MISSING_REQUIRED_BUFFER;
+    if (!color || (pick && !pick->pixels) || (occluder && !occluder->pixels)) return GSM_ERR_MISSING_REQUIRED_BUFFER;
     for (uint32_t o = 0; o < objectCount; ++o) {
         const gsm_gaussian_input& in = objects[o].input;
         if (in.gaussian_count > 0 && (!in.gaussians || !in.harmonics)) return GSM_ERR_MISSING_REQUIRED_BUFFER;
@@ -503,7 +521,7 @@ gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* 
     }
     // (everything above passed: what is left of validate_frame is the pitches and the alignment)
     gsm_status st = validate_frame(config_, maxGaussians_, maxWidth_, maxHeight_, countSum, true, false, width, height,
-                                   color, colorPitch, 1, depth, depthPitch, pick);
+                                   color, colorPitch, 1, depth, depthPitch, pick, occluder);
     if (st != GSM_OK) return st;
     for (uint32_t o = 1; o < objectCount; ++o)
         if (objects[o].input.sh_components != objects[0].input.sh_components) return GSM_ERR_INVALID_ARGUMENT;
@@ -575,7 +593,7 @@ gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* 
     const bool half = config_.precision == GSM_PRECISION_FLOAT16;
     return runFrame(s, a, width, height, color, colorPitch, depth, depthPitch,
                     [&](const ProjectArgs& pa) { launch_project_compose(half, deg, pa, vf.compose, arena_, s); },
-                    nullptr, false, nullptr, &vf, pick);
+                    nullptr, false, nullptr, &vf, pick, occluder);
 }
 
 gsm_status GlobalRenderer::renderRecords(hipStream_t s, const void* records, uint32_t count, uint32_t width,
@@ -713,7 +731,7 @@ gsm_status GlobalRenderer::partitionPush(hipStream_t s, uint32_t world, uint32_t
 }
 
 uint32_t GlobalRenderer::scheduleUnits(hipStream_t s, uint32_t width, uint32_t height, uint32_t views,
-                                       uint32_t batchTiles, bool compose, bool pick) {
+                                       uint32_t batchTiles, bool compose, bool pick, bool occluded) {
     // (a batch of views: the units of views * tiles(width, height) tiles; the view count is part of the key, so
     // a batch neither inherits nor leaves behind a single frame's costs.  A batch of different views: the units
     // of its batchTiles tiles, keyed by its whole signature batchSig_, compared word for word)
@@ -728,8 +746,9 @@ uint32_t GlobalRenderer::scheduleUnits(hipStream_t s, uint32_t width, uint32_t h
     const bool isBatch = batchTiles != 0;
     // (a pick frame walks without compaction or pairs: its costs are its own, either way round)
     bool changed = isBatch != schedBatch_ || compose != schedCompose_ || key != schedKey_ || views != schedViews_ ||
-                   pick != schedPick_;
+                   pick != schedPick_ || occluded != schedOccluded_;
     schedPick_ = pick;
+    schedOccluded_ = occluded;  // (an occluded frame's walks end at the occluder: its costs are its own as well)
     if (compose && !changed) changed = composeSig_ != schedComposeSig_;
     if (compose && changed) schedComposeSig_.assign(composeSig_.begin(), composeSig_.end());  // (reserved: no allocation)
     schedCompose_ = compose;
@@ -752,7 +771,8 @@ template <class Front>
 gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_t width, uint32_t height,
                                     void* color, size_t colorPitch, void* depth, size_t depthPitch,
                                     Front&& front, const uint32_t* devCount, bool preOrdered,
-                                    const MgArrive* blendArrive, const ViewFrame* views, const PickTarget* pick) {
+                                    const MgArrive* blendArrive, const ViewFrame* views, const PickTarget* pick,
+                                    const OccluderSource* occluder) {
     (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's: the launches below are checked)
     const int profiling = timer_.flags();
     const bool keep = (profiling & 2) != 0;
@@ -784,7 +804,8 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     // the multi-GPU frame orders them earlier, in its partition projection: preOrdered).
     const uint32_t units = preOrdered ? 0u
                                       : scheduleUnits(s, width, height, batch ? batch->views : views ? views->batch.views : 0u,
-                                                      batch ? batch->tiles : 0u, comp != nullptr, pick != nullptr);
+                                                      batch ? batch->tiles : 0u, comp != nullptr, pick != nullptr,
+                                                      occluder != nullptr);
     const bool costOrder = preOrdered ? tuning_.costOrder : units > 0;
     fa.schedUnits = units;
     // (written on every scheduled frame: the blend's remaining-walk priorities read the longest walk too)
@@ -843,6 +864,9 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     // stably by depth by one wave in LDS -- the same order as the reference's 4-pass sort of
     // (tile << 16 | depth) keys.  Tuning::fullRadix keeps the 4 full 8-bit passes (A/B).
     const bool fullRadix = tuning_.fullRadix;
+    // an occluded frame's blend walks the tiles' whole sorted runs: the tile sort writes them out
+    // as it does for a captured frame
+    const uint32_t* blendRun = nullptr;
     const bool ballot = tuning_.ballotRank;
     if (!fullRadix) {
         // the last tile pass also writes the tile starts (radix_sort_tiles: no pass over the keys); the
@@ -855,9 +879,10 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
         if (res == kSortNoSpace) return GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;  // (nothing of the sort launched)
         tile_depth_sort(kb[res], vb[res], kb[res ^ 1], vb[res ^ 1], arena_.tileStart, 0u, localTiles, s, ballot,
                         arena_.halfVals[0], arena_.halfVals[1],
-                        arena_.halfCount, tileCount_, capture, dev_.numCUs);
+                        arena_.halfCount, tileCount_, capture || occluder, dev_.numCUs);
         sortedKeys_ = capture ? kb[res ^ 1] : nullptr;
         sortedVals_ = capture ? vb[res ^ 1] : nullptr;
+        blendRun = occluder ? vb[res ^ 1] : nullptr;
     } else {
         const int res = radix_sort_pairs(kb, vb, &arena_.header->totalAssignments, maxAssignments_, 0,
                                          sortPassCount(), sort_space(arena_), s, ballot,
@@ -865,6 +890,7 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
         if (res == kSortNoSpace) return GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;
         sortedKeys_ = kb[res];
         sortedVals_ = vb[res];
+        blendRun = vb[res];
     }
     unsortedKeys_ = keep ? arena_.keysKeep : nullptr;
     unsortedVals_ = keep ? arena_.valsKeep : nullptr;
@@ -879,7 +905,8 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     timer_.record(5, s, true);
     lastBlendKernel_ = launch_blend(g, arena_, color, colorPitch, depth, depthPitch, dev_.numCUs, costOrder,
                  (int)config_.color_format, s, tuning_.blendWaves, tuning_.blendClaim, blendArrive,
-                 tuning_.blendPairs, pick ? pick->pixels : nullptr, pick ? pick->pitch : 0);
+                 tuning_.blendPairs, pick ? pick->pixels : nullptr, pick ? pick->pitch : 0,
+                 occluder ? occluder->pixels : nullptr, occluder ? occluder->pitch : 0, blendRun);
     timer_.record(6, s, true);
     timer_.frameDone();
     if (hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;

@@ -45,6 +45,14 @@ class GlobalRenderer {
     gsm_status renderCompositePick(hipStream_t stream, const gsm_global_object* objects, uint32_t objectCount,
                                    uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
                                    size_t depthPitch, void* pick, size_t pickPitch);
+    // render / renderComposite cut, pixel by pixel, at the depth of an opaque surface: one float per pixel, read
+    // only (gsm_global_render_occluded, gsm_global_render_composite_occluded)
+    gsm_status renderOccluded(hipStream_t stream, const gsm_gaussian_input& input, const gsm_camera_params& camera,
+                              uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
+                              size_t depthPitch, const void* occluder, size_t occluderPitch);
+    gsm_status renderCompositeOccluded(hipStream_t stream, const gsm_global_object* objects, uint32_t objectCount,
+                                       uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
+                                       size_t depthPitch, const void* occluder, size_t occluderPitch);
     // items of the last enqueued pick frame -> (object of the call, gaussian id within it); host only, no sync
     gsm_status pickOwner(const uint32_t* items, uint32_t n, uint32_t* object, uint32_t* gaussian) const;
 
@@ -75,7 +83,7 @@ class GlobalRenderer {
     // what renderRecords / the multi-GPU frame would refuse, checked before anything is enqueued
     gsm_status validateFrame(uint32_t count, bool inputMissing, uint32_t width, uint32_t height,
                              const void* color, size_t colorPitch, const void* depth, size_t depthPitch,
-                             const PickTarget* pick = nullptr) const;
+                             const PickTarget* pick = nullptr, const OccluderSource* occluder = nullptr) const;
     // the partition buffers (allocated lazily by the first partition frame; the multi-GPU frame
     // allocates them at prepare so that no frame can fail on an allocation)
     gsm_status ensurePartitionBuffers(uint32_t numSlabs);
@@ -111,13 +119,14 @@ class GlobalRenderer {
 
    private:
     GlobalRenderer() = default;
-    // render and renderPick, renderComposite and renderCompositePick (pick: null for the plain entries)
+    // render, renderPick and renderOccluded; renderComposite, renderCompositePick and renderCompositeOccluded
+    // (pick, occluder: null for the plain entries, never both)
     gsm_status renderFrame(hipStream_t stream, const gsm_gaussian_input& input, const gsm_camera_params& camera,
                            uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                           size_t depthPitch, const PickTarget* pick);
+                           size_t depthPitch, const PickTarget* pick, const OccluderSource* occluder = nullptr);
     gsm_status composeFrame(hipStream_t stream, const gsm_global_object* objects, uint32_t objectCount,
                             uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                            size_t depthPitch, const PickTarget* pick);
+                            size_t depthPitch, const PickTarget* pick, const OccluderSource* occluder = nullptr);
     ProjectArgs frameArgs(const gsm_camera_params& camera, uint32_t width, uint32_t height, uint32_t count,
                           uint32_t shComponents) const;
     // scan, scatter, sort, headers and blend after `front` filled the per-gaussian arrays
@@ -135,7 +144,7 @@ class GlobalRenderer {
                         size_t colorPitch, void* depth, size_t depthPitch, Front&& front,
                         const uint32_t* devCount = nullptr, bool preOrdered = false,
                         const MgArrive* blendArrive = nullptr, const ViewFrame* views = nullptr,
-                        const PickTarget* pick = nullptr);
+                        const PickTarget* pick = nullptr, const OccluderSource* occluder = nullptr);
     // the blend schedule's unit count for the current rows, or for a batch of `views` frames (0 when cost
     // order is off), its cost arrays cleared when the geometry or the view count changed
     // (batchTiles > 0: a batch of different views, keyed by its signature batchSig_ -- the view count and every
@@ -143,8 +152,9 @@ class GlobalRenderer {
     // (compose: a composite, on the single frame's units, keyed by its signature composeSig_ -- the size, the
     // object count and every object's count)
     // (pick: a pick frame -- part of the key, so it neither inherits walk costs from a plain frame nor leaves any)
+    // (occluded: an occluded frame -- part of the key in the same way)
     uint32_t scheduleUnits(hipStream_t s, uint32_t width, uint32_t height, uint32_t views = 0,
-                           uint32_t batchTiles = 0, bool compose = false, bool pick = false);
+                           uint32_t batchTiles = 0, bool compose = false, bool pick = false, bool occluded = false);
     static uint32_t tiles_of(uint32_t width, uint32_t height);  // tiles of a width x height frame
     // checks and arguments renderViews and renderBatch share: a view's size within the handle's, a batch's
     // tiles within its tile space and the key's 16-bit field, no set_tile_rows restriction, and the
@@ -209,6 +219,7 @@ class GlobalRenderer {
     std::vector<uint32_t> schedComposeSig_;   // the signature the unit costs belong to (schedCompose_)
     bool schedCompose_ = false;               // the unit costs belong to a composite
     bool schedPick_ = false;                  // the unit costs belong to a pick frame
+    bool schedOccluded_ = false;              // the unit costs belong to an occluded frame
     std::vector<uint32_t> composeObject_;     // the call's object index of every entry of composeHost_
     bool lastPick_ = false;                   // the last enqueued frame was a pick frame (pickOwner)
     bool lastPickComposite_ = false;          // ... of a composite: its owners are composeHost_ / composeObject_

@@ -256,6 +256,12 @@ _SIGNATURES = {
     "gsm_global_render_composite_pick": ([C.c_void_p, C.c_void_p, C.POINTER(_GlobalObject), C.c_uint32, C.c_uint32,
                                           C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                           C.c_size_t], C.c_int),
+    "gsm_global_render_occluded": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera), C.c_uint32,
+                                    C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                    C.c_size_t], C.c_int),
+    "gsm_global_render_composite_occluded": ([C.c_void_p, C.c_void_p, C.POINTER(_GlobalObject), C.c_uint32,
+                                              C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                              C.c_size_t, C.c_void_p, C.c_size_t], C.c_int),
     "gsm_global_pick_owner": ([C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int),
     "gsm_global_render_stereo": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera),
                                   C.POINTER(_Camera), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
@@ -473,6 +479,20 @@ class _Renderer:
         return raw[:n]
 
 
+def _object_array(objects):
+    """(gsm_global_object array, count) of a SceneObject list, for the composite entries; (None, 1) for None (a
+    NULL array, which the library refuses)."""
+    if objects is None:
+        return None, 1
+    n = len(objects)
+    arr = (_GlobalObject * max(n, 1))()
+    for g, o in zip(arr, objects):
+        g.input = _Input(_ptr(o.input.gaussians), _ptr(o.input.harmonics), int(o.input.gaussian_count),
+                         int(o.input.sh_components))
+        g.camera = _camera_struct(o.camera)
+    return arr, n
+
+
 class GlobalRenderer(_Renderer):
     """GlobalRenderer (GlobalRenderer.swift:72-572) on one HIP device."""
     _PREFIX, _STAGE_NAMES, _COUNTERS = "gsm_global", STAGES, _Counters
@@ -551,14 +571,7 @@ class GlobalRenderer(_Renderer):
                               pick_pitch: Optional[int] = None):
         """gsm_global_render_composite_pick: `render_composite` plus a pick target that receives, per pixel, the
         composite's item of the heaviest contribution (pick_owner maps items to objects and gaussian ids)."""
-        n = 1 if objects is None else len(objects)
-        arr = None
-        if objects is not None:
-            arr = (_GlobalObject * max(n, 1))()
-            for g, o in zip(arr, objects):
-                g.input = _Input(_ptr(o.input.gaussians), _ptr(o.input.harmonics), int(o.input.gaussian_count),
-                                 int(o.input.sh_components))
-                g.camera = _camera_struct(o.camera)
+        arr, n = _object_array(objects)
         cp = color_pitch if color_pitch is not None else int(width) * self._bpp
         dp = depth_pitch if depth_pitch is not None else int(width) * 2
         pp = pick_pitch if pick_pitch is not None else int(width) * 4
@@ -566,6 +579,36 @@ class GlobalRenderer(_Renderer):
                                                      int(height), _ptr(color_texture), cp, _ptr(depth_texture), dp,
                                                      _ptr(pick_texture), pp)
         _check(st, "gsm_global_render_composite_pick")
+
+    def render_occluded(self, color_texture, depth_texture, occluder, input: GaussianInput, camera: CameraParams,
+                        width: int, height: int, stream=None, color_pitch: Optional[int] = None,
+                        depth_pitch: Optional[int] = None, occluder_pitch: Optional[int] = None):
+        """gsm_global_render_occluded: `render` cut at an opaque surface -- `occluder` is a float32 CUDA tensor of
+        shape (H, W), or pitched, holding the surface's view-space depth (clip.w) per pixel; +inf occludes nothing."""
+        inp = _Input(_ptr(input.gaussians), _ptr(input.harmonics), int(input.gaussian_count),
+                     int(input.sh_components))
+        cam = _camera_struct(camera)
+        cp = color_pitch if color_pitch is not None else int(width) * self._bpp
+        dp = depth_pitch if depth_pitch is not None else int(width) * 2
+        op = occluder_pitch if occluder_pitch is not None else int(width) * 4
+        st = _lib().gsm_global_render_occluded(self._h, _stream_handle(stream), C.byref(inp), C.byref(cam),
+                                               int(width), int(height), _ptr(color_texture), cp,
+                                               _ptr(depth_texture), dp, _ptr(occluder), op)
+        _check(st, "gsm_global_render_occluded")
+
+    def render_composite_occluded(self, color_texture, depth_texture, occluder, objects, width: int, height: int,
+                                  stream=None, color_pitch: Optional[int] = None, depth_pitch: Optional[int] = None,
+                                  occluder_pitch: Optional[int] = None):
+        """gsm_global_render_composite_occluded: `render_composite` cut at the same kind of occluder, in the depth
+        unit of the composite's shared projection."""
+        arr, n = _object_array(objects)
+        cp = color_pitch if color_pitch is not None else int(width) * self._bpp
+        dp = depth_pitch if depth_pitch is not None else int(width) * 2
+        op = occluder_pitch if occluder_pitch is not None else int(width) * 4
+        st = _lib().gsm_global_render_composite_occluded(self._h, _stream_handle(stream), arr, n, int(width),
+                                                         int(height), _ptr(color_texture), cp, _ptr(depth_texture),
+                                                         dp, _ptr(occluder), op)
+        _check(st, "gsm_global_render_composite_occluded")
 
     def pick_owner(self, items):
         """gsm_global_pick_owner: items of the last enqueued pick frame (any integer array, host) ->
@@ -581,14 +624,7 @@ class GlobalRenderer(_Renderer):
         """gsm_global_render_composite: the SceneObject list `objects` -- resident scenes, each under its own
         pose given as a camera -- sorted and blended together into one width x height frame.  objects None: a
         NULL array with object_count 1 (the C entry's error path)."""
-        n = 1 if objects is None else len(objects)
-        arr = None
-        if objects is not None:
-            arr = (_GlobalObject * max(n, 1))()
-            for g, o in zip(arr, objects):
-                g.input = _Input(_ptr(o.input.gaussians), _ptr(o.input.harmonics), int(o.input.gaussian_count),
-                                 int(o.input.sh_components))
-                g.camera = _camera_struct(o.camera)
+        arr, n = _object_array(objects)
         cp = color_pitch if color_pitch is not None else int(width) * self._bpp
         dp = depth_pitch if depth_pitch is not None else int(width) * 2
         st = _lib().gsm_global_render_composite(self._h, _stream_handle(stream), arr, n, int(width), int(height),

@@ -313,6 +313,50 @@ gsm_status gsm_global_render_composite_pick(gsm_renderer *renderer, void *stream
 gsm_status gsm_global_pick_owner(gsm_renderer *renderer, const uint32_t *items, uint32_t n,
                                  uint32_t *object, uint32_t *gaussian);
 
+/* Occlusion by a depth image (no reference analogue): gsm_global_render and
+ * gsm_global_render_composite with one more input, the view-space depth of the opaque geometry the application
+ * draws itself.  Splats behind that surface disappear, pixel by pixel, inside the blend.
+ *
+ * Occluder: height rows of occluder_pitch_bytes, one float per pixel, in device memory; the frame only reads it.
+ * The value is the depth of the opaque surface at that pixel in the unit of the frame's own depth target: clip.w
+ * of the frame camera (of the shared projection for a composite).  INTEGRATION.md says how to get it from a
+ * hardware depth buffer.
+ *
+ * Rule, on the blend's walk of a pixel's tile list (front to back, per 4x2 pixel group).  Z = fp16(occluder
+ * value), one round-to-nearest-even conversion, denormals kept.  A pixel is closed from the first evaluated entry
+ * on whose fp16 depth dep lies behind the surface, Z < dep (false when either is NaN).  A closed pixel's alpha is
+ * +0 for that entry and every later one, and the group's saturation break takes a closed pixel's transmittance
+ * as +0; everything else of the walk is the plain entry's.  (Every entry of the tile's list counts, also one
+ * whose alpha is 0 on all of the group's pixels: it blends nothing, but it closes pixels.)  So:
+ *   - a splat at exactly the surface's fp16 depth is drawn (the cut moves in fp16 steps: 0.0625 near depth 100);
+ *   - an occluder value of +inf, NaN, or anything that rounds to fp16 +inf (above 65519) occludes nothing;
+ *   - a value at or below the near plane closes the pixel before its first entry;
+ *   - with an occluder of all +inf (or all NaN) the colour and depth bytes equal the plain entry's.
+ * Active tiles are those with list entries, whatever the occluder says: pixels of inactive tiles hold the clear
+ * value (alpha 1); a fully occluded pixel of an active tile holds colour 0, alpha 1 - 1 = +0 and depth 0.  Every
+ * gsm_color_format and both precisions; depth may be NULL.
+ *
+ * Checks: the plain entry's, in its order, with the occluder joining the rows it belongs to --
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  also: occluder NULL;
+ *   GSM_ERR_INVALID_BUFFER_SIZE      also: occluder_pitch_bytes < 4 * width, or the pointer or the pitch not
+ *                                    4-byte aligned;
+ *   GSM_ERR_UNSUPPORTED              (both entries, after every other check) the handle is restricted to tile
+ *                                    rows (gsm_global_set_tile_rows).
+ * Enqueue-only and capturable like the plain entries; nothing is allocated per frame.  gsm_global_render_views,
+ * gsm_global_render_batch, the pick entries, the DepthFirst and Local renderers and the multi-GPU frame have no
+ * occluded entry. */
+gsm_status gsm_global_render_occluded(gsm_renderer *renderer, void *stream, const gsm_gaussian_input *input,
+                                      const gsm_camera_params *camera, uint32_t width, uint32_t height,
+                                      void *color, size_t color_pitch_bytes, void *depth_r16f,
+                                      size_t depth_pitch_bytes, const void *occluder_r32f,
+                                      size_t occluder_pitch_bytes);
+gsm_status gsm_global_render_composite_occluded(gsm_renderer *renderer, void *stream,
+                                                const gsm_global_object *objects, uint32_t object_count,
+                                                uint32_t width, uint32_t height,
+                                                void *color, size_t color_pitch_bytes,
+                                                void *depth_r16f, size_t depth_pitch_bytes,
+                                                const void *occluder_r32f, size_t occluder_pitch_bytes);
+
 /* GlobalRenderer.renderStereo (GlobalRenderer.swift:240-255) calls fatalError for
  * every target; this entry returns GSM_ERR_UNSUPPORTED instead. */
 gsm_status gsm_global_render_stereo(gsm_renderer *renderer, void *stream,
