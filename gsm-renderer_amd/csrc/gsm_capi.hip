@@ -139,6 +139,36 @@ gsm_status gsm_global_render_composite_occluded(gsm_renderer* r, void* stream, c
                                             color_pitch, depth, depth_pitch, occluder, occluder_pitch);
 }
 
+gsm_status gsm_global_render_styled(gsm_renderer* r, void* stream, const gsm_gaussian_input* input,
+                                    const gsm_camera_params* camera, uint32_t width, uint32_t height, void* color,
+                                    size_t color_pitch, void* depth, size_t depth_pitch, void* pick, size_t pick_pitch,
+                                    const gsm_global_state* state, const gsm_global_style* styles,
+                                    uint32_t style_count) {
+    if (!r || !r->impl || !input || !camera) return GSM_ERR_INVALID_ARGUMENT;
+    return r->impl->renderStyled((hipStream_t)stream, *input, *camera, width, height, color, color_pitch, depth,
+                                 depth_pitch, pick, pick_pitch, state, styles, style_count);
+}
+
+gsm_status gsm_global_render_composite_styled(gsm_renderer* r, void* stream, const gsm_global_object* objects,
+                                              uint32_t object_count, uint32_t width, uint32_t height, void* color,
+                                              size_t color_pitch, void* depth, size_t depth_pitch, void* pick,
+                                              size_t pick_pitch, const gsm_global_state* states,
+                                              const gsm_global_style* styles, uint32_t style_count) {
+    if (!r || !r->impl) return GSM_ERR_INVALID_ARGUMENT;
+    return r->impl->renderCompositeStyled((hipStream_t)stream, objects, object_count, width, height, color,
+                                          color_pitch, depth, depth_pitch, pick, pick_pitch, states, styles,
+                                          style_count);
+}
+
+gsm_status gsm_global_select_mask(gsm_renderer* r, void* stream, const gsm_gaussian_input* input,
+                                  const gsm_camera_params* camera, uint32_t width, uint32_t height, const void* mask,
+                                  size_t mask_pitch, uint8_t* state, const gsm_global_style* styles,
+                                  uint32_t style_count, uint32_t and_mask, uint32_t xor_mask, uint32_t* matched) {
+    if (!r || !r->impl) return GSM_ERR_INVALID_ARGUMENT;
+    return r->impl->selectMask((hipStream_t)stream, input, camera, width, height, mask, mask_pitch, state, styles,
+                               style_count, and_mask, xor_mask, matched);
+}
+
 gsm_status gsm_global_pick_owner(gsm_renderer* r, const uint32_t* items, uint32_t n, uint32_t* object,
                                  uint32_t* gaussian) {
     if (!r || !r->impl || (n > 0 && (!items || !object || !gaussian))) return GSM_ERR_INVALID_ARGUMENT;

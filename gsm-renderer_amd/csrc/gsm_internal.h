@@ -105,9 +105,14 @@ struct ComposeObjectArgs {
     uint32_t count;  // gaussians of this object's scene
     const void* world;
     const void* harm;
-    uint32_t blockBase, pad[3];
+    uint32_t blockBase;
+    // a styled composite (k_project_compose_styled): the object's state bytes, or null and the state
+    // of all its gaussians; both zero in a plain composite, which reads neither
+    uint32_t defaultState;
+    const uint8_t* state;
 };
-static_assert(sizeof(ComposeObjectArgs) == 272 && sizeof(ComposeObjectArgs) < sizeof(BatchViewArgs),
+static_assert(sizeof(ComposeObjectArgs) == 272 && sizeof(ComposeObjectArgs) < sizeof(BatchViewArgs) &&
+                  offsetof(ComposeObjectArgs, blockBase) == 256,
               "ComposeObjectArgs: 17 16-B words");
 // the array is filled by kernel arguments, kComposeChunk entries per launch (a kernel argument block holds 4 KiB)
 constexpr uint32_t kComposeChunk = 14;
@@ -120,6 +125,23 @@ struct ComposeFrame {
     uint32_t blocks = 0;   // projection / scatter blocks: sum of ceil(count_o / 256)
     const ComposeObjectArgs* args = nullptr;   // device, [entries]
     const uint16_t* blockObject = nullptr;     // device, [blocks]: the entry of every block
+};
+
+// Per-gaussian styles (gsm_global_render_styled): the device table holds 256 packed styles --
+// word x: tint r | g << 8 | b << 16 | tint_amount << 24, word y: opacity_scale | hidden << 8 -- padded with the
+// identity past the caller's style_count, so a state byte indexes it without a bound.  It is filled by kernel
+// arguments (k_fill_styles): the host array is consumed at the call, a captured frame replays its table.
+constexpr uint32_t kStyleEntries = 256;
+constexpr uint32_t kStyleIdentityY = 255u;  // (x: 0 -- tint_amount 0; y: opacity_scale 255, not hidden)
+struct StyleChunk {
+    uint2 v[kStyleEntries];
+};
+static_assert(sizeof(StyleChunk) == 2048, "StyleChunk: 2 KiB of kernel arguments");
+// what a styled projection reads per gaussian: the table and the scene's state bytes (null: defaultState)
+struct StyleArgs {
+    const uint2* table = nullptr;
+    const uint8_t* state = nullptr;
+    uint32_t defaultState = 0;
 };
 
 // Multi-GPU partition: tile-row boundaries of the slabs, and the 48-byte
@@ -301,6 +323,7 @@ struct DeviceArena {
     uint16_t* batchTileView = nullptr;         // [tileCount] the view of every tile of a batch
     ComposeObjectArgs* composeArgs = nullptr;  // [min(ceil(maxG / 256), 65535)] per-object entries (render_composite; lazily)
     uint16_t* composeBlockObject = nullptr;    // [ceil(maxG / 256)] the entry of every projection block of a composite
+    uint2* styleTable = nullptr;               // [kStyleEntries] packed styles (styled frames, select_mask; lazily)
     uint16_t* expTable = nullptr;              // [65536]
     float2* sincosTable = nullptr;             // [kSincosEntries + 256]: sin/cos, then the byte table (det_byte_lut_entry)
 };
@@ -383,6 +406,21 @@ void launch_project_compose(bool halfInput, uint32_t shDegree, const ProjectArgs
                             const DeviceArena& A, hipStream_t stream);
 void launch_fill_compose(const ComposeChunk& chunk, uint32_t first, uint32_t n, ComposeObjectArgs* dst,
                          uint16_t* blockObject, uint32_t maxBlocks, hipStream_t stream);
+// the styled frames (k_project_styled, k_project_compose_styled): the projections above with the
+// style of every gaussian's state byte applied where its four u8 bytes are formed; a composite's state pointers
+// travel in its entries.  launch_fill_styles writes the 256-entry table from `chunk`.
+void launch_project_styled(bool halfInput, uint32_t shDegree, const void* world, const void* harmonics,
+                           const ProjectArgs& args, const StyleArgs& style, const DeviceArena& A, hipStream_t stream);
+void launch_project_compose_styled(bool halfInput, uint32_t shDegree, const ProjectArgs& args, const ComposeFrame& cf,
+                                   const uint2* styleTable, const DeviceArena& A, hipStream_t stream);
+void launch_fill_styles(const StyleChunk& chunk, uint2* dst, hipStream_t stream);
+// gsm_global_select_mask (k_select_mask): the state bytes of the gaussians whose fp16 mean lies on
+// a nonzero mask byte become (old & andMask) ^ xorMask; *matched (nullable, zeroed by the caller) counts them.
+// styleTable (nullable): gaussians whose current state is hidden do not match.
+void launch_select_mask(bool halfInput, const void* world, const ProjectArgs& args, const uint8_t* mask,
+                        size_t maskPitch, uint32_t width, uint32_t height, uint8_t* state, const uint2* styleTable,
+                        uint32_t andMask, uint32_t xorMask, uint32_t* matched, const DeviceArena& A,
+                        hipStream_t stream);
 // exclusive scan of the per-block sums, total + clamp into the header (GlobalShaders.metal:685-712)
 // project gaussians [0, a.count) of world/harm (already offset to the rank's range) and pack
 // the records of each slab's gaussians into `send` (slab-major, ascending id), counts to sendCounts

@@ -64,12 +64,18 @@ __device__ __forceinline__ void fill_byte_lut(ByteLut& L, const float2* __restri
 }
 
 
-template <bool HALF, int DEG>
+// MODE: kProjPlain -- the frame's projection; kProjStyled -- the same with the packed style of the
+// gaussian's state (`style`: StyleChunk's words) applied where the four u8 bytes are formed, a hidden style being
+// one more cull; kProjMean -- stop after the screen-bounds cull with only vis and the fp16 mean (rd.x) set, for
+// gsm_global_select_mask: no SH, no record, no tile rect, and the mean's bits are the frame's.
+constexpr int kProjPlain = 0, kProjStyled = 1, kProjMean = 2;
+template <bool HALF, int DEG, int MODE = kProjPlain>
 __device__ __forceinline__ ProjOut project_gaussian(const void* __restrict__ world,
                                                     const void* __restrict__ harm, uint32_t gid,
                                                     const ProjectArgs& P,
                                                     const float2* __restrict__ sincos,
-                                                    const ByteLut& lut, const uint4* preWorld = nullptr) {
+                                                    const ByteLut& lut, const uint4* preWorld = nullptr,
+                                                    uint2 style = make_uint2(0u, kStyleIdentityY)) {
     ProjOut o;
     o.vis = false;
     o.countable = false;
@@ -153,6 +159,15 @@ __device__ __forceinline__ ProjOut project_gaussian(const void* __restrict__ wor
             if (sx + ex < 0.0f || sx - ex > cam.width || sy + ey < 0.0f || sy - ey > cam.height)
                 vis = false;
         }
+        if constexpr (MODE == kProjMean) {
+            o.vis = vis;
+            o.rd = make_uint4((uint32_t)f_to_hbits(sx) | ((uint32_t)f_to_hbits(sy) << 16), 0u, 0u, 0u);
+            return o;
+        }
+        if constexpr (MODE == kProjStyled) {
+            // a hidden gaussian is culled exactly as by the culls above (before the SH evaluation: the same result)
+            if ((style.y >> 8) & 0xFFu) vis = false;
+        }
         if (vis) {
             float col[3];
             sh_color<HALF, DEG>(harm, gid, pos, cam.cameraCenter, cam.shComponents, col);
@@ -175,6 +190,15 @@ __device__ __forceinline__ ProjOut project_gaussian(const void* __restrict__ wor
             uint32_t cG = (uint32_t)(uint8_t)clampf(col[1] * 255.0f, 0.0f, 255.0f);
             uint32_t cB = (uint32_t)(uint8_t)clampf(col[2] * 255.0f, 0.0f, 255.0f);
             uint32_t cO = (uint32_t)(uint8_t)clampf(opacity * 255.0f, 0.0f, 255.0f);
+            if constexpr (MODE == kProjStyled) {
+                // the style rule, in unsigned integers: c' = (c (255 - k) + t k + 127) / 255, o' = (o s + 127) / 255;
+                // everything below -- the record, the tile-test level, the band -- reads the styled bytes
+                const uint32_t k = style.x >> 24, nk = 255u - k, sc = style.y & 0xFFu;
+                cR = (cR * nk + (style.x & 0xFFu) * k + 127u) / 255u;
+                cG = (cG * nk + ((style.x >> 8) & 0xFFu) * k + 127u) / 255u;
+                cB = (cB * nk + ((style.x >> 16) & 0xFFu) * k + 127u) / 255u;
+                cO = (cO * sc + 127u) / 255u;
+            }
             uint4 rdw;
             rdw.x = (uint32_t)hmx | ((uint32_t)hmy << 16);
             rdw.y = (uint32_t)thq | ((uint32_t)hs1 << 16);
@@ -310,6 +334,15 @@ __device__ __forceinline__ float2 band_of(const BlendRecordA& ra, short4 r, cons
 #define GSM_VIEWS 3
 #include "gsm_project_body.h"
 #undef GSM_VIEWS
+// the styled frames: the single frame's text and the composite's once more, with the style pass
+#define GSM_STYLED 1
+#define GSM_VIEWS 0
+#include "gsm_project_body.h"
+#undef GSM_VIEWS
+#define GSM_VIEWS 3
+#include "gsm_project_body.h"
+#undef GSM_VIEWS
+#undef GSM_STYLED
 
 // entries [first, first + n) of the per-view array from a kernel argument (plain vector stores): the host's
 // copy of the cameras is consumed when the frame is enqueued, so the call needs no staging buffer that a
@@ -358,6 +391,47 @@ __global__ __launch_bounds__(256) void k_fill_compose(ComposeChunk chunk, uint32
         const uint32_t b0 = min(V.blockBase, maxBlocks);
         const uint32_t b1 = min(V.blockBase + (V.count + kProjectBlock - 1u) / kProjectBlock, maxBlocks);
         for (uint32_t i = b0 + threadIdx.x; i < b1; i += 256u) blockObject[i] = entry;
+    }
+}
+
+// The style table of a styled frame or a select from a kernel argument, as the entries above: the
+// caller's array is consumed at the call and a captured frame replays its table.  256 entries, one per thread.
+__global__ __launch_bounds__(kStyleEntries) void k_fill_styles(StyleChunk chunk, uint2* __restrict__ dst) {
+    dst[threadIdx.x] = chunk.v[threadIdx.x];
+}
+
+// gsm_global_select_mask: one thread per gaussian.  project_gaussian's kProjMean mode runs the
+// frame's culls and forms the fp16 mean with the frame's own functions; the mean's pixel is looked up in the mask
+// and a matching gaussian's state byte becomes (old & andMask) ^ xorMask.  No SH, no record, no tile test; byte
+// loads and stores, one integer add per workgroup for the count (*matched: zeroed by the launcher).
+template <bool HALF>
+__global__ __launch_bounds__(kProjectBlock) void k_select_mask(
+    const void* __restrict__ world, ProjectArgs P, const float2* __restrict__ sincos,
+    const uint8_t* __restrict__ mask, size_t maskPitch, uint32_t width, uint32_t height, uint8_t* __restrict__ state,
+    const uint2* __restrict__ styleTable, uint32_t andMask, uint32_t xorMask, uint32_t* __restrict__ matched) {
+    __shared__ uint32_t lds[kProjectBlock / 64];
+    __shared__ ByteLut lut;  // (kProjMean reads no entry of it)
+    const uint32_t gid = blockIdx.x * kProjectBlock + threadIdx.x;
+    uint32_t hit = 0;
+    if (gid < P.count) {
+        const ProjOut o = project_gaussian<HALF, 0, kProjMean>(world, nullptr, gid, P, sincos, lut);
+        const uint32_t old = state[gid];
+        bool match = o.vis;
+        if (styleTable && ((styleTable[old].y >> 8) & 0xFFu)) match = false;  // hidden: not selectable
+        const uint16_t hmx = (uint16_t)(o.rd.x & 0xFFFFu), hmy = (uint16_t)(o.rd.x >> 16);
+        if ((hmx & 0x7C00u) == 0x7C00u || (hmy & 0x7C00u) == 0x7C00u) match = false;  // inf or NaN
+        // floor(m + 0.5): exact in fp32 for every finite fp16 m
+        const float fx = __builtin_floorf(hbits_to_f(hmx) + 0.5f), fy = __builtin_floorf(hbits_to_f(hmy) + 0.5f);
+        if (!(fx >= 0.0f && fx < (float)width && fy >= 0.0f && fy < (float)height)) match = false;
+        if (match) {
+            match = mask[(size_t)(uint32_t)fy * maskPitch + (uint32_t)fx] != 0;
+            if (match) state[gid] = (uint8_t)(((old & andMask) ^ xorMask) & 0xFFu);
+        }
+        hit = match ? 1u : 0u;
+    }
+    if (matched) {  // (uniform)
+        const uint32_t s = block_reduce_add<kProjectBlock>(hit, lds);
+        if (threadIdx.x == 0 && s) atomicAdd(matched, s);
     }
 }
 
@@ -1269,6 +1343,72 @@ void launch_fill_compose(const ComposeChunk& chunk, uint32_t first, uint32_t n, 
     if (n == 0) return;
     hipLaunchKernelGGL(k_fill_compose, dim3(1), dim3(256), 0, s, chunk, first, n > kComposeChunk ? kComposeChunk : n,
                        dst, blockObject, maxBlocks);
+}
+
+template <bool HALF>
+static void launch_project_styled_t(uint32_t deg, const void* world, const void* harm, const ProjectArgs& a,
+                                    const StyleArgs& st, const DeviceArena& A, hipStream_t s) {
+    const uint32_t blocks = (a.count + kProjectBlock - 1) / kProjectBlock;
+    if (blocks == 0 && a.schedUnits == 0) return;  // (an empty frame still orders its blend units)
+#define GSM_LAUNCH_PROJS(D)                                                                                         \
+    hipLaunchKernelGGL((k_project_styled<HALF, D>), dim3(blocks + (a.schedUnits ? 1u : 0u)), dim3(kProjectBlock), 0, \
+                       s, world, harm, a, A.renderData, A.bounds, A.rec, A.tileCounts, A.tileMasks, A.blockSums,     \
+                       A.sincosTable, A.unitCost, A.unitOrder, A.costMax, st.table, st.state, st.defaultState)
+    switch (deg) {
+        case 0: GSM_LAUNCH_PROJS(0); break;
+        case 1: GSM_LAUNCH_PROJS(1); break;
+        case 2: GSM_LAUNCH_PROJS(2); break;
+        default: GSM_LAUNCH_PROJS(3); break;
+    }
+#undef GSM_LAUNCH_PROJS
+}
+
+void launch_project_styled(bool halfInput, uint32_t deg, const void* world, const void* harm, const ProjectArgs& a,
+                           const StyleArgs& st, const DeviceArena& A, hipStream_t s) {
+    if (halfInput) launch_project_styled_t<true>(deg, world, harm, a, st, A, s);
+    else launch_project_styled_t<false>(deg, world, harm, a, st, A, s);
+}
+
+template <bool HALF>
+static void launch_project_compose_styled_t(uint32_t deg, const ProjectArgs& a, const ComposeFrame& cf,
+                                            const uint2* styleTable, const DeviceArena& A, hipStream_t s) {
+    if (cf.blocks == 0 && a.schedUnits == 0) return;  // (an empty composite still orders its blend units)
+#define GSM_LAUNCH_PROJCS(D)                                                                                        \
+    hipLaunchKernelGGL((k_project_compose_styled<HALF, D>), dim3(cf.blocks + (a.schedUnits ? 1u : 0u)),              \
+                       dim3(kProjectBlock), 0, s, a, cf.args, cf.blockObject, A.renderData, A.bounds, A.rec,         \
+                       A.tileCounts, A.tileMasks, A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax,    \
+                       styleTable)
+    switch (deg) {
+        case 0: GSM_LAUNCH_PROJCS(0); break;
+        case 1: GSM_LAUNCH_PROJCS(1); break;
+        case 2: GSM_LAUNCH_PROJCS(2); break;
+        default: GSM_LAUNCH_PROJCS(3); break;
+    }
+#undef GSM_LAUNCH_PROJCS
+}
+
+void launch_project_compose_styled(bool halfInput, uint32_t deg, const ProjectArgs& a, const ComposeFrame& cf,
+                                   const uint2* styleTable, const DeviceArena& A, hipStream_t s) {
+    if (halfInput) launch_project_compose_styled_t<true>(deg, a, cf, styleTable, A, s);
+    else launch_project_compose_styled_t<false>(deg, a, cf, styleTable, A, s);
+}
+
+void launch_fill_styles(const StyleChunk& chunk, uint2* dst, hipStream_t s) {
+    hipLaunchKernelGGL(k_fill_styles, dim3(1), dim3(kStyleEntries), 0, s, chunk, dst);
+}
+
+void launch_select_mask(bool halfInput, const void* world, const ProjectArgs& a, const uint8_t* mask, size_t maskPitch,
+                        uint32_t width, uint32_t height, uint8_t* state, const uint2* styleTable, uint32_t andMask,
+                        uint32_t xorMask, uint32_t* matched, const DeviceArena& A, hipStream_t s) {
+    if (matched) hipMemsetAsync(matched, 0, sizeof(uint32_t), s);  // (overwritten, not added to)
+    const uint32_t blocks = (a.count + kProjectBlock - 1) / kProjectBlock;
+    if (blocks == 0) return;
+    if (halfInput)
+        hipLaunchKernelGGL(k_select_mask<true>, dim3(blocks), dim3(kProjectBlock), 0, s, world, a, A.sincosTable, mask,
+                           maskPitch, width, height, state, styleTable, andMask, xorMask, matched);
+    else
+        hipLaunchKernelGGL(k_select_mask<false>, dim3(blocks), dim3(kProjectBlock), 0, s, world, a, A.sincosTable, mask,
+                           maskPitch, width, height, state, styleTable, andMask, xorMask, matched);
 }
 
 template <bool HALF>

@@ -1,9 +1,33 @@
-// gsm_project_body.h -- the text of k_project, compiled four times by gsm_kernels.hip: as the single frame's
+// gsm_project_body.h -- the text of k_project, compiled four times (and twice styled) by gsm_kernels.hip: as the single frame's
 // kernel (GSM_VIEWS 0: k_project, exactly the kernel it was before batches of views existed; an item is its
 // gaussian id), as the projection of a batch of views of one scene (GSM_VIEWS 1: k_project_views), as the
 // projection of a batch of views of different scenes and sizes (GSM_VIEWS 2: k_project_batch) and as the
 // projection of several posed objects into one frame (GSM_VIEWS 3: k_project_compose).  No include guard.
-#if GSM_VIEWS == 3
+// With GSM_STYLED defined (GSM_VIEWS 0 and 3 only) the same text gives k_project_styled and
+// k_project_compose_styled: one more argument, the style table -- and for the single frame the
+// scene's state bytes and default -- and project_gaussian's kProjStyled mode; nothing else differs.
+#if defined(GSM_STYLED) && GSM_VIEWS == 3
+template <bool HALF, int DEG>
+__global__ __launch_bounds__(kProjectBlock) void k_project_compose_styled(
+    ProjectArgs P, const ComposeObjectArgs* __restrict__ objects, const uint16_t* __restrict__ blockObject,
+    GaussianRenderData* __restrict__ outRD, short4* __restrict__ outBounds, BlendRecord* __restrict__ outRec,
+    uint32_t* __restrict__ counts, uint32_t* __restrict__ masks, uint32_t* __restrict__ blockSums,
+    const float2* __restrict__ sincos, const uint16_t* __restrict__ unitCost, uint32_t* __restrict__ unitOrder,
+    uint32_t* __restrict__ costMax, const uint2* __restrict__ styleTable) {
+    const void* __restrict__ world = nullptr;  // the block's scene: its object's (below)
+    const void* __restrict__ harm = nullptr;
+    const uint8_t* __restrict__ stateBytes = nullptr;  // the block's state bytes and default: its object's
+    uint32_t defaultState = 0;
+#elif defined(GSM_STYLED)
+template <bool HALF, int DEG>
+__global__ __launch_bounds__(kProjectBlock) void k_project_styled(
+    const void* __restrict__ world, const void* __restrict__ harm, ProjectArgs P,
+    GaussianRenderData* __restrict__ outRD, short4* __restrict__ outBounds,
+    BlendRecord* __restrict__ outRec, uint32_t* __restrict__ counts,
+    uint32_t* __restrict__ masks, uint32_t* __restrict__ blockSums, const float2* __restrict__ sincos,
+    const uint16_t* __restrict__ unitCost, uint32_t* __restrict__ unitOrder, uint32_t* __restrict__ costMax,
+    const uint2* __restrict__ styleTable, const uint8_t* __restrict__ stateBytes, uint32_t defaultState) {
+#elif GSM_VIEWS == 3
 // The projection of a composite (gsm_global_render_composite): block b belongs to the object of
 // entry blockObject[b] -- uniform per block, one 2-byte load -- and projects gaussians [(b - blockBase) * 256,
 // + 256) of that object's scene under that object's camera onto the frame's own tile grid.  The scene, the count
@@ -77,6 +101,10 @@ __global__ __launch_bounds__(kProjectBlock) void k_project(
         gblk = blk - V.blockBase;
         world = V.world;
         harm = V.harm;
+#ifdef GSM_STYLED
+        stateBytes = V.state;
+        defaultState = V.defaultState;
+#endif
         P.cam = V.cam;
         P.count = V.count;
         P.limX = V.limX;
@@ -141,6 +169,14 @@ __global__ __launch_bounds__(kProjectBlock) void k_project(
     __shared__ uint16_t sCand[kCandCap];
     uint4 preW[2];
     preload_world<HALF>(world, gblk * kProjectBlock + threadIdx.x, P.count, preW);
+#ifdef GSM_STYLED
+    // the gaussian's state byte, loaded with its world record before the byte table's barrier; the style entry
+    // (one 8-byte load of the 2 KiB table) follows it
+    uint32_t stateByte = defaultState;
+    if (stateBytes && gblk * kProjectBlock + threadIdx.x < P.count)
+        stateByte = stateBytes[gblk * kProjectBlock + threadIdx.x];
+    const uint2 style = styleTable[stateByte & (kStyleEntries - 1u)];
+#endif
     fill_byte_lut(lut, sincos);
     const uint32_t tid = threadIdx.x;
     const uint32_t gid = gblk * kProjectBlock + tid;
@@ -156,7 +192,11 @@ __global__ __launch_bounds__(kProjectBlock) void k_project(
     uint32_t area = 0;
     int ty0 = 0;
     if (gid < P.count) {
+#ifdef GSM_STYLED
+        o = project_gaussian<HALF, DEG, kProjStyled>(world, harm, gid, P, sincos, lut, HALF ? preW : nullptr, style);
+#else
         o = project_gaussian<HALF, DEG>(world, harm, gid, P, sincos, lut, HALF ? preW : nullptr);
+#endif
         outBounds[oid] = o.bounds;
         if (o.vis) {
             // GaussianRenderData: the frame itself only reads it for rects the scatter re-tests

@@ -253,22 +253,105 @@ gsm_status GlobalRenderer::pickOwner(const uint32_t* items, uint32_t n, uint32_t
 
 gsm_status GlobalRenderer::renderFrame(hipStream_t s, const gsm_gaussian_input& in, const gsm_camera_params& camp,
                                        uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                                       size_t depthPitch, const PickTarget* pick, const OccluderSource* occluder) {
+                                       size_t depthPitch, const PickTarget* pick, const OccluderSource* occluder,
+                                       const StyleSource* style) {
     gsm_status st = validateFrame(in.gaussian_count, !in.gaussians || !in.harmonics, width, height, color,
                                   colorPitch, depth, depthPitch, pick, occluder);
     if (st != GSM_OK) return st;
-    // (set_tile_rows: a pick frame and an occluded frame are whole frames)
-    if ((pick || occluder) && tileRowsRestricted()) return GSM_ERR_UNSUPPORTED;
+    if (style && !styleSourceOk(*style, 1)) return GSM_ERR_INVALID_ARGUMENT;
+    // (set_tile_rows: a pick frame, an occluded frame and a styled frame are whole frames)
+    if ((pick || occluder || style) && tileRowsRestricted()) return GSM_ERR_UNSUPPORTED;
     // the projection's tile tests walk contiguous rows; interleaved row sets come from the records
     // path only (gsm_multigpu)
     if (rowStride_ != 1) return GSM_ERR_INVALID_ARGUMENT;
     const ProjectArgs a = frameArgs(camp, width, height, in.gaussian_count, in.sh_components);
     const uint32_t deg = sh_degree(in.sh_components);
     const bool half = config_.precision == GSM_PRECISION_FLOAT16;
+    if (style) {
+        if ((st = fillStyleTable(s, style->styles, style->styleCount)) != GSM_OK) return st;
+        const StyleArgs sa{arena_.styleTable, style->states[0].state, style->states[0].default_state};
+        return runFrame(s, a, width, height, color, colorPitch, depth, depthPitch,
+                        [&](const ProjectArgs& pa) {
+                            launch_project_styled(half, deg, in.gaussians, in.harmonics, pa, sa, arena_, s);
+                        }, nullptr, false, nullptr, nullptr, pick, nullptr, true);
+    }
     return runFrame(s, a, width, height, color, colorPitch, depth, depthPitch,
                     [&](const ProjectArgs& pa) {
                         launch_project(half, deg, in.gaussians, in.harmonics, pa, arena_, s);
                     }, nullptr, false, nullptr, nullptr, pick, occluder);
+}
+
+bool GlobalRenderer::styleSourceOk(const StyleSource& style, uint32_t stateCount) {
+    if (!style.styles || style.styleCount == 0 || style.styleCount > kStyleEntries || !style.states) return false;
+    for (uint32_t o = 0; o < stateCount; ++o)
+        if (style.states[o].default_state > 255u) return false;
+    return true;
+}
+
+gsm_status GlobalRenderer::fillStyleTable(hipStream_t s, const gsm_global_style* styles, uint32_t styleCount) {
+    if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
+    if (!arena_.styleTable) {  // (the handle's first styled frame or select with styles)
+        const gsm_status st = allocs_.alloc((void**)&arena_.styleTable, sizeof(StyleChunk));
+        if (st != GSM_OK) return st;
+    }
+    StyleChunk c;
+    for (uint32_t i = 0; i < kStyleEntries; ++i) {
+        c.v[i] = make_uint2(0u, kStyleIdentityY);
+        if (i < styleCount) {
+            const gsm_global_style& S = styles[i];
+            c.v[i].x = (uint32_t)S.tint_r | ((uint32_t)S.tint_g << 8) | ((uint32_t)S.tint_b << 16) |
+                       ((uint32_t)S.tint_amount << 24);
+            c.v[i].y = (uint32_t)S.opacity_scale | (S.hidden ? 1u << 8 : 0u);
+        }
+    }
+    launch_fill_styles(c, arena_.styleTable, s);
+    return GSM_OK;
+}
+
+gsm_status GlobalRenderer::renderStyled(hipStream_t s, const gsm_gaussian_input& in, const gsm_camera_params& camp,
+                                        uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
+                                        size_t depthPitch, void* pick, size_t pickPitch,
+                                        const gsm_global_state* state, const gsm_global_style* styles,
+                                        uint32_t styleCount) {
+    const PickTarget pt{pick, pickPitch};
+    const StyleSource ss{state, styles, styleCount};
+    return renderFrame(s, in, camp, width, height, color, colorPitch, depth, depthPitch, pick ? &pt : nullptr, nullptr,
+                       &ss);
+}
+
+gsm_status GlobalRenderer::renderCompositeStyled(hipStream_t s, const gsm_global_object* objects, uint32_t objectCount,
+                                                 uint32_t width, uint32_t height, void* color, size_t colorPitch,
+                                                 void* depth, size_t depthPitch, void* pick, size_t pickPitch,
+                                                 const gsm_global_state* states, const gsm_global_style* styles,
+                                                 uint32_t styleCount) {
+    const PickTarget pt{pick, pickPitch};
+    const StyleSource ss{states, styles, styleCount};
+    return composeFrame(s, objects, objectCount, width, height, color, colorPitch, depth, depthPitch,
+                        pick ? &pt : nullptr, nullptr, &ss);
+}
+
+gsm_status GlobalRenderer::selectMask(hipStream_t s, const gsm_gaussian_input* in, const gsm_camera_params* camp,
+                                      uint32_t width, uint32_t height, const void* mask, size_t maskPitch,
+                                      uint8_t* state, const gsm_global_style* styles, uint32_t styleCount,
+                                      uint32_t andMask, uint32_t xorMask, uint32_t* matched) {
+    // (the count of a NULL input cannot be read: that is the missing buffer, before every other check)
+    if (!in) return GSM_ERR_MISSING_REQUIRED_BUFFER;
+    if (in->gaussian_count > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
+    if (!frameSizeOk(width, height)) return GSM_ERR_INVALID_DIMENSIONS;
+    if (!camp || !mask || (in->gaussian_count > 0 && (!in->gaussians || !state))) return GSM_ERR_MISSING_REQUIRED_BUFFER;
+    if (maskPitch < width || (((uintptr_t)matched) & 3u)) return GSM_ERR_INVALID_BUFFER_SIZE;
+    if (styles ? (styleCount == 0 || styleCount > kStyleEntries) : styleCount != 0) return GSM_ERR_INVALID_ARGUMENT;
+    if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
+    (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's)
+    if (styles && in->gaussian_count > 0) {
+        const gsm_status st = fillStyleTable(s, styles, styleCount);
+        if (st != GSM_OK) return st;
+    }
+    const ProjectArgs a = frameArgs(*camp, width, height, in->gaussian_count, 0);
+    launch_select_mask(config_.precision == GSM_PRECISION_FLOAT16, in->gaussians, a, (const uint8_t*)mask, maskPitch,
+                       width, height, state, styles ? arena_.styleTable : nullptr, andMask, xorMask, matched, arena_, s);
+    if (hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;
+    return GSM_OK;
 }
 
 uint32_t GlobalRenderer::tiles_of(uint32_t width, uint32_t height) {
@@ -496,7 +579,8 @@ gsm_status GlobalRenderer::renderComposite(hipStream_t s, const gsm_global_objec
 
 gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* objects, uint32_t objectCount,
                                         uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                                        size_t depthPitch, const PickTarget* pick, const OccluderSource* occluder) {
+                                        size_t depthPitch, const PickTarget* pick, const OccluderSource* occluder,
+                                        const StyleSource* style) {
     // Every check before anything is enqueued, one kind of check after another over all objects (the first
     // failing kind decides, within it the lowest object): counts, dimensions, missing buffers, sizes,
     // sh_components, tile rows.  (The counts of a NULL array cannot be read: that is the missing buffer.)
@@ -525,6 +609,7 @@ gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* 
     if (st != GSM_OK) return st;
     for (uint32_t o = 1; o < objectCount; ++o)
         if (objects[o].input.sh_components != objects[0].input.sh_components) return GSM_ERR_INVALID_ARGUMENT;
+    if (style && !styleSourceOk(*style, objectCount)) return GSM_ERR_INVALID_ARGUMENT;
     if (tileRowsRestricted()) return GSM_ERR_UNSUPPORTED;  // (set_tile_rows)
     if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
     // the per-object array and the block table: allocated by the handle's first composite, for the most objects
@@ -568,6 +653,10 @@ gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* 
         d.world = O.input.gaussians;
         d.harm = O.input.harmonics;
         d.blockBase = blockBase;
+        if (style) {  // (a styled composite: the object's state bytes and default travel with its entry)
+            d.state = style->states[o].state;
+            d.defaultState = style->states[o].default_state;
+        }
         composeHost_.push_back(d);
         composeObject_.push_back(o);  // (pickOwner: the entry's object index of the call)
         blockBase += (n + kProjectBlock - 1) / kProjectBlock;
@@ -591,6 +680,13 @@ gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* 
     vf.compose.blockObject = arena_.composeBlockObject;
     const uint32_t deg = sh_degree(sh);
     const bool half = config_.precision == GSM_PRECISION_FLOAT16;
+    if (style) {
+        if ((st = fillStyleTable(s, style->styles, style->styleCount)) != GSM_OK) return st;
+        return runFrame(s, a, width, height, color, colorPitch, depth, depthPitch,
+                        [&](const ProjectArgs& pa) {
+                            launch_project_compose_styled(half, deg, pa, vf.compose, arena_.styleTable, arena_, s);
+                        }, nullptr, false, nullptr, &vf, pick, nullptr, true);
+    }
     return runFrame(s, a, width, height, color, colorPitch, depth, depthPitch,
                     [&](const ProjectArgs& pa) { launch_project_compose(half, deg, pa, vf.compose, arena_, s); },
                     nullptr, false, nullptr, &vf, pick, occluder);
@@ -731,7 +827,7 @@ gsm_status GlobalRenderer::partitionPush(hipStream_t s, uint32_t world, uint32_t
 }
 
 uint32_t GlobalRenderer::scheduleUnits(hipStream_t s, uint32_t width, uint32_t height, uint32_t views,
-                                       uint32_t batchTiles, bool compose, bool pick, bool occluded) {
+                                       uint32_t batchTiles, bool compose, bool pick, bool occluded, bool styled) {
     // (a batch of views: the units of views * tiles(width, height) tiles; the view count is part of the key, so
     // a batch neither inherits nor leaves behind a single frame's costs.  A batch of different views: the units
     // of its batchTiles tiles, keyed by its whole signature batchSig_, compared word for word)
@@ -746,7 +842,8 @@ uint32_t GlobalRenderer::scheduleUnits(hipStream_t s, uint32_t width, uint32_t h
     const bool isBatch = batchTiles != 0;
     // (a pick frame walks without compaction or pairs: its costs are its own, either way round)
     bool changed = isBatch != schedBatch_ || compose != schedCompose_ || key != schedKey_ || views != schedViews_ ||
-                   pick != schedPick_ || occluded != schedOccluded_;
+                   pick != schedPick_ || occluded != schedOccluded_ || styled != schedStyled_;
+    schedStyled_ = styled;  // (a styled frame hides and fades gaussians: its walks are its own too)
     schedPick_ = pick;
     schedOccluded_ = occluded;  // (an occluded frame's walks end at the occluder: its costs are its own as well)
     if (compose && !changed) changed = composeSig_ != schedComposeSig_;
@@ -772,7 +869,7 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
                                     void* color, size_t colorPitch, void* depth, size_t depthPitch,
                                     Front&& front, const uint32_t* devCount, bool preOrdered,
                                     const MgArrive* blendArrive, const ViewFrame* views, const PickTarget* pick,
-                                    const OccluderSource* occluder) {
+                                    const OccluderSource* occluder, bool styled) {
     (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's: the launches below are checked)
     const int profiling = timer_.flags();
     const bool keep = (profiling & 2) != 0;
@@ -805,7 +902,7 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     const uint32_t units = preOrdered ? 0u
                                       : scheduleUnits(s, width, height, batch ? batch->views : views ? views->batch.views : 0u,
                                                       batch ? batch->tiles : 0u, comp != nullptr, pick != nullptr,
-                                                      occluder != nullptr);
+                                                      occluder != nullptr, styled);
     const bool costOrder = preOrdered ? tuning_.costOrder : units > 0;
     fa.schedUnits = units;
     // (written on every scheduled frame: the blend's remaining-walk priorities read the longest walk too)

@@ -53,6 +53,22 @@ class GlobalRenderer {
     gsm_status renderCompositeOccluded(hipStream_t stream, const gsm_global_object* objects, uint32_t objectCount,
                                        uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
                                        size_t depthPitch, const void* occluder, size_t occluderPitch);
+    // render / renderComposite with the style of every gaussian's state byte applied in the projection; pick
+    // null: the plain blend, else the pick frame (gsm_global_render_styled, gsm_global_render_composite_styled,
+    // DESIGN.md 22).  state / states and styles are host memory, consumed by the call.
+    gsm_status renderStyled(hipStream_t stream, const gsm_gaussian_input& input, const gsm_camera_params& camera,
+                            uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
+                            size_t depthPitch, void* pick, size_t pickPitch, const gsm_global_state* state,
+                            const gsm_global_style* styles, uint32_t styleCount);
+    gsm_status renderCompositeStyled(hipStream_t stream, const gsm_global_object* objects, uint32_t objectCount,
+                                     uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
+                                     size_t depthPitch, void* pick, size_t pickPitch, const gsm_global_state* states,
+                                     const gsm_global_style* styles, uint32_t styleCount);
+    // state bytes of the gaussians whose projected centre lies on a nonzero mask byte (gsm_global_select_mask)
+    gsm_status selectMask(hipStream_t stream, const gsm_gaussian_input* input, const gsm_camera_params* camera,
+                          uint32_t width, uint32_t height, const void* mask, size_t maskPitch, uint8_t* state,
+                          const gsm_global_style* styles, uint32_t styleCount, uint32_t andMask, uint32_t xorMask,
+                          uint32_t* matched);
     // items of the last enqueued pick frame -> (object of the call, gaussian id within it); host only, no sync
     gsm_status pickOwner(const uint32_t* items, uint32_t n, uint32_t* object, uint32_t* gaussian) const;
 
@@ -121,12 +137,24 @@ class GlobalRenderer {
     GlobalRenderer() = default;
     // render, renderPick and renderOccluded; renderComposite, renderCompositePick and renderCompositeOccluded
     // (pick, occluder: null for the plain entries, never both)
+    // (style: null for every entry but the styled ones -- the caller's states, one per object, and its table)
+    struct StyleSource {
+        const gsm_global_state* states;
+        const gsm_global_style* styles;
+        uint32_t styleCount;
+    };
     gsm_status renderFrame(hipStream_t stream, const gsm_gaussian_input& input, const gsm_camera_params& camera,
                            uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                           size_t depthPitch, const PickTarget* pick, const OccluderSource* occluder = nullptr);
+                           size_t depthPitch, const PickTarget* pick, const OccluderSource* occluder = nullptr,
+                           const StyleSource* style = nullptr);
     gsm_status composeFrame(hipStream_t stream, const gsm_global_object* objects, uint32_t objectCount,
                             uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                            size_t depthPitch, const PickTarget* pick, const OccluderSource* occluder = nullptr);
+                            size_t depthPitch, const PickTarget* pick, const OccluderSource* occluder = nullptr,
+                            const StyleSource* style = nullptr);
+    // a styled entry's own refusals (GSM_ERR_INVALID_ARGUMENT), checked after the plain entry's
+    static bool styleSourceOk(const StyleSource& style, uint32_t stateCount);
+    // the handle's style table: allocated by its first use, filled from the caller's styles (identity past them)
+    gsm_status fillStyleTable(hipStream_t s, const gsm_global_style* styles, uint32_t styleCount);
     ProjectArgs frameArgs(const gsm_camera_params& camera, uint32_t width, uint32_t height, uint32_t count,
                           uint32_t shComponents) const;
     // scan, scatter, sort, headers and blend after `front` filled the per-gaussian arrays
@@ -144,7 +172,8 @@ class GlobalRenderer {
                         size_t colorPitch, void* depth, size_t depthPitch, Front&& front,
                         const uint32_t* devCount = nullptr, bool preOrdered = false,
                         const MgArrive* blendArrive = nullptr, const ViewFrame* views = nullptr,
-                        const PickTarget* pick = nullptr, const OccluderSource* occluder = nullptr);
+                        const PickTarget* pick = nullptr, const OccluderSource* occluder = nullptr,
+                        bool styled = false);
     // the blend schedule's unit count for the current rows, or for a batch of `views` frames (0 when cost
     // order is off), its cost arrays cleared when the geometry or the view count changed
     // (batchTiles > 0: a batch of different views, keyed by its signature batchSig_ -- the view count and every
@@ -153,8 +182,10 @@ class GlobalRenderer {
     // object count and every object's count)
     // (pick: a pick frame -- part of the key, so it neither inherits walk costs from a plain frame nor leaves any)
     // (occluded: an occluded frame -- part of the key in the same way)
+    // (styled: a styled frame -- hidden and faded gaussians change the walks -- part of the key in the same way)
     uint32_t scheduleUnits(hipStream_t s, uint32_t width, uint32_t height, uint32_t views = 0,
-                           uint32_t batchTiles = 0, bool compose = false, bool pick = false, bool occluded = false);
+                           uint32_t batchTiles = 0, bool compose = false, bool pick = false, bool occluded = false,
+                           bool styled = false);
     static uint32_t tiles_of(uint32_t width, uint32_t height);  // tiles of a width x height frame
     // checks and arguments renderViews and renderBatch share: a view's size within the handle's, a batch's
     // tiles within its tile space and the key's 16-bit field, no set_tile_rows restriction, and the
@@ -220,6 +251,7 @@ class GlobalRenderer {
     bool schedCompose_ = false;               // the unit costs belong to a composite
     bool schedPick_ = false;                  // the unit costs belong to a pick frame
     bool schedOccluded_ = false;              // the unit costs belong to an occluded frame
+    bool schedStyled_ = false;                // the unit costs belong to a styled frame
     std::vector<uint32_t> composeObject_;     // the call's object index of every entry of composeHost_
     bool lastPick_ = false;                   // the last enqueued frame was a pick frame (pickOwner)
     bool lastPickComposite_ = false;          // ... of a composite: its owners are composeHost_ / composeObject_

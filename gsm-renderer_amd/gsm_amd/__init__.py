@@ -175,6 +175,17 @@ class SceneObject:
     camera: CameraParams
 
 
+@dataclass
+class Style:
+    """gsm_global_style: one entry of a styled frame's table.  tint is (r, g, b) in the u8 colour space of the
+    projected gaussians; tint_amount 0 leaves the colour, 255 replaces it; opacity_scale 255 leaves the opacity, 0
+    removes the splat's tiles; hidden culls the gaussian."""
+    tint: tuple = (0, 0, 0)
+    tint_amount: int = 0
+    opacity_scale: int = 255
+    hidden: bool = False
+
+
 # ---------------------------------------------------------------------------
 # ctypes layer
 # ---------------------------------------------------------------------------
@@ -203,6 +214,15 @@ class _GlobalView(C.Structure):  # gsm_global_view
 
 class _GlobalObject(C.Structure):  # gsm_global_object
     _fields_ = [("input", _Input), ("camera", _Camera)]
+
+
+class _Style(C.Structure):  # gsm_global_style
+    _fields_ = [("tint_r", C.c_uint8), ("tint_g", C.c_uint8), ("tint_b", C.c_uint8), ("tint_amount", C.c_uint8),
+                ("opacity_scale", C.c_uint8), ("hidden", C.c_uint8), ("pad", C.c_uint8 * 2)]
+
+
+class _State(C.Structure):  # gsm_global_state
+    _fields_ = [("state", C.c_void_p), ("default_state", C.c_uint32), ("pad", C.c_uint32)]
 
 
 class _Counters(C.Structure):
@@ -263,6 +283,15 @@ _SIGNATURES = {
                                               C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
                                               C.c_size_t, C.c_void_p, C.c_size_t], C.c_int),
     "gsm_global_pick_owner": ([C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int),
+    "gsm_global_render_styled": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera), C.c_uint32,
+                                  C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                  C.POINTER(_State), C.POINTER(_Style), C.c_uint32], C.c_int),
+    "gsm_global_render_composite_styled": ([C.c_void_p, C.c_void_p, C.POINTER(_GlobalObject), C.c_uint32, C.c_uint32,
+                                            C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                            C.c_size_t, C.POINTER(_State), C.POINTER(_Style), C.c_uint32], C.c_int),
+    "gsm_global_select_mask": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera), C.c_uint32,
+                                C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(_Style), C.c_uint32,
+                                C.c_uint32, C.c_uint32, C.c_void_p], C.c_int),
     "gsm_global_render_stereo": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera),
                                   C.POINTER(_Camera), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                   C.c_void_p, C.c_size_t], C.c_int),
@@ -493,6 +522,25 @@ def _object_array(objects):
     return arr, n
 
 
+def _style_array(styles):
+    """(gsm_global_style array, count) of a Style list; (None, 0) for None (a NULL table, which the styled
+    entries refuse and the select takes as "no styles")."""
+    if styles is None:
+        return None, 0
+    arr = (_Style * max(len(styles), 1))()
+    for d, s in zip(arr, styles):
+        d.tint_r, d.tint_g, d.tint_b = (int(v) for v in s.tint)
+        d.tint_amount, d.opacity_scale, d.hidden = int(s.tint_amount), int(s.opacity_scale), 1 if s.hidden else 0
+    return arr, len(styles)
+
+
+def _state_struct(state) -> _State:
+    """gsm_global_state of a device byte tensor (its state array) or of an int (no array: that default)."""
+    if isinstance(state, int):
+        return _State(None, int(state), 0)
+    return _State(_ptr(state), 0, 0)
+
+
 class GlobalRenderer(_Renderer):
     """GlobalRenderer (GlobalRenderer.swift:72-572) on one HIP device."""
     _PREFIX, _STAGE_NAMES, _COUNTERS = "gsm_global", STAGES, _Counters
@@ -609,6 +657,66 @@ class GlobalRenderer(_Renderer):
                                                          int(height), _ptr(color_texture), cp, _ptr(depth_texture),
                                                          dp, _ptr(occluder), op)
         _check(st, "gsm_global_render_composite_occluded")
+
+    def render_styled(self, color_texture, depth_texture, pick_texture, input: GaussianInput, camera: CameraParams,
+                      width: int, height: int, state, styles, stream=None, color_pitch: Optional[int] = None,
+                      depth_pitch: Optional[int] = None, pick_pitch: Optional[int] = None,
+                      style_count: Optional[int] = None):
+        """gsm_global_render_styled: `render` (pick_texture None) or `render_pick` with the Style of every
+        gaussian's state applied in the projection.  state: a uint8 CUDA tensor, one byte per gaussian, or an int
+        (every gaussian's state); None passes a NULL gsm_global_state (the C entry's error path).  styles: a Style
+        list (None: a NULL table); style_count overrides its length."""
+        inp = _Input(_ptr(input.gaussians), _ptr(input.harmonics), int(input.gaussian_count),
+                     int(input.sh_components))
+        cam = _camera_struct(camera)
+        cp = color_pitch if color_pitch is not None else int(width) * self._bpp
+        dp = depth_pitch if depth_pitch is not None else int(width) * 2
+        pp = pick_pitch if pick_pitch is not None else int(width) * 4
+        arr, n = _style_array(styles)
+        st = _lib().gsm_global_render_styled(self._h, _stream_handle(stream), C.byref(inp), C.byref(cam), int(width),
+                                             int(height), _ptr(color_texture), cp, _ptr(depth_texture), dp,
+                                             _ptr(pick_texture), pp,
+                                             None if state is None else C.byref(_state_struct(state)), arr,
+                                             n if style_count is None else int(style_count))
+        _check(st, "gsm_global_render_styled")
+
+    def render_composite_styled(self, color_texture, depth_texture, pick_texture, objects, width: int, height: int,
+                                states, styles, stream=None, color_pitch: Optional[int] = None,
+                                depth_pitch: Optional[int] = None, pick_pitch: Optional[int] = None,
+                                style_count: Optional[int] = None):
+        """gsm_global_render_composite_styled: `render_composite` (pick_texture None) or `render_composite_pick`
+        with styles.  states: one entry per object, each a uint8 CUDA tensor or an int (the whole object's state);
+        None passes a NULL array."""
+        arr, n = _object_array(objects)
+        cp = color_pitch if color_pitch is not None else int(width) * self._bpp
+        dp = depth_pitch if depth_pitch is not None else int(width) * 2
+        pp = pick_pitch if pick_pitch is not None else int(width) * 4
+        sarr, sn = _style_array(styles)
+        starr = None
+        if states is not None:
+            starr = (_State * max(len(states), 1))(*[_state_struct(s) for s in states])
+        st = _lib().gsm_global_render_composite_styled(self._h, _stream_handle(stream), arr, n, int(width),
+                                                       int(height), _ptr(color_texture), cp, _ptr(depth_texture), dp,
+                                                       _ptr(pick_texture), pp, starr, sarr,
+                                                       sn if style_count is None else int(style_count))
+        _check(st, "gsm_global_render_composite_styled")
+
+    def select_mask(self, input: GaussianInput, camera: CameraParams, width: int, height: int, mask, state,
+                    and_mask: int, xor_mask: int, styles=None, matched=None, stream=None,
+                    mask_pitch: Optional[int] = None, style_count: Optional[int] = None):
+        """gsm_global_select_mask: the state byte of every gaussian whose projected centre lies on a nonzero byte
+        of `mask` (uint8 CUDA tensor, height rows of mask_pitch bytes) becomes (old & and_mask) ^ xor_mask; with
+        `styles`, gaussians whose current state is hidden are skipped.  matched: an int32 / uint32 CUDA tensor of
+        one element that receives the count.  input.harmonics may be None."""
+        inp = _Input(_ptr(input.gaussians), _ptr(input.harmonics), int(input.gaussian_count), 0)
+        cam = _camera_struct(camera)
+        mp = mask_pitch if mask_pitch is not None else int(width)
+        sarr, sn = _style_array(styles)
+        st = _lib().gsm_global_select_mask(self._h, _stream_handle(stream), C.byref(inp), C.byref(cam), int(width),
+                                           int(height), _ptr(mask), mp, _ptr(state), sarr,
+                                           sn if style_count is None else int(style_count),
+                                           int(and_mask) & 0xFFFFFFFF, int(xor_mask) & 0xFFFFFFFF, _ptr(matched))
+        _check(st, "gsm_global_select_mask")
 
     def pick_owner(self, items):
         """gsm_global_pick_owner: items of the last enqueued pick frame (any integer array, host) ->

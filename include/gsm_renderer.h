@@ -357,6 +357,98 @@ gsm_status gsm_global_render_composite_occluded(gsm_renderer *renderer, void *st
                                                 void *depth_r16f, size_t depth_pitch_bytes,
                                                 const void *occluder_r32f, size_t occluder_pitch_bytes);
 
+/* Per-gaussian styles (no reference analogue): gsm_global_render and gsm_global_render_composite
+ * with one state byte per gaussian and a table of at most 256 styles, so an application shows a selection --
+ * hides, highlights or fades splats -- without rewriting its scene.
+ *
+ * Rule.  A gaussian's state s is its byte of the state array, or default_state when the array is NULL.  Its style
+ * is S = styles[s] when s < style_count, otherwise the identity {tint_amount 0, opacity_scale 255, hidden 0}.  For
+ * a gaussian that passed every cull of the projection and formed its four u8 bytes (colour r, g, b and opacity of
+ * GaussianRenderData):
+ *   - S.hidden != 0: the gaussian is culled -- empty bounds (0, -1, 0, -1), no tiles, never listed, never picked;
+ *   - otherwise each colour byte c becomes (c * (255 - k) + t * k + 127) / 255, k = tint_amount, t the tint byte
+ *     of that channel, and the opacity byte o becomes (o * opacity_scale + 127) / 255, in unsigned integers.
+ * Everything after that point is the plain frame applied to the styled bytes: the tile test's level, the blend
+ * record's fp16 colour and opacity, the skip band, the sort and the blend.  An opacity byte of 0 gives the
+ * gaussian no tiles but leaves it visible (its bounds stay).  So: with every reachable style the identity (or every
+ * state at or above style_count) the bytes equal the plain entry's; with only hidden styles in use the colour and
+ * depth equal gsm_global_render of the scene with the hidden gaussians removed.
+ *
+ * pick_r32u may be NULL: the frame then uses the plain blend and pick_pitch_bytes is ignored.  Non-NULL: the pick
+ * frame above, and gsm_global_pick_owner works after it.  `styles`, `state` / `states` (the structs) are host
+ * memory, consumed before the call returns; the state arrays are device memory the frame only reads.  A composite
+ * takes one gsm_global_state per object: {NULL, 1} highlights or hides an object as a whole.
+ *
+ * Checks: the plain entry's (the pick entry's when pick_r32u is non-NULL), in its order; then
+ *   GSM_ERR_INVALID_ARGUMENT  styles NULL, style_count 0 or above 256, state / states NULL, or a default_state
+ *                             above 255 (the lowest object index decides);
+ *   GSM_ERR_UNSUPPORTED       the handle is restricted to tile rows (gsm_global_set_tile_rows).
+ * Enqueue-only and capturable; a captured frame replays the table and the state pointers it was captured with.
+ * Nothing is allocated per frame (the handle's first styled frame allocates the 2 KiB table).
+ * gsm_global_render_views, gsm_global_render_batch, the occluded entries, the DepthFirst and Local renderers and
+ * the multi-GPU frame have no styled entry; a style changes neither position nor scale. */
+typedef struct {
+    uint8_t tint_r, tint_g, tint_b; /* in the u8 colour space of GaussianRenderData: after the SH evaluation and,
+                                       for gaussian_color_space SRGB, after the decode to linear */
+    uint8_t tint_amount;            /* 0: colour unchanged ... 255: colour replaced by the tint */
+    uint8_t opacity_scale;          /* 255: opacity unchanged ... 0: opacity byte 0 */
+    uint8_t hidden;                 /* nonzero: the gaussian is culled */
+    uint8_t pad[2];                 /* ignored */
+} gsm_global_style;
+typedef struct {
+    const uint8_t *state;   /* device memory, one byte per gaussian of the scene, or NULL */
+    uint32_t default_state; /* 0..255: every gaussian's state when `state` is NULL; ignored otherwise */
+    uint32_t pad;
+} gsm_global_state;
+#ifdef __cplusplus
+static_assert(sizeof(gsm_global_style) == 8, "gsm_global_style is 8 bytes");
+static_assert(sizeof(gsm_global_state) == 16, "gsm_global_state is 16 bytes");
+#else
+_Static_assert(sizeof(gsm_global_style) == 8, "gsm_global_style is 8 bytes");
+_Static_assert(sizeof(gsm_global_state) == 16, "gsm_global_state is 16 bytes");
+#endif
+gsm_status gsm_global_render_styled(gsm_renderer *renderer, void *stream, const gsm_gaussian_input *input,
+                                    const gsm_camera_params *camera, uint32_t width, uint32_t height,
+                                    void *color, size_t color_pitch_bytes, void *depth_r16f,
+                                    size_t depth_pitch_bytes, void *pick_r32u, size_t pick_pitch_bytes,
+                                    const gsm_global_state *state, const gsm_global_style *styles,
+                                    uint32_t style_count);
+gsm_status gsm_global_render_composite_styled(gsm_renderer *renderer, void *stream,
+                                              const gsm_global_object *objects, uint32_t object_count,
+                                              uint32_t width, uint32_t height,
+                                              void *color, size_t color_pitch_bytes,
+                                              void *depth_r16f, size_t depth_pitch_bytes,
+                                              void *pick_r32u, size_t pick_pitch_bytes,
+                                              const gsm_global_state *states /* [object_count] */,
+                                              const gsm_global_style *styles, uint32_t style_count);
+
+/* Selection by a screen mask: "every splat whose centre lies under these pixels" -- rectangle, brush
+ * and lasso selection -- on the device, into the state array the styled frames read.
+ *
+ * Gaussian g < gaussian_count matches when (1) it passes every cull of the projection for camera, width, height
+ * (input.harmonics is not read and may be NULL, sh_components is ignored); (2) `styles` is NULL or the style of its
+ * current state byte is not hidden; (3) mx and my, the fp16 mean of its GaussianRenderData, are finite; (4) px =
+ * floor(mx + 0.5) lies in [0, width), py = floor(my + 0.5) in [0, height), and the mask byte at (px, py) is
+ * nonzero.  A matching gaussian's state becomes ((old & and_mask) ^ xor_mask) & 0xFF -- set a bit (and ~b, xor b),
+ * clear it (and ~b, xor 0), toggle it (and 0xFF, xor b), assign (and 0, xor v); every other byte of `state`, and
+ * every byte at or past gaussian_count, keeps its value.  `matched` (device, nullable) receives the number of
+ * matching gaussians: it is overwritten, not added to.  mask_u8: device memory, height rows of mask_pitch_bytes.
+ * For a composite, call it once per object with that object's camera.  Enqueue-only and capturable.
+ *
+ * Checks, in this order:
+ *   GSM_ERR_INVALID_GAUSSIAN_COUNT   gaussian_count > max_gaussians;
+ *   GSM_ERR_INVALID_DIMENSIONS       width or height zero, or above max_width / max_height;
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  input, camera or mask_u8 NULL; gaussians or state NULL with a count > 0;
+ *   GSM_ERR_INVALID_BUFFER_SIZE      mask_pitch_bytes < width, or matched not 4-byte aligned;
+ *   GSM_ERR_INVALID_ARGUMENT         styles NULL with style_count != 0, or styles non-NULL with style_count 0 or
+ *                                    above 256.
+ * A count of 0 is a no-op that writes *matched = 0. */
+gsm_status gsm_global_select_mask(gsm_renderer *renderer, void *stream, const gsm_gaussian_input *input,
+                                  const gsm_camera_params *camera, uint32_t width, uint32_t height,
+                                  const void *mask_u8, size_t mask_pitch_bytes, uint8_t *state,
+                                  const gsm_global_style *styles, uint32_t style_count,
+                                  uint32_t and_mask, uint32_t xor_mask, uint32_t *matched);
+
 /* GlobalRenderer.renderStereo (GlobalRenderer.swift:240-255) calls fatalError for
  * every target; this entry returns GSM_ERR_UNSUPPORTED instead. */
 gsm_status gsm_global_render_stereo(gsm_renderer *renderer, void *stream,
