@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "../../include/gsm_debug.h"
 #include "../../include/gsm_renderer.h"
@@ -181,32 +182,51 @@ static int blend_waves_per_wg(uint32_t numTiles, int numCUs) {
 
 
 
+// (waves, P) -> f(std::integral_constant<int, NTH>, std::integral_constant<int, PP>, grid) for every k_blend_px*
+// launch: 16 or 12 waves of 64 lanes, 8 for anything else; one workgroup per `waves` units, at most one per CU
+template <class F>
+static void dispatch_blend(int waves, int P, uint32_t numTiles, int numCUs, F&& f) {
+    const uint32_t units = numTiles * (4u / (uint32_t)P);
+    uint32_t grid = (units + (uint32_t)waves - 1) / (uint32_t)waves;
+    if (grid > (uint32_t)numCUs) grid = (uint32_t)numCUs;
+    auto by_waves = [&](auto pp) {
+        if (waves == 16) f(std::integral_constant<int, 1024>{}, pp, grid);
+        else if (waves == 12) f(std::integral_constant<int, 768>{}, pp, grid);
+        else f(std::integral_constant<int, 512>{}, pp, grid);
+    };
+    if (P == 1) by_waves(std::integral_constant<int, 1>{});
+    else by_waves(std::integral_constant<int, 2>{});
+}
+
 // Measured schedule choices: units longest-first by last frame's walk (costOrder;
 // 1080p 8 waves 293 -> 248 us, 4K 16 waves 703 -> 660), the longest on one top-priority wave per
 // SIMD (flags bit 2), later units' priority rising with the age of their walk (flags bit 1).
-int launch_blend(const FrameGeometry& g, const DeviceArena& A, void* color,
-                  size_t colorPitch, void* depth, size_t depthPitch, int numCUs, bool costOrder, int colorFormat,
-                  hipStream_t s, int wavesOverride, int claim, const MgArrive* arrive, bool pairs, void* pick,
-                  size_t pickPitch, const void* occluder, size_t occluderPitch, const uint32_t* sortedVals) {
+int launch_blend(const FrameGeometry& g, const DeviceArena& A, const FrameTargets& t, const BlendOptions& o,
+                 hipStream_t s) {
     // local tile ids: tile t = k * tilesX + tx of the renderer's row k (pixel row rowBegin + k * rowStride)
     // (a batch of views: views * tilesPerView tiles, every rule below takes the batch's count)
     const uint32_t numTiles = frame_tiles(g);
     if (numTiles == 0) return 0;
-    const uint32_t t0 = 0;
-    // (a batch's later views start view strides after the first: the wide stores need those aligned too)
-    const bool strides = g.views > 1;
+    uint8_t* const color = (uint8_t*)t.color;
+    uint8_t* const depth = (uint8_t*)t.depth;
+    const size_t colorPitch = t.colorPitch, depthPitch = t.depthPitch;
+    const int numCUs = o.numCUs;
+    // (a Views frame's later views start view strides after the first: the wide stores need those aligned too)
+    const bool strides = g.kind == FrameKind::Views && g.views > 1;
     const int vec = ((((uintptr_t)color) & 15u) == 0 && (colorPitch & 15u) == 0 &&
                      (!strides || (g.colorViewStride & 15u) == 0) &&
                      (depth == nullptr || ((((uintptr_t)depth) & 7u) == 0 && (depthPitch & 7u) == 0 &&
                                            (!strides || (g.depthViewStride & 7u) == 0))))
                         ? 1
                         : 0;
-    const int flags = vec | 2 | (costOrder ? 4 : 0) | ((colorFormat & 15) << 4) | ((claim & 3) << 8) |
-                      (arrive ? 4096 : 0) |  // (a gathered multi-GPU frame: the L2 write-back at exit)
+    const int flags = vec | 2 | (o.costOrder ? 4 : 0) | ((o.colorFormat & 15) << 4) | ((o.claim & 3) << 8) |
+                      (o.arrive ? 4096 : 0) |  // (a gathered multi-GPU frame: the L2 write-back at exit)
                       ((depth && (((uintptr_t)depth) & 15u) == 0 && (depthPitch & 15u) == 0) ? 2048 : 0);
     // A.tileQueue was zeroed by k_scan_blocks earlier in the frame
     const int P = blend_pairs_per_lane(numTiles, numCUs);
-    const int waves = wavesOverride ? wavesOverride : blend_waves_per_wg(numTiles, numCUs);
+    const int waves = o.waves ? o.waves : blend_waves_per_wg(numTiles, numCUs);
+    const uint32_t* order = o.costOrder ? A.unitOrder : nullptr;
+    const int kernel = P == 1 ? GSM_BLEND_KERNEL_QUADRANT : GSM_BLEND_KERNEL_HALF_TILE;
     // One GPU's half-tile frame with >= 6 units per wave slot (16 waves per CU: the 4K frame): two units
     // per wave (r05, k_blend_pw).  The pairs cut the VALU work (-10 %) but halve the waves walking: a gain
     // where the walk is VALU-bound (config 3: blend 370 -> 327 us), a loss where it is bound by its
@@ -214,125 +234,72 @@ int launch_blend(const FrameGeometry& g, const DeviceArena& A, void* color,
     // A pick frame: the single frame's walk that also writes the pick target -- quadrant or
     // half-tile units by the rule above, no compaction, no pair walk.  (Whole frames of one GPU only: the host
     // refuses tile rows, and no batch or gathered frame has a pick entry.)
-    if (pick) {
-        const uint32_t punits = numTiles * (4u / (uint32_t)P);
-        uint32_t pgrid = (punits + (uint32_t)waves - 1) / (uint32_t)waves;
-        if (pgrid > (uint32_t)numCUs) pgrid = (uint32_t)numCUs;
+    if (o.pick) {
+        uint8_t* const pick = (uint8_t*)o.pick->pixels;
+        const size_t pickPitch = o.pick->pitch;
         const int pflags = flags | (((((uintptr_t)pick) & 7u) == 0 && (pickPitch & 7u) == 0) ? 8192 : 0);
-#define GSM_LAUNCH_BLEND_PICK(NTH, PP)                                                                                \
-    hipLaunchKernelGGL((k_blend_px_pick<NTH, PP, false>), dim3(pgrid), dim3(NTH), 0, s, A.tileStart, A.rec,          \
-                       A.expTable, A.tileQueue, numTiles, g.tilesX, g.width, g.height, (uint8_t*)color, colorPitch,  \
-                       (uint8_t*)depth, depthPitch, (uint8_t*)pick, pickPitch, pflags,                               \
-                       costOrder ? A.unitOrder : nullptr, A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1],    \
-                       A.halfCount, g.tileCount, A.costMax)
-        if (P == 1) {
-            if (waves == 16) GSM_LAUNCH_BLEND_PICK(1024, 1);
-            else if (waves == 12) GSM_LAUNCH_BLEND_PICK(768, 1);
-            else GSM_LAUNCH_BLEND_PICK(512, 1);
-        } else {
-            if (waves == 16) GSM_LAUNCH_BLEND_PICK(1024, 2);
-            else if (waves == 12) GSM_LAUNCH_BLEND_PICK(768, 2);
-            else GSM_LAUNCH_BLEND_PICK(512, 2);
-        }
-#undef GSM_LAUNCH_BLEND_PICK
-        return P == 1 ? GSM_BLEND_KERNEL_QUADRANT : GSM_BLEND_KERNEL_HALF_TILE;
+        dispatch_blend(waves, P, numTiles, numCUs, [&](auto NTH, auto PP, uint32_t grid) {
+            hipLaunchKernelGGL((k_blend_px_pick<decltype(NTH)::value, decltype(PP)::value, false>), dim3(grid),
+                               dim3(decltype(NTH)::value), 0, s, A.tileStart, A.rec, A.expTable, A.tileQueue, numTiles,
+                               g.tilesX, g.width, g.height, color, colorPitch, depth, depthPitch, pick, pickPitch,
+                               pflags, order, A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1], A.halfCount,
+                               g.tileCount, A.costMax);
+        });
+        return kernel;
     }
     // An occluded frame: the same units and the same rules, the walk cut at the occluder -- no
     // compaction, no pair walk; whole frames of one GPU only.  It walks the tiles' whole sorted runs (sortedVals,
     // the values with their skip flags), which the host makes the sort keep for such a frame.
-    if (occluder) {
-        if (!sortedVals) return 0;  // (the host passes them with every occluder)
-        const uint32_t ounits = numTiles * (4u / (uint32_t)P);
-        uint32_t ogrid = (ounits + (uint32_t)waves - 1) / (uint32_t)waves;
-        if (ogrid > (uint32_t)numCUs) ogrid = (uint32_t)numCUs;
+    if (o.occluder) {
+        if (!o.sortedVals) return 0;  // (the host passes them with every occluder)
+        const uint8_t* const occluder = (const uint8_t*)o.occluder->pixels;
+        const size_t occluderPitch = o.occluder->pitch;
         const int oflags = flags | (((((uintptr_t)occluder) & 7u) == 0 && (occluderPitch & 7u) == 0) ? 16384 : 0);
-#define GSM_LAUNCH_BLEND_OCC(NTH, PP)                                                                                 \
-    hipLaunchKernelGGL((k_blend_px_occ<NTH, PP, false>), dim3(ogrid), dim3(NTH), 0, s, A.tileStart, A.rec,           \
-                       A.expTable, A.tileQueue, numTiles, g.tilesX, g.width, g.height, (uint8_t*)color, colorPitch,  \
-                       (uint8_t*)depth, depthPitch, (const uint8_t*)occluder, occluderPitch, oflags,                 \
-                       costOrder ? A.unitOrder : nullptr, A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1],    \
-                       A.halfCount, g.tileCount, A.costMax, sortedVals)
-        if (P == 1) {
-            if (waves == 16) GSM_LAUNCH_BLEND_OCC(1024, 1);
-            else if (waves == 12) GSM_LAUNCH_BLEND_OCC(768, 1);
-            else GSM_LAUNCH_BLEND_OCC(512, 1);
-        } else {
-            if (waves == 16) GSM_LAUNCH_BLEND_OCC(1024, 2);
-            else if (waves == 12) GSM_LAUNCH_BLEND_OCC(768, 2);
-            else GSM_LAUNCH_BLEND_OCC(512, 2);
-        }
-#undef GSM_LAUNCH_BLEND_OCC
-        return P == 1 ? GSM_BLEND_KERNEL_QUADRANT : GSM_BLEND_KERNEL_HALF_TILE;
+        dispatch_blend(waves, P, numTiles, numCUs, [&](auto NTH, auto PP, uint32_t grid) {
+            hipLaunchKernelGGL((k_blend_px_occ<decltype(NTH)::value, decltype(PP)::value, false>), dim3(grid),
+                               dim3(decltype(NTH)::value), 0, s, A.tileStart, A.rec, A.expTable, A.tileQueue, numTiles,
+                               g.tilesX, g.width, g.height, color, colorPitch, depth, depthPitch, occluder,
+                               occluderPitch, oflags, order, A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1],
+                               A.halfCount, g.tileCount, A.costMax, o.sortedVals);
+        });
+        return kernel;
     }
-    if (pairs && P == 2 && !arrive && waves == 16) {
-        launch_blend_pw(g, A, color, colorPitch, depth, depthPitch, numCUs, costOrder, colorFormat, s, waves);
+    if (o.pairs && P == 2 && !o.arrive && waves == 16) {
+        BlendOptions po = o;
+        po.waves = waves;
+        launch_blend_pw(g, A, t, po, s);
         return GSM_BLEND_KERNEL_PAIR_WALK;
     }
-    const uint32_t units = numTiles * (4u / (uint32_t)P);
-    uint32_t grid = (units + (uint32_t)waves - 1) / (uint32_t)waves;
-    if (grid > (uint32_t)numCUs) grid = (uint32_t)numCUs;
-    const uint32_t* order = costOrder ? A.unitOrder : nullptr;
-    MgArrive ar{};
-    if (arrive) {
-        ar = *arrive;
-        ar.total = grid;  // every workgroup arrives once, at its exit
-    }
-#define GSM_LAUNCH_BLEND(NTH, PP, CMP)                                                                       \
-    hipLaunchKernelGGL((k_blend_px<NTH, PP, CMP>), dim3(grid), dim3(NTH), 0, s, A.tileStart, A.rec, \
-                       A.expTable, A.tileQueue, t0, numTiles, g.tilesX, g.width, g.height,          \
-                       (uint8_t*)color, colorPitch, (uint8_t*)depth, depthPitch, flags, order, A.unitCost,  \
-                       A.blendTrace, A.halfVals[0], A.halfVals[1], A.halfCount, g.tileCount, A.costMax, \
-                       g.rowBegin, g.rowStride, ar)
-#define GSM_LAUNCH_BLEND_VIEWS(NTH, PP, CMP)                                                                      \
-    hipLaunchKernelGGL((k_blend_px_views<NTH, PP, CMP>), dim3(grid), dim3(NTH), 0, s, A.tileStart, A.rec, A.expTable, \
-                       A.tileQueue, numTiles, g.tilesX, g.tilesPerView, g.width, g.height, (uint8_t*)color,           \
-                       colorPitch, g.colorViewStride, (uint8_t*)depth, depthPitch, g.depthViewStride, flags, order,   \
-                       A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1], A.halfCount, g.tileCount, A.costMax)
-    // a batch of different views: the targets, sizes and store widths are per view (BatchTarget);
-    // the kernel's flags keep what the batch shares
-#define GSM_LAUNCH_BLEND_BATCH(NTH, PP, CMP)                                                                       \
-    hipLaunchKernelGGL((k_blend_px_batch<NTH, PP, CMP>), dim3(grid), dim3(NTH), 0, s, A.tileStart, A.rec, A.expTable, \
-                       A.tileQueue, numTiles, (const BatchViewArgs*)g.batchArgs, g.batchTileView, flags & ~(1 | 2048), \
-                       order, A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1], A.halfCount, g.tileCount,       \
-                       A.costMax)
-    if (g.batchTiles) {
-        if (P == 1) {
-            if (waves == 16) GSM_LAUNCH_BLEND_BATCH(1024, 1, false);
-            else if (waves == 12) GSM_LAUNCH_BLEND_BATCH(768, 1, false);
-            else GSM_LAUNCH_BLEND_BATCH(512, 1, false);
+    // half tiles (P == 2: CMP) compact to one pair per lane once <= 16 of their 32 groups are alive
+    dispatch_blend(waves, P, numTiles, numCUs, [&](auto NTH, auto PP, uint32_t grid) {
+        constexpr int kNth = decltype(NTH)::value, kP = decltype(PP)::value;
+        constexpr bool kCmp = kP == 2;
+        if (g.kind == FrameKind::Batch) {
+            //  the targets, sizes and store widths are per view (BatchTarget); the kernel's flags
+            // keep what the batch shares
+            hipLaunchKernelGGL((k_blend_px_batch<kNth, kP, kCmp>), dim3(grid), dim3(kNth), 0, s, A.tileStart, A.rec,
+                               A.expTable, A.tileQueue, numTiles, (const BatchViewArgs*)g.batchArgs, g.batchTileView,
+                               flags & ~(1 | 2048), order, A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1],
+                               A.halfCount, g.tileCount, A.costMax);
+        } else if (g.kind == FrameKind::Views) {
+            hipLaunchKernelGGL((k_blend_px_views<kNth, kP, kCmp>), dim3(grid), dim3(kNth), 0, s, A.tileStart, A.rec,
+                               A.expTable, A.tileQueue, numTiles, g.tilesX, g.tilesPerView, g.width, g.height, color,
+                               colorPitch, g.colorViewStride, depth, depthPitch, g.depthViewStride, flags, order,
+                               A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1], A.halfCount, g.tileCount,
+                               A.costMax);
         } else {
-            if (waves == 16) GSM_LAUNCH_BLEND_BATCH(1024, 2, true);
-            else if (waves == 12) GSM_LAUNCH_BLEND_BATCH(768, 2, true);
-            else GSM_LAUNCH_BLEND_BATCH(512, 2, true);
+            MgArrive ar{};
+            if (o.arrive) {
+                ar = *o.arrive;
+                ar.total = grid;  // every workgroup arrives once, at its exit
+            }
+            hipLaunchKernelGGL((k_blend_px<kNth, kP, kCmp>), dim3(grid), dim3(kNth), 0, s, A.tileStart, A.rec,
+                               A.expTable, A.tileQueue, 0u, numTiles, g.tilesX, g.width, g.height, color, colorPitch,
+                               depth, depthPitch, flags, order, A.unitCost, A.blendTrace, A.halfVals[0],
+                               A.halfVals[1], A.halfCount, g.tileCount, A.costMax, g.rowBegin, g.rowStride, ar);
         }
-        return P == 1 ? GSM_BLEND_KERNEL_QUADRANT : GSM_BLEND_KERNEL_HALF_TILE;
-    }
-#undef GSM_LAUNCH_BLEND_BATCH
-    if (g.views) {
-        if (P == 1) {
-            if (waves == 16) GSM_LAUNCH_BLEND_VIEWS(1024, 1, false);
-            else if (waves == 12) GSM_LAUNCH_BLEND_VIEWS(768, 1, false);
-            else GSM_LAUNCH_BLEND_VIEWS(512, 1, false);
-        } else {
-            if (waves == 16) GSM_LAUNCH_BLEND_VIEWS(1024, 2, true);
-            else if (waves == 12) GSM_LAUNCH_BLEND_VIEWS(768, 2, true);
-            else GSM_LAUNCH_BLEND_VIEWS(512, 2, true);
-        }
-        return P == 1 ? GSM_BLEND_KERNEL_QUADRANT : GSM_BLEND_KERNEL_HALF_TILE;
-    }
-#undef GSM_LAUNCH_BLEND_VIEWS
-    // half tiles compact to one pair per lane once <= 16 of their 32 groups are alive
-    if (P == 1) {
-        if (waves == 16) GSM_LAUNCH_BLEND(1024, 1, false);
-        else if (waves == 12) GSM_LAUNCH_BLEND(768, 1, false);
-        else GSM_LAUNCH_BLEND(512, 1, false);
-    } else {
-        if (waves == 16) GSM_LAUNCH_BLEND(1024, 2, true);
-        else if (waves == 12) GSM_LAUNCH_BLEND(768, 2, true);
-        else GSM_LAUNCH_BLEND(512, 2, true);
-    }
-#undef GSM_LAUNCH_BLEND
-    return P == 1 ? GSM_BLEND_KERNEL_QUADRANT : GSM_BLEND_KERNEL_HALF_TILE;
+    });
+    return kernel;
 }
 
 }  // namespace gsm

@@ -150,11 +150,17 @@ __device__ __forceinline__ void pw_write_pair(const PwTarget& t, uint32_t px, ui
 
 
 // the pair walk for a frame of half-tile units on one GPU (no multi-GPU gather); `waves` per workgroup
-void launch_blend_pw(const FrameGeometry& g, const DeviceArena& A, void* color, size_t colorPitch, void* depth,
-                     size_t depthPitch, int numCUs, bool costOrder, int colorFormat, hipStream_t s, int waves) {
+void launch_blend_pw(const FrameGeometry& g, const DeviceArena& A, const FrameTargets& t, const BlendOptions& o,
+                     hipStream_t s) {
     const uint32_t numTiles = frame_tiles(g);
     if (numTiles == 0) return;
-    const bool strides = g.views > 1;  // (a batch's later views: the wide stores need the view strides aligned too)
+    void* const color = t.color;
+    void* const depth = t.depth;
+    const size_t colorPitch = t.colorPitch, depthPitch = t.depthPitch;
+    const int numCUs = o.numCUs, colorFormat = o.colorFormat, waves = o.waves;
+    const bool costOrder = o.costOrder;
+    // (a Views frame's later views: the wide stores need the view strides aligned too)
+    const bool strides = g.kind == FrameKind::Views && g.views > 1;
     const int vec = ((((uintptr_t)color) & 15u) == 0 && (colorPitch & 15u) == 0 &&
                      (!strides || (g.colorViewStride & 15u) == 0) &&
                      (depth == nullptr || ((((uintptr_t)depth) & 3u) == 0 && (depthPitch & 3u) == 0 &&
@@ -185,14 +191,14 @@ void launch_blend_pw(const FrameGeometry& g, const DeviceArena& A, void* color, 
                        A.tileQueue, numTiles, (const BatchViewArgs*)g.batchArgs, g.batchTileView, tg.flags & ~1,     \
                        order, A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1], A.halfCount, g.tileCount,      \
                        A.costMax, flags)
-    if (g.batchTiles) {
+    if (g.kind == FrameKind::Batch) {
         if (waves >= 16) GSM_LAUNCH_PW_BATCH(1024);
         else if (waves >= 12) GSM_LAUNCH_PW_BATCH(768);
         else GSM_LAUNCH_PW_BATCH(512);
         return;
     }
 #undef GSM_LAUNCH_PW_BATCH
-    if (g.views) {
+    if (g.kind == FrameKind::Views) {
         if (waves >= 16) GSM_LAUNCH_PW_VIEWS(1024);
         else if (waves >= 12) GSM_LAUNCH_PW_VIEWS(768);
         else GSM_LAUNCH_PW_VIEWS(512);

@@ -77,8 +77,8 @@ gsm_status gsm_global_render(gsm_renderer* r, void* stream, const gsm_gaussian_i
                              const gsm_camera_params* camera, uint32_t width, uint32_t height,
                              void* color, size_t color_pitch, void* depth, size_t depth_pitch) {
     if (!r || !r->impl || !input || !camera) return GSM_ERR_INVALID_ARGUMENT;
-    return r->impl->render((hipStream_t)stream, *input, *camera, width, height, color, color_pitch,
-                           depth, depth_pitch);
+    return r->impl->renderFrame((hipStream_t)stream, *input, *camera, width, height,
+                                gsm::FrameTargets{color, color_pitch, depth, depth_pitch});
 }
 
 gsm_status gsm_global_render_views(gsm_renderer* r, void* stream, const gsm_gaussian_input* input,
@@ -99,8 +99,8 @@ gsm_status gsm_global_render_composite(gsm_renderer* r, void* stream, const gsm_
                                        uint32_t object_count, uint32_t width, uint32_t height, void* color,
                                        size_t color_pitch, void* depth, size_t depth_pitch) {
     if (!r || !r->impl) return GSM_ERR_INVALID_ARGUMENT;
-    return r->impl->renderComposite((hipStream_t)stream, objects, object_count, width, height, color, color_pitch,
-                                    depth, depth_pitch);
+    return r->impl->composeFrame((hipStream_t)stream, objects, object_count, width, height,
+                                 gsm::FrameTargets{color, color_pitch, depth, depth_pitch});
 }
 
 gsm_status gsm_global_render_pick(gsm_renderer* r, void* stream, const gsm_gaussian_input* input,
@@ -108,8 +108,11 @@ gsm_status gsm_global_render_pick(gsm_renderer* r, void* stream, const gsm_gauss
                                   size_t color_pitch, void* depth, size_t depth_pitch, void* pick,
                                   size_t pick_pitch) {
     if (!r || !r->impl || !input || !camera) return GSM_ERR_INVALID_ARGUMENT;
-    return r->impl->renderPick((hipStream_t)stream, *input, *camera, width, height, color, color_pitch, depth,
-                               depth_pitch, pick, pick_pitch);
+    const gsm::PickTarget pt{pick, pick_pitch};
+    gsm::FrameExtras extras;
+    extras.pick = &pt;
+    return r->impl->renderFrame((hipStream_t)stream, *input, *camera, width, height,
+                                gsm::FrameTargets{color, color_pitch, depth, depth_pitch}, extras);
 }
 
 gsm_status gsm_global_render_composite_pick(gsm_renderer* r, void* stream, const gsm_global_object* objects,
@@ -117,8 +120,11 @@ gsm_status gsm_global_render_composite_pick(gsm_renderer* r, void* stream, const
                                             size_t color_pitch, void* depth, size_t depth_pitch, void* pick,
                                             size_t pick_pitch) {
     if (!r || !r->impl) return GSM_ERR_INVALID_ARGUMENT;
-    return r->impl->renderCompositePick((hipStream_t)stream, objects, object_count, width, height, color,
-                                        color_pitch, depth, depth_pitch, pick, pick_pitch);
+    const gsm::PickTarget pt{pick, pick_pitch};
+    gsm::FrameExtras extras;
+    extras.pick = &pt;
+    return r->impl->composeFrame((hipStream_t)stream, objects, object_count, width, height,
+                                 gsm::FrameTargets{color, color_pitch, depth, depth_pitch}, extras);
 }
 
 gsm_status gsm_global_render_occluded(gsm_renderer* r, void* stream, const gsm_gaussian_input* input,
@@ -126,8 +132,11 @@ gsm_status gsm_global_render_occluded(gsm_renderer* r, void* stream, const gsm_g
                                       size_t color_pitch, void* depth, size_t depth_pitch, const void* occluder,
                                       size_t occluder_pitch) {
     if (!r || !r->impl || !input || !camera) return GSM_ERR_INVALID_ARGUMENT;
-    return r->impl->renderOccluded((hipStream_t)stream, *input, *camera, width, height, color, color_pitch, depth,
-                                   depth_pitch, occluder, occluder_pitch);
+    const gsm::OccluderSource os{occluder, occluder_pitch};
+    gsm::FrameExtras extras;
+    extras.occluder = &os;
+    return r->impl->renderFrame((hipStream_t)stream, *input, *camera, width, height,
+                                gsm::FrameTargets{color, color_pitch, depth, depth_pitch}, extras);
 }
 
 gsm_status gsm_global_render_composite_occluded(gsm_renderer* r, void* stream, const gsm_global_object* objects,
@@ -135,8 +144,11 @@ gsm_status gsm_global_render_composite_occluded(gsm_renderer* r, void* stream, c
                                                 size_t color_pitch, void* depth, size_t depth_pitch,
                                                 const void* occluder, size_t occluder_pitch) {
     if (!r || !r->impl) return GSM_ERR_INVALID_ARGUMENT;
-    return r->impl->renderCompositeOccluded((hipStream_t)stream, objects, object_count, width, height, color,
-                                            color_pitch, depth, depth_pitch, occluder, occluder_pitch);
+    const gsm::OccluderSource os{occluder, occluder_pitch};
+    gsm::FrameExtras extras;
+    extras.occluder = &os;
+    return r->impl->composeFrame((hipStream_t)stream, objects, object_count, width, height,
+                                 gsm::FrameTargets{color, color_pitch, depth, depth_pitch}, extras);
 }
 
 gsm_status gsm_global_render_styled(gsm_renderer* r, void* stream, const gsm_gaussian_input* input,
@@ -145,8 +157,13 @@ gsm_status gsm_global_render_styled(gsm_renderer* r, void* stream, const gsm_gau
                                     const gsm_global_state* state, const gsm_global_style* styles,
                                     uint32_t style_count) {
     if (!r || !r->impl || !input || !camera) return GSM_ERR_INVALID_ARGUMENT;
-    return r->impl->renderStyled((hipStream_t)stream, *input, *camera, width, height, color, color_pitch, depth,
-                                 depth_pitch, pick, pick_pitch, state, styles, style_count);
+    const gsm::PickTarget pt{pick, pick_pitch};
+    const gsm::StyleSource ss{state, styles, style_count};
+    gsm::FrameExtras extras;
+    extras.pick = pick ? &pt : nullptr;  // (a null pick pointer: the plain blend)
+    extras.style = &ss;
+    return r->impl->renderFrame((hipStream_t)stream, *input, *camera, width, height,
+                                gsm::FrameTargets{color, color_pitch, depth, depth_pitch}, extras);
 }
 
 gsm_status gsm_global_render_composite_styled(gsm_renderer* r, void* stream, const gsm_global_object* objects,
@@ -155,9 +172,13 @@ gsm_status gsm_global_render_composite_styled(gsm_renderer* r, void* stream, con
                                               size_t pick_pitch, const gsm_global_state* states,
                                               const gsm_global_style* styles, uint32_t style_count) {
     if (!r || !r->impl) return GSM_ERR_INVALID_ARGUMENT;
-    return r->impl->renderCompositeStyled((hipStream_t)stream, objects, object_count, width, height, color,
-                                          color_pitch, depth, depth_pitch, pick, pick_pitch, states, styles,
-                                          style_count);
+    const gsm::PickTarget pt{pick, pick_pitch};
+    const gsm::StyleSource ss{states, styles, style_count};
+    gsm::FrameExtras extras;
+    extras.pick = pick ? &pt : nullptr;  // (a null pick pointer: the plain blend)
+    extras.style = &ss;
+    return r->impl->composeFrame((hipStream_t)stream, objects, object_count, width, height,
+                                 gsm::FrameTargets{color, color_pitch, depth, depth_pitch}, extras);
 }
 
 gsm_status gsm_global_select_mask(gsm_renderer* r, void* stream, const gsm_gaussian_input* input,
@@ -199,13 +220,13 @@ gsm_status gsm_global_render_stereo_sbs(gsm_renderer* r, void* stream, const gsm
                                         void* depth, size_t depth_pitch) {
     if (!r || !r->impl || !input || !left || !right) return GSM_ERR_INVALID_ARGUMENT;
     if (!color) return GSM_ERR_MISSING_REQUIRED_BUFFER;
-    gsm_status st = r->impl->render((hipStream_t)stream, *input, *left, width_per_eye, height, color,
-                                    color_pitch, depth, depth_pitch);
+    gsm_status st = r->impl->renderFrame((hipStream_t)stream, *input, *left, width_per_eye, height,
+                                         gsm::FrameTargets{color, color_pitch, depth, depth_pitch});
     if (st != GSM_OK) return st;
     char* rc = (char*)color + (size_t)width_per_eye * 8;
     char* rd = depth ? (char*)depth + (size_t)width_per_eye * 2 : nullptr;
-    return r->impl->render((hipStream_t)stream, *input, *right, width_per_eye, height, rc, color_pitch, rd,
-                           depth_pitch);
+    return r->impl->renderFrame((hipStream_t)stream, *input, *right, width_per_eye, height,
+                                gsm::FrameTargets{rc, color_pitch, rd, depth_pitch});
 }
 
 gsm_status gsm_global_render_stereo(gsm_renderer* r, void*, const gsm_gaussian_input*,

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "gsm_host.h"
 #include "gsm_types.h"
 
 namespace gsm {
@@ -125,6 +126,26 @@ struct ComposeFrame {
     uint32_t blocks = 0;   // projection / scatter blocks: sum of ceil(count_o / 256)
     const ComposeObjectArgs* args = nullptr;   // device, [entries]
     const uint16_t* blockObject = nullptr;     // device, [blocks]: the entry of every block
+};
+
+// The kind of a Global frame and that kind's payload.  Only `kind` says which payload is live: read one through
+// its accessor (null for every other kind), never by a count being nonzero.
+struct FramePayload {
+    FrameKind kind = FrameKind::Single;
+    ViewBatch viewBatch;                              // Views
+    size_t colorViewStride = 0, depthViewStride = 0;  // Views: bytes from one view's target to the next's
+    BatchFrame batchFrame;                            // Batch
+    ComposeFrame composeFrame;                        // Compose
+    const ViewBatch* views() const { return kind == FrameKind::Views ? &viewBatch : nullptr; }
+    const BatchFrame* batch() const { return kind == FrameKind::Batch ? &batchFrame : nullptr; }
+    const ComposeFrame* compose() const { return kind == FrameKind::Compose ? &composeFrame : nullptr; }
+};
+// the colour and depth targets of a frame (depth nullable; a Views frame's are view 0's, a Batch's are per view)
+struct FrameTargets {
+    void* color = nullptr;
+    size_t colorPitch = 0;
+    void* depth = nullptr;
+    size_t depthPitch = 0;
 };
 
 // Per-gaussian styles (gsm_global_render_styled): the device table holds 256 packed styles --
@@ -451,12 +472,10 @@ void launch_scan_sums(uint32_t* sums, uint32_t nb, uint32_t cap, TileAssignmentH
 // duplicate-with-keys (GlobalShaders.metal:623-678 fused with :266-295)
 // fusedScan: A.blockSums holds the unscanned block counts (no launch_scan_blocks before it); each
 // workgroup adds up the counts before its own, workgroup 0 also the total (header, blend queue)
-// views (nullable): a batch's items (k_scatter_views): tile ids v * tilesPerView + local tile
-// batch (nullable): a batch of different views (k_scatter_batch): tile ids tileBase of the view + local tile
-// compose (nullable): a composite's items (k_scatter_compose): the frame's own tile ids
-void launch_scatter(const ProjectArgs& args, const DeviceArena& A, hipStream_t stream,
-                    const uint32_t* devCount = nullptr, bool fusedScan = false, const ViewBatch* views = nullptr,
-                    const BatchFrame* batch = nullptr, const ComposeFrame* compose = nullptr);
+// payload: Views -> k_scatter_views (tile ids v * tilesPerView + local tile), Batch -> k_scatter_batch (tileBase of
+// the view + local tile), Compose -> k_scatter_compose (the frame's own tile ids), else k_scatter
+void launch_scatter(const ProjectArgs& args, const DeviceArena& A, hipStream_t stream, const FramePayload& payload,
+                    const uint32_t* devCount = nullptr, bool fusedScan = false);
 // the blend's half-tile lists from the sorted values (skip flags, k_scatter), tiles [tileBegin, +numTiles)
 void launch_half_lists(const uint32_t* sortedVals, uint32_t tileBegin, uint32_t numTiles, const DeviceArena& A,
                        uint32_t tileCount, hipStream_t stream);
@@ -465,20 +484,27 @@ void launch_headers(const uint32_t* sortedKeys, const FrameGeometry& geo, const 
                     hipStream_t stream);
 // front-to-back fp16 blend + clear (GlobalShaders.metal:140-154, 1030-1187); returns the kernel it
 // launched (gsm_blend_kernel, include/gsm_debug.h; 0 for an empty frame)
-// pick (nullable): a pick frame's third target, one uint32_t per pixel (k_blend_px_pick) -- a
-// single frame or a composite over the handle's whole tile grid
-// occluder (nullable, not together with pick): an occluded frame's depth image, one float per pixel
-// (k_blend_px_occ) -- the same frames; sortedVals: the frame's sorted values, which that walk reads
-// in place of the half-tile lists
-int launch_blend(const FrameGeometry& geo, const DeviceArena& A,
-                  void* color, size_t colorPitch, void* depth, size_t depthPitch, int numCUs,
-                  bool costOrder, int colorFormat, hipStream_t stream, int waves = 0, int claim = 1,
-                  const MgArrive* arrive = nullptr, bool pairs = false, void* pick = nullptr,
-                  size_t pickPitch = 0, const void* occluder = nullptr, size_t occluderPitch = 0,
-                  const uint32_t* sortedVals = nullptr);
-// k_blend_pw (gsm_blend_pw.hip): two half-tile units per wave, one GPU's frame
-void launch_blend_pw(const FrameGeometry& g, const DeviceArena& A, void* color, size_t colorPitch, void* depth,
-                     size_t depthPitch, int numCUs, bool costOrder, int colorFormat, hipStream_t s, int waves);
+// geo.kind picks the Views / Batch kernels; pick, occluder: a Single or Compose frame over the handle's whole grid
+struct BlendOptions {
+    bool costOrder = false;  // units in A.unitOrder's order
+    int colorFormat = 0;
+    int waves = 0;           // waves per workgroup (0: by frame size)
+    int claim = 1;           // Tuning::blendClaim
+    bool pairs = false;      // Tuning::blendPairs: k_blend_pw where its rule holds
+    const MgArrive* arrive = nullptr;  // nullable: the blend's waves arrive at that barrier after their pixel stores
+    // nullable: a pick frame's third target, one uint32_t per pixel (k_blend_px_pick)
+    const PickTarget* pick = nullptr;
+    // nullable, not together with pick: an occluded frame's depth image, one float per pixel (k_blend_px_occ,
+    // DESIGN.md 21); sortedVals: the frame's sorted values, which that walk reads in place of the half-tile lists
+    const OccluderSource* occluder = nullptr;
+    const uint32_t* sortedVals = nullptr;
+    int numCUs = 0;
+};
+int launch_blend(const FrameGeometry& geo, const DeviceArena& A, const FrameTargets& targets,
+                 const BlendOptions& options, hipStream_t stream);
+// k_blend_pw (gsm_blend_pw.hip): two half-tile units per wave, one GPU's frame; options.waves as resolved
+void launch_blend_pw(const FrameGeometry& geo, const DeviceArena& A, const FrameTargets& targets,
+                     const BlendOptions& options, hipStream_t stream);
 // blend kernel shape: pixel pairs per lane (0 = quadrant kernel) and blend units per tile
 int blend_pairs_per_lane(uint32_t numTiles, int numCUs);
 uint32_t blend_units_per_tile(uint32_t numTiles, int numCUs);

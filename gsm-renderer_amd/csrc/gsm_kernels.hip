@@ -1231,53 +1231,45 @@ void launch_half_lists(const uint32_t* sortedVals, uint32_t tileBegin, uint32_t 
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-template <bool HALF>
-static void launch_project_t(uint32_t deg, const void* world, const void* harm, const ProjectArgs& a,
-                             const DeviceArena& A, hipStream_t s) {
-    const uint32_t blocks = (a.count + kProjectBlock - 1) / kProjectBlock;
-    if (blocks == 0 && a.schedUnits == 0) return;  // (an empty frame still orders its blend units)
-#define GSM_LAUNCH_PROJ(D)                                                                     \
-    hipLaunchKernelGGL((k_project<HALF, D>), dim3(blocks + (a.schedUnits ? 1u : 0u)), dim3(kProjectBlock), 0, s, \
-                       world, harm, a, A.renderData, A.bounds, A.rec, A.tileCounts, A.tileMasks,           \
-                       A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax)
-    switch (deg) {
-        case 0: GSM_LAUNCH_PROJ(0); break;
-        case 1: GSM_LAUNCH_PROJ(1); break;
-        case 2: GSM_LAUNCH_PROJ(2); break;
-        default: GSM_LAUNCH_PROJ(3); break;
-    }
-#undef GSM_LAUNCH_PROJ
+// (half, SH degree) -> f(std::bool_constant<HALF>, std::integral_constant<int, DEG>): every projection launcher's
+// template choice (SH_DEGREE selection: degrees past 3 take 3)
+template <class F>
+static void dispatch_sh(bool halfInput, uint32_t deg, F&& f) {
+    auto by_degree = [&](auto half) {
+        switch (deg) {
+            case 0: f(half, std::integral_constant<int, 0>{}); break;
+            case 1: f(half, std::integral_constant<int, 1>{}); break;
+            case 2: f(half, std::integral_constant<int, 2>{}); break;
+            default: f(half, std::integral_constant<int, 3>{}); break;
+        }
+    };
+    if (halfInput) by_degree(std::true_type{});
+    else by_degree(std::false_type{});
 }
+// the projection grids: the items' blocks, plus one workgroup that orders the blend units (a.schedUnits)
+static dim3 project_grid(uint32_t blocks, const ProjectArgs& a) { return dim3(blocks + (a.schedUnits ? 1u : 0u)); }
 
 void launch_project(bool halfInput, uint32_t deg, const void* world, const void* harm,
                     const ProjectArgs& a, const DeviceArena& A, hipStream_t s) {
-    if (halfInput) launch_project_t<true>(deg, world, harm, a, A, s);
-    else launch_project_t<false>(deg, world, harm, a, A, s);
-}
-
-template <bool HALF>
-static void launch_project_views_t(uint32_t deg, const void* world, const void* harm, const ProjectArgs& a,
-                                   const ViewBatch& vb, const DeviceArena& A, hipStream_t s) {
-    const uint32_t blocks = vb.views * vb.blocksPerView;
-    if (blocks == 0 && a.schedUnits == 0) return;  // (an empty batch still orders its blend units)
-#define GSM_LAUNCH_PROJV(D)                                                                                          \
-    hipLaunchKernelGGL((k_project_views<HALF, D>), dim3(blocks + (a.schedUnits ? 1u : 0u)), dim3(kProjectBlock), 0, \
-                       s, world, harm, a, vb.args, vb.blocksPerView ? vb.blocksPerView : 1u, A.renderData, A.bounds, \
-                       A.rec, A.tileCounts, A.tileMasks, A.blockSums, A.sincosTable, A.unitCost, A.unitOrder,        \
-                       A.costMax)
-    switch (deg) {
-        case 0: GSM_LAUNCH_PROJV(0); break;
-        case 1: GSM_LAUNCH_PROJV(1); break;
-        case 2: GSM_LAUNCH_PROJV(2); break;
-        default: GSM_LAUNCH_PROJV(3); break;
-    }
-#undef GSM_LAUNCH_PROJV
+    const uint32_t blocks = (a.count + kProjectBlock - 1) / kProjectBlock;
+    if (blocks == 0 && a.schedUnits == 0) return;  // (an empty frame still orders its blend units)
+    dispatch_sh(halfInput, deg, [&](auto H, auto D) {
+        hipLaunchKernelGGL((k_project<decltype(H)::value, decltype(D)::value>), project_grid(blocks, a),
+                           dim3(kProjectBlock), 0, s, world, harm, a, A.renderData, A.bounds, A.rec, A.tileCounts,
+                           A.tileMasks, A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax);
+    });
 }
 
 void launch_project_views(bool halfInput, uint32_t deg, const void* world, const void* harm, const ProjectArgs& a,
                           const ViewBatch& vb, const DeviceArena& A, hipStream_t s) {
-    if (halfInput) launch_project_views_t<true>(deg, world, harm, a, vb, A, s);
-    else launch_project_views_t<false>(deg, world, harm, a, vb, A, s);
+    const uint32_t blocks = vb.views * vb.blocksPerView;
+    if (blocks == 0 && a.schedUnits == 0) return;  // (an empty batch still orders its blend units)
+    dispatch_sh(halfInput, deg, [&](auto H, auto D) {
+        hipLaunchKernelGGL((k_project_views<decltype(H)::value, decltype(D)::value>), project_grid(blocks, a),
+                           dim3(kProjectBlock), 0, s, world, harm, a, vb.args,
+                           vb.blocksPerView ? vb.blocksPerView : 1u, A.renderData, A.bounds, A.rec, A.tileCounts,
+                           A.tileMasks, A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax);
+    });
 }
 
 void launch_fill_views(const ViewChunk& chunk, uint32_t first, uint32_t n, ViewArgs* dst, hipStream_t s) {
@@ -1285,27 +1277,14 @@ void launch_fill_views(const ViewChunk& chunk, uint32_t first, uint32_t n, ViewA
     hipLaunchKernelGGL(k_fill_views, dim3(1), dim3(256), 0, s, chunk, n > kViewChunk ? kViewChunk : n, dst + first);
 }
 
-template <bool HALF>
-static void launch_project_batch_t(uint32_t deg, const ProjectArgs& a, const BatchFrame& bf, const DeviceArena& A,
-                                   hipStream_t s) {
-    if (bf.blocks == 0 && a.schedUnits == 0) return;  // (an empty batch still orders its blend units)
-#define GSM_LAUNCH_PROJB(D)                                                                                          \
-    hipLaunchKernelGGL((k_project_batch<HALF, D>), dim3(bf.blocks + (a.schedUnits ? 1u : 0u)), dim3(kProjectBlock), \
-                       0, s, a, bf.args, bf.blockView, A.renderData, A.bounds, A.rec, A.tileCounts, A.tileMasks,     \
-                       A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax)
-    switch (deg) {
-        case 0: GSM_LAUNCH_PROJB(0); break;
-        case 1: GSM_LAUNCH_PROJB(1); break;
-        case 2: GSM_LAUNCH_PROJB(2); break;
-        default: GSM_LAUNCH_PROJB(3); break;
-    }
-#undef GSM_LAUNCH_PROJB
-}
-
 void launch_project_batch(bool halfInput, uint32_t deg, const ProjectArgs& a, const BatchFrame& bf,
                           const DeviceArena& A, hipStream_t s) {
-    if (halfInput) launch_project_batch_t<true>(deg, a, bf, A, s);
-    else launch_project_batch_t<false>(deg, a, bf, A, s);
+    if (bf.blocks == 0 && a.schedUnits == 0) return;  // (an empty batch still orders its blend units)
+    dispatch_sh(halfInput, deg, [&](auto H, auto D) {
+        hipLaunchKernelGGL((k_project_batch<decltype(H)::value, decltype(D)::value>), project_grid(bf.blocks, a),
+                           dim3(kProjectBlock), 0, s, a, bf.args, bf.blockView, A.renderData, A.bounds, A.rec,
+                           A.tileCounts, A.tileMasks, A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax);
+    });
 }
 
 void launch_fill_batch(const BatchChunk& chunk, uint32_t first, uint32_t n, BatchViewArgs* dst, uint16_t* blockView,
@@ -1315,27 +1294,14 @@ void launch_fill_batch(const BatchChunk& chunk, uint32_t first, uint32_t n, Batc
                        blockView, maxBlocks, tileView, maxTiles);
 }
 
-template <bool HALF>
-static void launch_project_compose_t(uint32_t deg, const ProjectArgs& a, const ComposeFrame& cf, const DeviceArena& A,
-                                     hipStream_t s) {
-    if (cf.blocks == 0 && a.schedUnits == 0) return;  // (an empty composite still orders its blend units)
-#define GSM_LAUNCH_PROJC(D)                                                                                            \
-    hipLaunchKernelGGL((k_project_compose<HALF, D>), dim3(cf.blocks + (a.schedUnits ? 1u : 0u)), dim3(kProjectBlock), \
-                       0, s, a, cf.args, cf.blockObject, A.renderData, A.bounds, A.rec, A.tileCounts, A.tileMasks,     \
-                       A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax)
-    switch (deg) {
-        case 0: GSM_LAUNCH_PROJC(0); break;
-        case 1: GSM_LAUNCH_PROJC(1); break;
-        case 2: GSM_LAUNCH_PROJC(2); break;
-        default: GSM_LAUNCH_PROJC(3); break;
-    }
-#undef GSM_LAUNCH_PROJC
-}
-
 void launch_project_compose(bool halfInput, uint32_t deg, const ProjectArgs& a, const ComposeFrame& cf,
                             const DeviceArena& A, hipStream_t s) {
-    if (halfInput) launch_project_compose_t<true>(deg, a, cf, A, s);
-    else launch_project_compose_t<false>(deg, a, cf, A, s);
+    if (cf.blocks == 0 && a.schedUnits == 0) return;  // (an empty composite still orders its blend units)
+    dispatch_sh(halfInput, deg, [&](auto H, auto D) {
+        hipLaunchKernelGGL((k_project_compose<decltype(H)::value, decltype(D)::value>), project_grid(cf.blocks, a),
+                           dim3(kProjectBlock), 0, s, a, cf.args, cf.blockObject, A.renderData, A.bounds, A.rec,
+                           A.tileCounts, A.tileMasks, A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax);
+    });
 }
 
 void launch_fill_compose(const ComposeChunk& chunk, uint32_t first, uint32_t n, ComposeObjectArgs* dst,
@@ -1345,52 +1311,27 @@ void launch_fill_compose(const ComposeChunk& chunk, uint32_t first, uint32_t n, 
                        dst, blockObject, maxBlocks);
 }
 
-template <bool HALF>
-static void launch_project_styled_t(uint32_t deg, const void* world, const void* harm, const ProjectArgs& a,
-                                    const StyleArgs& st, const DeviceArena& A, hipStream_t s) {
-    const uint32_t blocks = (a.count + kProjectBlock - 1) / kProjectBlock;
-    if (blocks == 0 && a.schedUnits == 0) return;  // (an empty frame still orders its blend units)
-#define GSM_LAUNCH_PROJS(D)                                                                                         \
-    hipLaunchKernelGGL((k_project_styled<HALF, D>), dim3(blocks + (a.schedUnits ? 1u : 0u)), dim3(kProjectBlock), 0, \
-                       s, world, harm, a, A.renderData, A.bounds, A.rec, A.tileCounts, A.tileMasks, A.blockSums,     \
-                       A.sincosTable, A.unitCost, A.unitOrder, A.costMax, st.table, st.state, st.defaultState)
-    switch (deg) {
-        case 0: GSM_LAUNCH_PROJS(0); break;
-        case 1: GSM_LAUNCH_PROJS(1); break;
-        case 2: GSM_LAUNCH_PROJS(2); break;
-        default: GSM_LAUNCH_PROJS(3); break;
-    }
-#undef GSM_LAUNCH_PROJS
-}
-
 void launch_project_styled(bool halfInput, uint32_t deg, const void* world, const void* harm, const ProjectArgs& a,
                            const StyleArgs& st, const DeviceArena& A, hipStream_t s) {
-    if (halfInput) launch_project_styled_t<true>(deg, world, harm, a, st, A, s);
-    else launch_project_styled_t<false>(deg, world, harm, a, st, A, s);
-}
-
-template <bool HALF>
-static void launch_project_compose_styled_t(uint32_t deg, const ProjectArgs& a, const ComposeFrame& cf,
-                                            const uint2* styleTable, const DeviceArena& A, hipStream_t s) {
-    if (cf.blocks == 0 && a.schedUnits == 0) return;  // (an empty composite still orders its blend units)
-#define GSM_LAUNCH_PROJCS(D)                                                                                        \
-    hipLaunchKernelGGL((k_project_compose_styled<HALF, D>), dim3(cf.blocks + (a.schedUnits ? 1u : 0u)),              \
-                       dim3(kProjectBlock), 0, s, a, cf.args, cf.blockObject, A.renderData, A.bounds, A.rec,         \
-                       A.tileCounts, A.tileMasks, A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax,    \
-                       styleTable)
-    switch (deg) {
-        case 0: GSM_LAUNCH_PROJCS(0); break;
-        case 1: GSM_LAUNCH_PROJCS(1); break;
-        case 2: GSM_LAUNCH_PROJCS(2); break;
-        default: GSM_LAUNCH_PROJCS(3); break;
-    }
-#undef GSM_LAUNCH_PROJCS
+    const uint32_t blocks = (a.count + kProjectBlock - 1) / kProjectBlock;
+    if (blocks == 0 && a.schedUnits == 0) return;  // (an empty frame still orders its blend units)
+    dispatch_sh(halfInput, deg, [&](auto H, auto D) {
+        hipLaunchKernelGGL((k_project_styled<decltype(H)::value, decltype(D)::value>), project_grid(blocks, a),
+                           dim3(kProjectBlock), 0, s, world, harm, a, A.renderData, A.bounds, A.rec, A.tileCounts,
+                           A.tileMasks, A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax, st.table,
+                           st.state, st.defaultState);
+    });
 }
 
 void launch_project_compose_styled(bool halfInput, uint32_t deg, const ProjectArgs& a, const ComposeFrame& cf,
                                    const uint2* styleTable, const DeviceArena& A, hipStream_t s) {
-    if (halfInput) launch_project_compose_styled_t<true>(deg, a, cf, styleTable, A, s);
-    else launch_project_compose_styled_t<false>(deg, a, cf, styleTable, A, s);
+    if (cf.blocks == 0 && a.schedUnits == 0) return;  // (an empty composite still orders its blend units)
+    dispatch_sh(halfInput, deg, [&](auto H, auto D) {
+        hipLaunchKernelGGL((k_project_compose_styled<decltype(H)::value, decltype(D)::value>),
+                           project_grid(cf.blocks, a), dim3(kProjectBlock), 0, s, a, cf.args, cf.blockObject,
+                           A.renderData, A.bounds, A.rec, A.tileCounts, A.tileMasks, A.blockSums, A.sincosTable,
+                           A.unitCost, A.unitOrder, A.costMax, styleTable);
+    });
 }
 
 void launch_fill_styles(const StyleChunk& chunk, uint2* dst, hipStream_t s) {
@@ -1411,23 +1352,18 @@ void launch_select_mask(bool halfInput, const void* world, const ProjectArgs& a,
                            maskPitch, width, height, state, styleTable, andMask, xorMask, matched);
 }
 
-template <bool HALF>
-static void launch_project_part_t(uint32_t deg, const void* world, const void* harm, const ProjectArgs& a,
-                                  const SlabTable& slabs, const PartitionBuffers& B, const float2* sincos,
-                                  const DeviceArena* A, hipStream_t s) {
+// A (nullable): the arena whose blend units the launch also orders (a.schedUnits)
+static void launch_project_part(bool halfInput, uint32_t deg, const void* world, const void* harm,
+                                const ProjectArgs& a, const SlabTable& slabs, const PartitionBuffers& B,
+                                const float2* sincos, const DeviceArena* A, hipStream_t s) {
     const uint32_t blocks = (a.count + kProjectBlock - 1) / kProjectBlock;
     const uint32_t sched = (A && a.schedUnits) ? 1u : 0u;
-#define GSM_LAUNCH_PPART(D)                                                                                 \
-    hipLaunchKernelGGL((k_project_part<HALF, D>), dim3(blocks + sched), dim3(kProjectBlock), 0, s, world,   \
-                       harm, a, slabs, B.runs, B.runStride, B.blockSlabCounts, sincos,                      \
-                       sched ? A->unitCost : nullptr, sched ? A->unitOrder : nullptr, sched ? A->costMax : nullptr)
-    switch (deg) {
-        case 0: GSM_LAUNCH_PPART(0); break;
-        case 1: GSM_LAUNCH_PPART(1); break;
-        case 2: GSM_LAUNCH_PPART(2); break;
-        default: GSM_LAUNCH_PPART(3); break;
-    }
-#undef GSM_LAUNCH_PPART
+    dispatch_sh(halfInput, deg, [&](auto H, auto D) {
+        hipLaunchKernelGGL((k_project_part<decltype(H)::value, decltype(D)::value>), dim3(blocks + sched),
+                           dim3(kProjectBlock), 0, s, world, harm, a, slabs, B.runs, B.runStride, B.blockSlabCounts,
+                           sincos, sched ? A->unitCost : nullptr, sched ? A->unitOrder : nullptr,
+                           sched ? A->costMax : nullptr);
+    });
 }
 
 constexpr uint32_t kCopyMaxBlocks = 2048;  // k_part_copy<false>: workgroups loop over the runs
@@ -1442,8 +1378,7 @@ void launch_partition(bool halfInput, uint32_t deg, const void* world, const voi
     }
     ProjectArgs pa = a;
     pa.schedUnits = 0;  // (the send-buffer path leaves the schedule to the receiving renderer)
-    if (halfInput) launch_project_part_t<true>(deg, world, harm, pa, slabs, B, sincos, nullptr, s);
-    else launch_project_part_t<false>(deg, world, harm, pa, slabs, B, sincos, nullptr, s);
+    launch_project_part(halfInput, deg, world, harm, pa, slabs, B, sincos, nullptr, s);
     hipLaunchKernelGGL(k_part_scan, dim3(slabs.n), dim3(1024), 0, s, B.blockSlabCounts, blocks, sendCounts,
                        CountPublish{});
     hipLaunchKernelGGL(k_part_copy<false>, dim3(min(blocks, kCopyMaxBlocks)), dim3(kProjectBlock), 0, s, B.runs,
@@ -1455,10 +1390,8 @@ void launch_partition_counts(bool halfInput, uint32_t deg, const void* world, co
                              const SlabTable& slabs, const PartitionBuffers& B, const float2* sincos,
                              uint32_t* sendCounts, const DeviceArena& A, const CountPublish& pub, hipStream_t s) {
     const uint32_t blocks = (a.count + kProjectBlock - 1) / kProjectBlock;
-    if (blocks > 0 || a.schedUnits > 0) {  // (no ids: the schedule block may still run)
-        if (halfInput) launch_project_part_t<true>(deg, world, harm, a, slabs, B, sincos, &A, s);
-        else launch_project_part_t<false>(deg, world, harm, a, slabs, B, sincos, &A, s);
-    }
+    // (no ids: the schedule block may still run)
+    if (blocks > 0 || a.schedUnits > 0) launch_project_part(halfInput, deg, world, harm, a, slabs, B, sincos, &A, s);
     // with no ids the scan still runs: zero counts, published, and the arrival at barrier 0
     CountPublish p = pub;
     if (p.arrive.done) p.arrive.total = slabs.n;
@@ -1504,23 +1437,23 @@ void launch_scan_blocks(uint32_t nb, const ProjectArgs& a, const DeviceArena& A,
                        a.maxAssignments, A.header, A.tileQueue, devCount);
 }
 
-void launch_scatter(const ProjectArgs& a, const DeviceArena& A, hipStream_t s, const uint32_t* devCount,
-                    bool fusedScan, const ViewBatch* vb, const BatchFrame* bf, const ComposeFrame* cf) {
-    if (cf) {
+void launch_scatter(const ProjectArgs& a, const DeviceArena& A, hipStream_t s, const FramePayload& payload,
+                    const uint32_t* devCount, bool fusedScan) {
+    if (const ComposeFrame* cf = payload.compose()) {
         if (cf->blocks == 0) return;
         hipLaunchKernelGGL(k_scatter_compose, dim3(cf->blocks), dim3(kProjectBlock), 0, s, a, cf->args,
                            cf->blockObject, A.renderData, A.bounds, A.tileCounts, A.tileMasks, A.blockSums, A.keys[0],
                            A.vals[0], A.sincosTable, A.rec, fusedScan ? 1u : 0u, A.header, A.tileQueue);
         return;
     }
-    if (bf) {
+    if (const BatchFrame* bf = payload.batch()) {
         if (bf->blocks == 0) return;
         hipLaunchKernelGGL(k_scatter_batch, dim3(bf->blocks), dim3(kProjectBlock), 0, s, a, bf->args, bf->blockView,
                            A.renderData, A.bounds, A.tileCounts, A.tileMasks, A.blockSums, A.keys[0], A.vals[0],
                            A.sincosTable, A.rec, fusedScan ? 1u : 0u, A.header, A.tileQueue);
         return;
     }
-    if (vb) {
+    if (const ViewBatch* vb = payload.views()) {
         const uint32_t vblocks = vb->views * vb->blocksPerView;
         if (vblocks == 0) return;
         hipLaunchKernelGGL(k_scatter_views, dim3(vblocks), dim3(kProjectBlock), 0, s, a, vb->blocksPerView,

@@ -184,42 +184,6 @@ gsm_status GlobalRenderer::validateFrame(uint32_t count, bool inputMissing, uint
     return GSM_OK;
 }
 
-gsm_status GlobalRenderer::render(hipStream_t s, const gsm_gaussian_input& in,
-                                  const gsm_camera_params& camp, uint32_t width, uint32_t height,
-                                  void* color, size_t colorPitch, void* depth, size_t depthPitch) {
-    return renderFrame(s, in, camp, width, height, color, colorPitch, depth, depthPitch, nullptr);
-}
-
-gsm_status GlobalRenderer::renderPick(hipStream_t s, const gsm_gaussian_input& in, const gsm_camera_params& camp,
-                                      uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                                      size_t depthPitch, void* pick, size_t pickPitch) {
-    const PickTarget pt{pick, pickPitch};
-    return renderFrame(s, in, camp, width, height, color, colorPitch, depth, depthPitch, &pt);
-}
-
-gsm_status GlobalRenderer::renderCompositePick(hipStream_t s, const gsm_global_object* objects, uint32_t objectCount,
-                                               uint32_t width, uint32_t height, void* color, size_t colorPitch,
-                                               void* depth, size_t depthPitch, void* pick, size_t pickPitch) {
-    const PickTarget pt{pick, pickPitch};
-    return composeFrame(s, objects, objectCount, width, height, color, colorPitch, depth, depthPitch, &pt);
-}
-
-gsm_status GlobalRenderer::renderOccluded(hipStream_t s, const gsm_gaussian_input& in, const gsm_camera_params& camp,
-                                          uint32_t width, uint32_t height, void* color, size_t colorPitch,
-                                          void* depth, size_t depthPitch, const void* occluder,
-                                          size_t occluderPitch) {
-    const OccluderSource os{occluder, occluderPitch};
-    return renderFrame(s, in, camp, width, height, color, colorPitch, depth, depthPitch, nullptr, &os);
-}
-
-gsm_status GlobalRenderer::renderCompositeOccluded(hipStream_t s, const gsm_global_object* objects,
-                                                   uint32_t objectCount, uint32_t width, uint32_t height, void* color,
-                                                   size_t colorPitch, void* depth, size_t depthPitch,
-                                                   const void* occluder, size_t occluderPitch) {
-    const OccluderSource os{occluder, occluderPitch};
-    return composeFrame(s, objects, objectCount, width, height, color, colorPitch, depth, depthPitch, nullptr, &os);
-}
-
 gsm_status GlobalRenderer::pickOwner(const uint32_t* items, uint32_t n, uint32_t* object, uint32_t* gaussian) const {
     if (!lastPick_) return GSM_ERR_RENDER_FAILED;  // (the handle's last enqueued frame wrote no pick target)
     for (uint32_t i = 0; i < n; ++i) {
@@ -251,34 +215,47 @@ gsm_status GlobalRenderer::pickOwner(const uint32_t* items, uint32_t n, uint32_t
     return GSM_OK;
 }
 
+GlobalRenderer::FrameRequest GlobalRenderer::request(FrameKind kind, const ProjectArgs& args, uint32_t width,
+                                                     uint32_t height, const FrameTargets& targets) const {
+    FrameRequest rq;
+    rq.args = args;
+    rq.width = width;
+    rq.height = height;
+    rq.targets = targets;
+    rq.payload.kind = kind;
+    return rq;
+}
+
 gsm_status GlobalRenderer::renderFrame(hipStream_t s, const gsm_gaussian_input& in, const gsm_camera_params& camp,
-                                       uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                                       size_t depthPitch, const PickTarget* pick, const OccluderSource* occluder,
-                                       const StyleSource* style) {
-    gsm_status st = validateFrame(in.gaussian_count, !in.gaussians || !in.harmonics, width, height, color,
-                                  colorPitch, depth, depthPitch, pick, occluder);
+                                       uint32_t width, uint32_t height, const FrameTargets& t,
+                                       const FrameExtras& extras) {
+    const StyleSource* style = extras.style;
+    gsm_status st = validateFrame(in.gaussian_count, !in.gaussians || !in.harmonics, width, height, t.color,
+                                  t.colorPitch, t.depth, t.depthPitch, extras.pick, extras.occluder);
     if (st != GSM_OK) return st;
     if (style && !styleSourceOk(*style, 1)) return GSM_ERR_INVALID_ARGUMENT;
     // (set_tile_rows: a pick frame, an occluded frame and a styled frame are whole frames)
-    if ((pick || occluder || style) && tileRowsRestricted()) return GSM_ERR_UNSUPPORTED;
+    if ((extras.pick || extras.occluder || style) && tileRowsRestricted()) return GSM_ERR_UNSUPPORTED;
     // the projection's tile tests walk contiguous rows; interleaved row sets come from the records
     // path only (gsm_multigpu)
     if (rowStride_ != 1) return GSM_ERR_INVALID_ARGUMENT;
-    const ProjectArgs a = frameArgs(camp, width, height, in.gaussian_count, in.sh_components);
+    FrameRequest rq = request(FrameKind::Single, frameArgs(camp, width, height, in.gaussian_count, in.sh_components),
+                              width, height, t);
+    rq.pick = extras.pick;
+    rq.occluder = extras.occluder;
     const uint32_t deg = sh_degree(in.sh_components);
     const bool half = config_.precision == GSM_PRECISION_FLOAT16;
     if (style) {
         if ((st = fillStyleTable(s, style->styles, style->styleCount)) != GSM_OK) return st;
         const StyleArgs sa{arena_.styleTable, style->states[0].state, style->states[0].default_state};
-        return runFrame(s, a, width, height, color, colorPitch, depth, depthPitch,
-                        [&](const ProjectArgs& pa) {
-                            launch_project_styled(half, deg, in.gaussians, in.harmonics, pa, sa, arena_, s);
-                        }, nullptr, false, nullptr, nullptr, pick, nullptr, true);
+        rq.styled = true;
+        return runFrame(s, rq, [&](const ProjectArgs& pa) {
+            launch_project_styled(half, deg, in.gaussians, in.harmonics, pa, sa, arena_, s);
+        });
     }
-    return runFrame(s, a, width, height, color, colorPitch, depth, depthPitch,
-                    [&](const ProjectArgs& pa) {
-                        launch_project(half, deg, in.gaussians, in.harmonics, pa, arena_, s);
-                    }, nullptr, false, nullptr, nullptr, pick, occluder);
+    return runFrame(s, rq, [&](const ProjectArgs& pa) {
+        launch_project(half, deg, in.gaussians, in.harmonics, pa, arena_, s);
+    });
 }
 
 bool GlobalRenderer::styleSourceOk(const StyleSource& style, uint32_t stateCount) {
@@ -306,28 +283,6 @@ gsm_status GlobalRenderer::fillStyleTable(hipStream_t s, const gsm_global_style*
     }
     launch_fill_styles(c, arena_.styleTable, s);
     return GSM_OK;
-}
-
-gsm_status GlobalRenderer::renderStyled(hipStream_t s, const gsm_gaussian_input& in, const gsm_camera_params& camp,
-                                        uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                                        size_t depthPitch, void* pick, size_t pickPitch,
-                                        const gsm_global_state* state, const gsm_global_style* styles,
-                                        uint32_t styleCount) {
-    const PickTarget pt{pick, pickPitch};
-    const StyleSource ss{state, styles, styleCount};
-    return renderFrame(s, in, camp, width, height, color, colorPitch, depth, depthPitch, pick ? &pt : nullptr, nullptr,
-                       &ss);
-}
-
-gsm_status GlobalRenderer::renderCompositeStyled(hipStream_t s, const gsm_global_object* objects, uint32_t objectCount,
-                                                 uint32_t width, uint32_t height, void* color, size_t colorPitch,
-                                                 void* depth, size_t depthPitch, void* pick, size_t pickPitch,
-                                                 const gsm_global_state* states, const gsm_global_style* styles,
-                                                 uint32_t styleCount) {
-    const PickTarget pt{pick, pickPitch};
-    const StyleSource ss{states, styles, styleCount};
-    return composeFrame(s, objects, objectCount, width, height, color, colorPitch, depth, depthPitch,
-                        pick ? &pt : nullptr, nullptr, &ss);
 }
 
 gsm_status GlobalRenderer::selectMask(hipStream_t s, const gsm_gaussian_input* in, const gsm_camera_params* camp,
@@ -370,6 +325,20 @@ static void set_view_terms(Entry& d, const ProjectArgs& pv) {
     d.maxEig = pv.maxEig;
     d.adjFar = pv.adjFar;
     d.adjDen = pv.adjDen;
+}
+
+// the first `count` entries of a host copy to their device array, a kernel-argument chunk at a time: launch(chunk,
+// first, n) writes entries [first, first + n)
+template <class Chunk, class Entry, class Launch>
+static void fill_chunks(const std::vector<Entry>& host, uint32_t count, Launch&& launch) {
+    constexpr uint32_t kPer = sizeof(Chunk::v) / sizeof(Entry);
+    for (uint32_t e0 = 0; e0 < count; e0 += kPer) {
+        Chunk c;
+        const uint32_t n = std::min(kPer, count - e0);
+        std::memset(&c, 0, sizeof(c));
+        std::memcpy(c.v, host.data() + e0, (size_t)n * sizeof(Entry));
+        launch(c, e0, n);
+    }
 }
 
 bool GlobalRenderer::frameSizeOk(uint32_t width, uint32_t height) const {
@@ -427,26 +396,22 @@ gsm_status GlobalRenderer::renderViews(hipStream_t s, const gsm_gaussian_input& 
         std::memset(&d, 0, sizeof(d));
         set_view_terms(d, pv);
     }
-    for (uint32_t v0 = 0; v0 < viewCount; v0 += kViewChunk) {
-        ViewChunk c;
-        const uint32_t n = std::min(kViewChunk, viewCount - v0);
-        std::memset(&c, 0, sizeof(c));
-        std::memcpy(c.v, viewHost_.data() + v0, (size_t)n * sizeof(ViewArgs));
+    fill_chunks<ViewChunk>(viewHost_, viewCount, [&](const ViewChunk& c, uint32_t v0, uint32_t n) {
         launch_fill_views(c, v0, n, arena_.viewArgs, s);
-    }
-    ViewFrame vf;
-    vf.batch.views = viewCount;
-    vf.batch.blocksPerView = (uint32_t)(padded / kProjectBlock);
-    vf.batch.tilesPerView = T;
-    vf.batch.args = arena_.viewArgs;
-    vf.colorStride = colorStride;
-    vf.depthStride = depthStride;
+    });
+    FrameRequest rq = request(FrameKind::Views, a, width, height, FrameTargets{color, colorPitch, depth, depthPitch});
+    ViewBatch& vb = rq.payload.viewBatch;
+    vb.views = viewCount;
+    vb.blocksPerView = (uint32_t)(padded / kProjectBlock);
+    vb.tilesPerView = T;
+    vb.args = arena_.viewArgs;
+    rq.payload.colorViewStride = colorStride;
+    rq.payload.depthViewStride = depthStride;
     const uint32_t deg = sh_degree(in.sh_components);
     const bool half = config_.precision == GSM_PRECISION_FLOAT16;
-    return runFrame(s, a, width, height, color, colorPitch, depth, depthPitch,
-                    [&](const ProjectArgs& pa) {
-                        launch_project_views(half, deg, in.gaussians, in.harmonics, pa, vf.batch, arena_, s);
-                    }, nullptr, false, nullptr, &vf);
+    return runFrame(s, rq, [&](const ProjectArgs& pa) {
+        launch_project_views(half, deg, in.gaussians, in.harmonics, pa, vb, arena_, s);
+    });
 }
 
 gsm_status GlobalRenderer::renderBatch(hipStream_t s, const gsm_global_view* views, uint32_t viewCount) {
@@ -496,8 +461,8 @@ gsm_status GlobalRenderer::renderBatch(hipStream_t s, const gsm_global_view* vie
         if (st == GSM_OK) st = allocs_.alloc((void**)&tv, (size_t)tileCount_ * sizeof(uint16_t));
         if (st != GSM_OK) return st;
         batchHost_.reserve(mv);
-        batchSig_.reserve(3 * (size_t)mv);
-        schedBatchSig_.reserve(3 * (size_t)mv);
+        key_.reserve(ScheduleKey::kFixedWords + 3 * (size_t)mv);  // (the largest signature the handle can hold)
+        schedState_.reserve(ScheduleKey::kFixedWords + 3 * (size_t)mv);
         arena_.batchArgs = args;
         arena_.batchBlockView = bv;
         arena_.batchTileView = tv;
@@ -508,7 +473,6 @@ gsm_status GlobalRenderer::renderBatch(hipStream_t s, const gsm_global_view* vie
     // frameArgs -- the camera terms depend on its width and height -- on its own tile grid, rows [0, tilesY)
     const uint32_t sh = views[0].input.sh_components;
     batchHost_.resize(viewCount);
-    batchSig_.clear();
     uint32_t blockBase = 0, tileBase = 0, countSum = 0;
     for (uint32_t v = 0; v < viewCount; ++v) {
         const gsm_global_view& V = views[v];
@@ -542,45 +506,37 @@ gsm_status GlobalRenderer::renderBatch(hipStream_t s, const gsm_global_view* vie
         blockBase += (n + kProjectBlock - 1) / kProjectBlock;
         tileBase += d.bin.tilesX * d.bin.tilesY;
         countSum += n;
-        batchSig_.push_back(V.width);
-        batchSig_.push_back(V.height);
-        batchSig_.push_back(n);
     }
-    for (uint32_t v0 = 0; v0 < viewCount; v0 += kBatchChunk) {
-        BatchChunk c;
-        const uint32_t n = std::min(kBatchChunk, viewCount - v0);
-        std::memset(&c, 0, sizeof(c));
-        std::memcpy(c.v, batchHost_.data() + v0, (size_t)n * sizeof(BatchViewArgs));
+    fill_chunks<BatchChunk>(batchHost_, viewCount, [&](const BatchChunk& c, uint32_t v0, uint32_t n) {
         launch_fill_batch(c, v0, n, arena_.batchArgs, arena_.batchBlockView, maxBlocks, arena_.batchTileView, tileCount_,
                           s);
-    }
+    });
     // what the batch shares: the thresholds, the capacity and the schedule; count = the batch's gaussians (counters)
     const ProjectArgs a = batchSharedArgs(views[0].camera, views[0].width, views[0].height, countSum, sh);
-    ViewFrame vf;
-    vf.batchFrame.views = viewCount;
-    vf.batchFrame.blocks = blockBase;
-    vf.batchFrame.tiles = tileBase;
-    vf.batchFrame.args = arena_.batchArgs;
-    vf.batchFrame.blockView = arena_.batchBlockView;
-    vf.batchFrame.tileView = arena_.batchTileView;
+    FrameRequest rq = request(FrameKind::Batch, a, views[0].width, views[0].height,
+                              FrameTargets{views[0].color, views[0].color_pitch_bytes, views[0].depth,
+                                           views[0].depth_pitch_bytes});
+    BatchFrame& bf = rq.payload.batchFrame;
+    bf.views = viewCount;
+    bf.blocks = blockBase;
+    bf.tiles = tileBase;
+    bf.args = arena_.batchArgs;
+    bf.blockView = arena_.batchBlockView;
+    bf.tileView = arena_.batchTileView;
     const uint32_t deg = sh_degree(sh);
     const bool half = config_.precision == GSM_PRECISION_FLOAT16;
-    return runFrame(s, a, views[0].width, views[0].height, views[0].color, views[0].color_pitch_bytes, views[0].depth,
-                    views[0].depth_pitch_bytes,
-                    [&](const ProjectArgs& pa) { launch_project_batch(half, deg, pa, vf.batchFrame, arena_, s); },
-                    nullptr, false, nullptr, &vf);
-}
-
-gsm_status GlobalRenderer::renderComposite(hipStream_t s, const gsm_global_object* objects, uint32_t objectCount,
-                                           uint32_t width, uint32_t height, void* color, size_t colorPitch,
-                                           void* depth, size_t depthPitch) {
-    return composeFrame(s, objects, objectCount, width, height, color, colorPitch, depth, depthPitch, nullptr);
+    return runFrame(s, rq, [&](const ProjectArgs& pa) { launch_project_batch(half, deg, pa, bf, arena_, s); });
 }
 
 gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* objects, uint32_t objectCount,
-                                        uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                                        size_t depthPitch, const PickTarget* pick, const OccluderSource* occluder,
-                                        const StyleSource* style) {
+                                        uint32_t width, uint32_t height, const FrameTargets& t,
+                                        const FrameExtras& extras) {
+    const PickTarget* pick = extras.pick;
+    const OccluderSource* occluder = extras.occluder;
+    const StyleSource* style = extras.style;
+    void* const color = t.color;
+    void* const depth = t.depth;
+    const size_t colorPitch = t.colorPitch, depthPitch = t.depthPitch;
     // Every check before anything is enqueued, one kind of check after another over all objects (the first
     // failing kind decides, within it the lowest object): counts, dimensions, missing buffers, sizes,
     // sh_components, tile rows.  (The counts of a NULL array cannot be read: that is the missing buffer.)
@@ -625,25 +581,21 @@ gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* 
         if (st != GSM_OK) return st;
         composeHost_.reserve(maxEntries);
         composeObject_.reserve(maxEntries);
-        composeSig_.reserve(2 + 65535u);
-        schedComposeSig_.reserve(2 + 65535u);
+        key_.reserve(ScheduleKey::kFixedWords + 65535u);  // (the largest signature: a count per object)
+        schedState_.reserve(ScheduleKey::kFixedWords + 65535u);
         arena_.composeArgs = args;
         arena_.composeBlockObject = bo;
     }
     (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's)
     // the host copy of the entries (`objects` is consumed before the call returns): each object's own frameArgs
-    // -- its camera on the frame's size -- for the objects that have gaussians; the signature takes every object
+    // -- its camera on the frame's size -- for the objects that have gaussians
     const uint32_t sh = objects[0].input.sh_components;
     composeHost_.clear();
     composeObject_.clear();
-    composeSig_.clear();
-    composeSig_.push_back(width);
-    composeSig_.push_back(height);
     uint32_t blockBase = 0;
     for (uint32_t o = 0; o < objectCount; ++o) {
         const gsm_global_object& O = objects[o];
         const uint32_t n = O.input.gaussian_count;
-        composeSig_.push_back(n);
         if (n == 0) continue;  // (no block, no entry)
         const ProjectArgs po = frameArgs(O.camera, width, height, n, sh);
         ComposeObjectArgs d;
@@ -661,35 +613,32 @@ gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* 
         composeObject_.push_back(o);  // (pickOwner: the entry's object index of the call)
         blockBase += (n + kProjectBlock - 1) / kProjectBlock;
     }
-    for (uint32_t e0 = 0; e0 < entries; e0 += kComposeChunk) {
-        ComposeChunk c;
-        const uint32_t n = std::min(kComposeChunk, entries - e0);
-        std::memset(&c, 0, sizeof(c));
-        std::memcpy(c.v, composeHost_.data() + e0, (size_t)n * sizeof(ComposeObjectArgs));
+    fill_chunks<ComposeChunk>(composeHost_, entries, [&](const ComposeChunk& c, uint32_t e0, uint32_t n) {
         launch_fill_compose(c, e0, n, arena_.composeArgs, arena_.composeBlockObject, maxBlocks, s);
-    }
+    });
     // the frame's arguments are the single frame's: the handle's tile grid and rows, the thresholds, the capacity
     // and the schedule; count = the composite's gaussians (counters).  (Not batchSharedArgs: that puts a batch on
     // view 0's own grid, and a composite stays on the handle's, as gsm_global_render does.)
     const ProjectArgs a = frameArgs(objects[0].camera, width, height, countSum, sh);
-    ViewFrame vf;
-    vf.compose.objects = objectCount;
-    vf.compose.entries = entries;
-    vf.compose.blocks = blockBase;
-    vf.compose.args = arena_.composeArgs;
-    vf.compose.blockObject = arena_.composeBlockObject;
+    FrameRequest rq = request(FrameKind::Compose, a, width, height, t);
+    ComposeFrame& cf = rq.payload.composeFrame;
+    cf.objects = objectCount;
+    cf.entries = entries;
+    cf.blocks = blockBase;
+    cf.args = arena_.composeArgs;
+    cf.blockObject = arena_.composeBlockObject;
+    rq.pick = pick;
+    rq.occluder = occluder;
     const uint32_t deg = sh_degree(sh);
     const bool half = config_.precision == GSM_PRECISION_FLOAT16;
     if (style) {
         if ((st = fillStyleTable(s, style->styles, style->styleCount)) != GSM_OK) return st;
-        return runFrame(s, a, width, height, color, colorPitch, depth, depthPitch,
-                        [&](const ProjectArgs& pa) {
-                            launch_project_compose_styled(half, deg, pa, vf.compose, arena_.styleTable, arena_, s);
-                        }, nullptr, false, nullptr, &vf, pick, nullptr, true);
+        rq.styled = true;
+        return runFrame(s, rq, [&](const ProjectArgs& pa) {
+            launch_project_compose_styled(half, deg, pa, cf, arena_.styleTable, arena_, s);
+        });
     }
-    return runFrame(s, a, width, height, color, colorPitch, depth, depthPitch,
-                    [&](const ProjectArgs& pa) { launch_project_compose(half, deg, pa, vf.compose, arena_, s); },
-                    nullptr, false, nullptr, &vf, pick, occluder);
+    return runFrame(s, rq, [&](const ProjectArgs& pa) { launch_project_compose(half, deg, pa, cf, arena_, s); });
 }
 
 gsm_status GlobalRenderer::renderRecords(hipStream_t s, const void* records, uint32_t count, uint32_t width,
@@ -702,11 +651,12 @@ gsm_status GlobalRenderer::renderRecords(hipStream_t s, const void* records, uin
     if (st != GSM_OK) return st;
     gsm_camera_params cam;
     std::memset(&cam, 0, sizeof(cam));
-    const ProjectArgs a = frameArgs(cam, width, height, count, 1);
-    return runFrame(s, a, width, height, color, colorPitch, depth, depthPitch,
-                    [&](const ProjectArgs& pa) {
-                        launch_records_in(records, pa, arena_, s, devCount);
-                    }, devCount, preOrdered, blendArrive);
+    FrameRequest rq = request(FrameKind::Records, frameArgs(cam, width, height, count, 1), width, height,
+                              FrameTargets{color, colorPitch, depth, depthPitch});
+    rq.devCount = devCount;
+    rq.preOrdered = preOrdered;
+    rq.blendArrive = blendArrive;
+    return runFrame(s, rq, [&](const ProjectArgs& pa) { launch_records_in(records, pa, arena_, s, devCount); });
 }
 
 gsm_status GlobalRenderer::preparePartition(const gsm_gaussian_input& in, const gsm_camera_params& camp,
@@ -803,7 +753,11 @@ gsm_status GlobalRenderer::partitionCounts(hipStream_t s, const gsm_gaussian_inp
                                      sendCounts, &f, interleave);
     if (st != GSM_OK) return st;
     // the blend units of this renderer's rows (its slab), ordered by one extra workgroup of the launch
-    f.a.schedUnits = orderUnits ? scheduleUnits(s, width, height) : 0u;
+    if (orderUnits) {
+        uint32_t tiles = 0;
+        const ScheduleKey& key = requestKey(request(FrameKind::Single, f.a, width, height, FrameTargets{}), &tiles);
+        f.a.schedUnits = scheduleUnits(s, key, tiles);
+    }
     f.a.pairBucket = tuning_.blendPairs ? (uint32_t)std::max(1, tuning_.pairBucket) : kUoBuckets;
     launch_partition_counts(f.half, f.deg, f.world, f.harm, f.a, f.slabs, part_, arena_.sincosTable, sendCounts,
                             arena_, publish ? *publish : CountPublish{}, s);
@@ -826,84 +780,96 @@ gsm_status GlobalRenderer::partitionPush(hipStream_t s, uint32_t world, uint32_t
     return GSM_OK;
 }
 
-uint32_t GlobalRenderer::scheduleUnits(hipStream_t s, uint32_t width, uint32_t height, uint32_t views,
-                                       uint32_t batchTiles, bool compose, bool pick, bool occluded, bool styled) {
-    // (a batch of views: the units of views * tiles(width, height) tiles; the view count is part of the key, so
-    // a batch neither inherits nor leaves behind a single frame's costs.  A batch of different views: the units
-    // of its batchTiles tiles, keyed by its whole signature batchSig_, compared word for word)
-    const uint32_t tiles = batchTiles ? batchTiles : views ? views * tiles_of(width, height) : rowCount() * tilesX_;
-    const uint32_t upt = blend_units_per_tile(tiles, dev_.numCUs);
-    const uint32_t units = tiles * upt;
-    // (a composite: the single frame's units, keyed by its whole signature composeSig_, so it neither inherits
-    // walk costs from a render / render_views / render_batch of the handle nor leaves any to one)
-    const uint64_t key = compose ? ~1ull : batchTiles ? ~0ull
-                                    : ((uint64_t)upt << 60) ^ ((uint64_t)width << 40) ^ ((uint64_t)height << 20) ^
-                                          ((uint64_t)rowStride_ << 30) ^ ((uint64_t)rowBegin_ << 10) ^ rowEnd_;
-    const bool isBatch = batchTiles != 0;
-    // (a pick frame walks without compaction or pairs: its costs are its own, either way round)
-    bool changed = isBatch != schedBatch_ || compose != schedCompose_ || key != schedKey_ || views != schedViews_ ||
-                   pick != schedPick_ || occluded != schedOccluded_ || styled != schedStyled_;
-    schedStyled_ = styled;  // (a styled frame hides and fades gaussians: its walks are its own too)
-    schedPick_ = pick;
-    schedOccluded_ = occluded;  // (an occluded frame's walks end at the occluder: its costs are its own as well)
-    if (compose && !changed) changed = composeSig_ != schedComposeSig_;
-    if (compose && changed) schedComposeSig_.assign(composeSig_.begin(), composeSig_.end());  // (reserved: no allocation)
-    schedCompose_ = compose;
-    if (isBatch && !changed) changed = batchSig_ != schedBatchSig_;
-    if (isBatch && changed) schedBatchSig_.assign(batchSig_.begin(), batchSig_.end());  // (reserved: no allocation)
-    schedBatch_ = isBatch;
-    if (changed) {  // new geometry: no walks to order by yet (either schedule set)
+const ScheduleKey& GlobalRenderer::requestKey(const FrameRequest& rq, uint32_t* tiles) {
+    const FramePayload& p = rq.payload;
+    // (the records path walks the single frame's units of the handle's rows: it shares the Single key, so a slab
+    // ordered by partitionCounts and one ordered by renderRecords itself keep one set of costs)
+    key_.reset(p.kind == FrameKind::Records ? FrameKind::Single : p.kind);
+    *tiles = rowCount() * tilesX_;  // (a composite: the single frame's units)
+    if (const ViewBatch* vb = p.views()) {
+        *tiles = vb->views * tiles_of(rq.width, rq.height);
+        key_[ScheduleKey::kViewCount] = vb->views;
+    } else if (const BatchFrame* bf = p.batch()) {  // (every view's width, height and count: batchHost_)
+        *tiles = bf->tiles;
+        key_[ScheduleKey::kViewCount] = bf->views;
+        for (uint32_t v = 0; v < bf->views; ++v) {
+            key_.push(batchHost_[v].tg.width);
+            key_.push(batchHost_[v].tg.height);
+            key_.push(batchHost_[v].count);
+        }
+    } else if (const ComposeFrame* cf = p.compose()) {  // (every object's count: composeHost_, 0 without an entry)
+        key_[ScheduleKey::kViewCount] = cf->objects;
+        for (uint32_t o = 0, e = 0; o < cf->objects; ++o) {
+            const bool has = e < cf->entries && composeObject_[e] == o;
+            key_.push(has ? composeHost_[e].count : 0u);
+            e += has ? 1u : 0u;
+        }
+    }
+    // (a pick frame walks without compaction or pairs, an occluded frame's walks end at the occluder, a styled
+    // frame hides and fades gaussians: their costs are their own, either way round)
+    key_[ScheduleKey::kPick] = rq.pick ? 1u : 0u;
+    key_[ScheduleKey::kOccluded] = rq.occluder ? 1u : 0u;
+    key_[ScheduleKey::kStyled] = rq.styled ? 1u : 0u;
+    key_[ScheduleKey::kUnitsPerTile] = blend_units_per_tile(*tiles, dev_.numCUs);
+    key_[ScheduleKey::kWidth] = rq.width;
+    key_[ScheduleKey::kHeight] = rq.height;
+    key_[ScheduleKey::kRowBegin] = rowBegin_;
+    key_[ScheduleKey::kRowEnd] = rowEnd_;
+    key_[ScheduleKey::kRowStride] = rowStride_;
+    return key_;
+}
+
+uint32_t GlobalRenderer::scheduleUnits(hipStream_t s, const ScheduleKey& key, uint32_t tiles) {
+    const uint32_t units = tiles * key[ScheduleKey::kUnitsPerTile];
+    if (schedState_.update(key)) {  // another frame: no walks to order by yet (either schedule set)
         for (const ScheduleSet& t : sched_) {
             if (!t.unitCost) continue;
             hipMemsetAsync(t.unitCost, 0, (size_t)units * sizeof(uint16_t), s);
             hipMemsetAsync(t.costMax, 0, (kCostMaxSlots + 2) * sizeof(uint32_t), s);
         }
-        schedKey_ = key;
-        schedViews_ = views;
     }
     return tuning_.costOrder ? units : 0u;
 }
 
 template <class Front>
-gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_t width, uint32_t height,
-                                    void* color, size_t colorPitch, void* depth, size_t depthPitch,
-                                    Front&& front, const uint32_t* devCount, bool preOrdered,
-                                    const MgArrive* blendArrive, const ViewFrame* views, const PickTarget* pick,
-                                    const OccluderSource* occluder, bool styled) {
+gsm_status GlobalRenderer::runFrame(hipStream_t s, const FrameRequest& rq, Front&& front) {
     (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's: the launches below are checked)
+    const ProjectArgs& a = rq.args;
+    const FrameTargets& tg = rq.targets;
     const int profiling = timer_.flags();
     const bool keep = (profiling & 2) != 0;
     // captured frame: the reference's intermediates (render data, sorted keys / values) are kept
     // for readback; the product path writes neither (the blend reads its records and half lists)
     const bool capture = (profiling & (2 | 16)) != 0;
-    // (a batch of views: a.count gaussians per view, every view's items padded to whole blocks)
-    const BatchFrame* batch = views && views->batchFrame.views ? &views->batchFrame : nullptr;
-    // (a composite: the objects' items padded to whole blocks, everything from the scan on the single frame's)
-    const ComposeFrame* comp = views && views->compose.objects ? &views->compose : nullptr;
-    if (comp) views = nullptr;
-    const uint32_t nb = comp ? comp->blocks : batch ? batch->blocks
-                        : views ? views->batch.views * views->batch.blocksPerView
-                                : (a.count + kProjectBlock - 1) / kProjectBlock;
+    // (Views: a.count gaussians per view, every view's items padded to whole blocks.  Batch: the same per view.
+    // Compose: the objects' items padded to whole blocks, everything from the scan on the single frame's)
+    const ViewBatch* views = rq.payload.views();
+    const BatchFrame* batch = rq.payload.batch();
+    const ComposeFrame* comp = rq.payload.compose();
+    const uint32_t nb = comp ? comp->blocks : batch ? batch->blocks : views ? views->views * views->blocksPerView
+                                                                            : (a.count + kProjectBlock - 1) / kProjectBlock;
     // GaussianRenderData for readback only when profiling (bits 0, 1), gsm_debug.h
     ProjectArgs fa = a;
     fa.keepRenderData = capture ? 1u : 0u;
     keptRenderData_ = fa.keepRenderData != 0;
     lastCount_ = a.count;
     lastItems_ = comp ? comp->blocks * (uint32_t)kProjectBlock : a.count;
-    lastWidth_ = width;
-    lastHeight_ = height;
-    lastPick_ = pick != nullptr;
-    lastPickComposite_ = pick && comp;
+    lastWidth_ = rq.width;
+    lastHeight_ = rq.height;
+    lastPick_ = rq.pick != nullptr;
+    lastPickComposite_ = rq.pick && comp;
     // Blend schedule: the units ordered by the walk lengths the previous frame of the same
-    // geometry measured (the image does not depend on the order, only the load balance does).
+    // key measured (the image does not depend on the order, only the load balance does).
     // The ordering only needs those costs: one extra workgroup of the projection launch does it
     // (unit_order_block) while the others project (k_project, or k_records_in on the records path;
     // the multi-GPU frame orders them earlier, in its partition projection: preOrdered).
-    const uint32_t units = preOrdered ? 0u
-                                      : scheduleUnits(s, width, height, batch ? batch->views : views ? views->batch.views : 0u,
-                                                      batch ? batch->tiles : 0u, comp != nullptr, pick != nullptr,
-                                                      occluder != nullptr, styled);
-    const bool costOrder = preOrdered ? tuning_.costOrder : units > 0;
+    uint32_t units = 0;
+    if (!rq.preOrdered) {
+        uint32_t tiles = 0;
+        const ScheduleKey& key = requestKey(rq, &tiles);
+        units = scheduleUnits(s, key, tiles);
+    }
+    const bool costOrder = rq.preOrdered ? tuning_.costOrder : units > 0;
     fa.schedUnits = units;
     // (written on every scheduled frame: the blend's remaining-walk priorities read the longest walk too)
     fa.pairBucket = tuning_.blendPairs ? (uint32_t)std::max(1, tuning_.pairBucket) : kUoBuckets;
@@ -916,10 +882,10 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     // (devCount: a multi-GPU slab) sizes its grids for the receive capacity but adds up only the blocks of
     // the records received -- at 8 ranks ~1/8 of a frame's gaussians -- so it takes the fused scan up to 4x
     // the block count (a slab that receives more than 2M records pays a longer prefix instead of the launch)
-    const bool fusedScan = tuning_.fusedScan && nb > 0 && nb <= (devCount ? 4u : 1u) * kFusedScanMaxBlocks;
-    if (!fusedScan) launch_scan_blocks(nb, a, arena_, s, devCount);
+    const bool fusedScan = tuning_.fusedScan && nb > 0 && nb <= (rq.devCount ? 4u : 1u) * kFusedScanMaxBlocks;
+    if (!fusedScan) launch_scan_blocks(nb, a, arena_, s, rq.devCount);
     timer_.record(2, s);
-    launch_scatter(a, arena_, s, devCount, fusedScan, views && !batch ? &views->batch : nullptr, batch, comp);
+    launch_scatter(a, arena_, s, rq.payload, rq.devCount, fusedScan);
     if (keep) {  // preserve the unsorted assignment arrays for readback
         hipMemcpyAsync(arena_.keysKeep, arena_.keys[0], (size_t)maxAssignments_ * 4, hipMemcpyDeviceToDevice, s);
         hipMemcpyAsync(arena_.valsKeep, arena_.vals[0], (size_t)maxAssignments_ * 4, hipMemcpyDeviceToDevice, s);
@@ -928,6 +894,7 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     uint32_t* kb[2] = {arena_.keys[0], arena_.keys[1]};
     uint32_t* vb[2] = {arena_.vals[0], arena_.vals[1]};
     FrameGeometry g;
+    g.kind = rq.payload.kind;
     g.tilesX = tilesX_;
     g.tilesY = tilesY_;
     g.tileCount = tileCount_;
@@ -935,8 +902,8 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     g.rowEnd = rowEnd_;
     g.rowStride = rowStride_;
     g.rowCount = rowCount();
-    g.width = width;
-    g.height = height;
+    g.width = rq.width;
+    g.height = rq.height;
     g.maxAssignments = maxAssignments_;
     if (batch) {  // every view on its own grid, one after another in the handle's tile space
         g.rowBegin = 0;
@@ -951,10 +918,10 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
         g.rowBegin = 0;
         g.rowEnd = g.rowCount = g.tilesY;
         g.rowStride = 1;
-        g.views = views->batch.views;
-        g.tilesPerView = views->batch.tilesPerView;
-        g.colorViewStride = views->colorStride;
-        g.depthViewStride = views->depthStride;
+        g.views = views->views;
+        g.tilesPerView = views->tilesPerView;
+        g.colorViewStride = rq.payload.colorViewStride;
+        g.depthViewStride = rq.payload.depthViewStride;
     }
     // Frame sort.  Default: a stable LSD sort by the tile field only
     // (ceil(tileBits / 8) passes, the last one writing the tile starts), then each tile's run sorted
@@ -976,10 +943,10 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
         if (res == kSortNoSpace) return GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;  // (nothing of the sort launched)
         tile_depth_sort(kb[res], vb[res], kb[res ^ 1], vb[res ^ 1], arena_.tileStart, 0u, localTiles, s, ballot,
                         arena_.halfVals[0], arena_.halfVals[1],
-                        arena_.halfCount, tileCount_, capture || occluder, dev_.numCUs);
+                        arena_.halfCount, tileCount_, capture || rq.occluder, dev_.numCUs);
         sortedKeys_ = capture ? kb[res ^ 1] : nullptr;
         sortedVals_ = capture ? vb[res ^ 1] : nullptr;
-        blendRun = occluder ? vb[res ^ 1] : nullptr;
+        blendRun = rq.occluder ? vb[res ^ 1] : nullptr;
     } else {
         const int res = radix_sort_pairs(kb, vb, &arena_.header->totalAssignments, maxAssignments_, 0,
                                          sortPassCount(), sort_space(arena_), s, ballot,
@@ -1000,10 +967,18 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const ProjectArgs& a, uint32_
     arena_.blendTrace = (profiling & 4) ? traceBuf_ : nullptr;
     // the schedule from the walks the previous frame's blend recorded (same stream: no join)
     timer_.record(5, s, true);
-    lastBlendKernel_ = launch_blend(g, arena_, color, colorPitch, depth, depthPitch, dev_.numCUs, costOrder,
-                 (int)config_.color_format, s, tuning_.blendWaves, tuning_.blendClaim, blendArrive,
-                 tuning_.blendPairs, pick ? pick->pixels : nullptr, pick ? pick->pitch : 0,
-                 occluder ? occluder->pixels : nullptr, occluder ? occluder->pitch : 0, blendRun);
+    BlendOptions bo;
+    bo.costOrder = costOrder;
+    bo.colorFormat = (int)config_.color_format;
+    bo.waves = tuning_.blendWaves;
+    bo.claim = tuning_.blendClaim;
+    bo.pairs = tuning_.blendPairs;
+    bo.arrive = rq.blendArrive;
+    bo.pick = rq.pick;
+    bo.occluder = rq.occluder;
+    bo.sortedVals = blendRun;
+    bo.numCUs = dev_.numCUs;
+    lastBlendKernel_ = launch_blend(g, arena_, tg, bo, s);
     timer_.record(6, s, true);
     timer_.frameDone();
     if (hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;

@@ -9,8 +9,25 @@
 #include "../../include/gsm_renderer.h"
 #include "gsm_host.h"
 #include "gsm_internal.h"
+#include "gsm_schedule_key.h"
 
 namespace gsm {
+
+// What the entries of a family add to the plain frame, all nullable (pick and occluder never both):
+// pick: a per-pixel pick target, the item of each pixel's heaviest contribution;
+// occluder: the frame cut, pixel by pixel, at the depth of an opaque surface, one float per pixel, read only
+// (DESIGN.md 21); style: the style of every gaussian's state byte applied in the projection --
+// the caller's states, one per object, and its table: host memory, consumed by the call.
+struct StyleSource {
+    const gsm_global_state* states;
+    const gsm_global_style* styles;
+    uint32_t styleCount;
+};
+struct FrameExtras {
+    const PickTarget* pick = nullptr;
+    const OccluderSource* occluder = nullptr;
+    const StyleSource* style = nullptr;
+};
 
 class GlobalRenderer {
    public:
@@ -18,10 +35,16 @@ class GlobalRenderer {
     static gsm_status create(const gsm_renderer_config& cfg, int hipDevice, GlobalRenderer** out);
     ~GlobalRenderer() { hipSetDevice(dev_.id); }  // (the events and buffers are released on their device)
 
-    // GlobalRenderer.render (GlobalRenderer.swift:201-238)
-    gsm_status render(hipStream_t stream, const gsm_gaussian_input& input,
-                      const gsm_camera_params& camera, uint32_t width, uint32_t height, void* color,
-                      size_t colorPitch, void* depth, size_t depthPitch);
+    // GlobalRenderer.render (GlobalRenderer.swift:201-238): gsm_global_render and its pick / occluded / styled
+    // entries
+    gsm_status renderFrame(hipStream_t stream, const gsm_gaussian_input& input, const gsm_camera_params& camera,
+                           uint32_t width, uint32_t height, const FrameTargets& targets,
+                           const FrameExtras& extras = {});
+    // several posed objects in one frame over one tile space and one target: gsm_global_render_composite and its
+    // pick / occluded / styled entries
+    gsm_status composeFrame(hipStream_t stream, const gsm_global_object* objects, uint32_t objectCount,
+                            uint32_t width, uint32_t height, const FrameTargets& targets,
+                            const FrameExtras& extras = {});
 
     // several views of one scene in one frame over a combined tile space (gsm_global_render_views)
     gsm_status renderViews(hipStream_t stream, const gsm_gaussian_input& input, const gsm_camera_params* cameras,
@@ -31,39 +54,6 @@ class GlobalRenderer {
     // views of different scenes and sizes in one frame (gsm_global_render_batch)
     gsm_status renderBatch(hipStream_t stream, const gsm_global_view* views, uint32_t viewCount);
 
-    // several posed objects in one frame over one tile space and one target (gsm_global_render_composite,
-    // DESIGN.md 19)
-    gsm_status renderComposite(hipStream_t stream, const gsm_global_object* objects, uint32_t objectCount,
-                               uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                               size_t depthPitch);
-
-    // render / renderComposite with a per-pixel pick target: the item of each pixel's heaviest contribution
-    // (gsm_global_render_pick, gsm_global_render_composite_pick)
-    gsm_status renderPick(hipStream_t stream, const gsm_gaussian_input& input, const gsm_camera_params& camera,
-                          uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                          size_t depthPitch, void* pick, size_t pickPitch);
-    gsm_status renderCompositePick(hipStream_t stream, const gsm_global_object* objects, uint32_t objectCount,
-                                   uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                                   size_t depthPitch, void* pick, size_t pickPitch);
-    // render / renderComposite cut, pixel by pixel, at the depth of an opaque surface: one float per pixel, read
-    // only (gsm_global_render_occluded, gsm_global_render_composite_occluded)
-    gsm_status renderOccluded(hipStream_t stream, const gsm_gaussian_input& input, const gsm_camera_params& camera,
-                              uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                              size_t depthPitch, const void* occluder, size_t occluderPitch);
-    gsm_status renderCompositeOccluded(hipStream_t stream, const gsm_global_object* objects, uint32_t objectCount,
-                                       uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                                       size_t depthPitch, const void* occluder, size_t occluderPitch);
-    // render / renderComposite with the style of every gaussian's state byte applied in the projection; pick
-    // null: the plain blend, else the pick frame (gsm_global_render_styled, gsm_global_render_composite_styled,
-    // DESIGN.md 22).  state / states and styles are host memory, consumed by the call.
-    gsm_status renderStyled(hipStream_t stream, const gsm_gaussian_input& input, const gsm_camera_params& camera,
-                            uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                            size_t depthPitch, void* pick, size_t pickPitch, const gsm_global_state* state,
-                            const gsm_global_style* styles, uint32_t styleCount);
-    gsm_status renderCompositeStyled(hipStream_t stream, const gsm_global_object* objects, uint32_t objectCount,
-                                     uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                                     size_t depthPitch, void* pick, size_t pickPitch, const gsm_global_state* states,
-                                     const gsm_global_style* styles, uint32_t styleCount);
     // state bytes of the gaussians whose projected centre lies on a nonzero mask byte (gsm_global_select_mask)
     gsm_status selectMask(hipStream_t stream, const gsm_gaussian_input* input, const gsm_camera_params* camera,
                           uint32_t width, uint32_t height, const void* mask, size_t maskPitch, uint8_t* state,
@@ -135,57 +125,39 @@ class GlobalRenderer {
 
    private:
     GlobalRenderer() = default;
-    // render, renderPick and renderOccluded; renderComposite, renderCompositePick and renderCompositeOccluded
-    // (pick, occluder: null for the plain entries, never both)
-    // (style: null for every entry but the styled ones -- the caller's states, one per object, and its table)
-    struct StyleSource {
-        const gsm_global_state* states;
-        const gsm_global_style* styles;
-        uint32_t styleCount;
-    };
-    gsm_status renderFrame(hipStream_t stream, const gsm_gaussian_input& input, const gsm_camera_params& camera,
-                           uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                           size_t depthPitch, const PickTarget* pick, const OccluderSource* occluder = nullptr,
-                           const StyleSource* style = nullptr);
-    gsm_status composeFrame(hipStream_t stream, const gsm_global_object* objects, uint32_t objectCount,
-                            uint32_t width, uint32_t height, void* color, size_t colorPitch, void* depth,
-                            size_t depthPitch, const PickTarget* pick, const OccluderSource* occluder = nullptr,
-                            const StyleSource* style = nullptr);
     // a styled entry's own refusals (GSM_ERR_INVALID_ARGUMENT), checked after the plain entry's
     static bool styleSourceOk(const StyleSource& style, uint32_t stateCount);
     // the handle's style table: allocated by its first use, filled from the caller's styles (identity past them)
     gsm_status fillStyleTable(hipStream_t s, const gsm_global_style* styles, uint32_t styleCount);
     ProjectArgs frameArgs(const gsm_camera_params& camera, uint32_t width, uint32_t height, uint32_t count,
                           uint32_t shComponents) const;
-    // scan, scatter, sort, headers and blend after `front` filled the per-gaussian arrays
-    // (views: a batch -- `a` holds what its views share, the targets are view 0's)
-    // (batchFrame.views > 0: a batch of different views -- `a` holds what they share, nothing per view)
-    // (compose.objects > 0: a composite -- `a` is the frame's, as a single frame's; only the items differ)
-    struct ViewFrame {
-        ViewBatch batch;
-        size_t colorStride = 0, depthStride = 0;
-        BatchFrame batchFrame;
-        ComposeFrame compose;
+    // One description of a frame: what runFrame enqueues after `front` filled the per-gaussian arrays.
+    // (Views: args holds what the views share, the targets are view 0's.  Batch: args holds what the views share,
+    // nothing per view.  Compose: args is the frame's, as a single frame's; only the items differ.)
+    struct FrameRequest {
+        ProjectArgs args;
+        uint32_t width = 0, height = 0;
+        FrameTargets targets;
+        FramePayload payload;  // the kind and its payload
+        const PickTarget* pick = nullptr;
+        const OccluderSource* occluder = nullptr;
+        bool styled = false;  // the projection applies styles: the walks are the frame's own (schedule key)
+        // the records path: the count on the device, the units ordered by an earlier partitionCounts, the barrier
+        // the blend's waves arrive at
+        const uint32_t* devCount = nullptr;
+        bool preOrdered = false;
+        const MgArrive* blendArrive = nullptr;
     };
+    FrameRequest request(FrameKind kind, const ProjectArgs& args, uint32_t width, uint32_t height,
+                         const FrameTargets& targets) const;
+    // scan, scatter, sort, headers and blend around front(args): the projection (or records) launch
     template <class Front>
-    gsm_status runFrame(hipStream_t s, const ProjectArgs& a, uint32_t width, uint32_t height, void* color,
-                        size_t colorPitch, void* depth, size_t depthPitch, Front&& front,
-                        const uint32_t* devCount = nullptr, bool preOrdered = false,
-                        const MgArrive* blendArrive = nullptr, const ViewFrame* views = nullptr,
-                        const PickTarget* pick = nullptr, const OccluderSource* occluder = nullptr,
-                        bool styled = false);
-    // the blend schedule's unit count for the current rows, or for a batch of `views` frames (0 when cost
-    // order is off), its cost arrays cleared when the geometry or the view count changed
-    // (batchTiles > 0: a batch of different views, keyed by its signature batchSig_ -- the view count and every
-    // view's width, height and count)
-    // (compose: a composite, on the single frame's units, keyed by its signature composeSig_ -- the size, the
-    // object count and every object's count)
-    // (pick: a pick frame -- part of the key, so it neither inherits walk costs from a plain frame nor leaves any)
-    // (occluded: an occluded frame -- part of the key in the same way)
-    // (styled: a styled frame -- hidden and faded gaussians change the walks -- part of the key in the same way)
-    uint32_t scheduleUnits(hipStream_t s, uint32_t width, uint32_t height, uint32_t views = 0,
-                           uint32_t batchTiles = 0, bool compose = false, bool pick = false, bool occluded = false,
-                           bool styled = false);
+    gsm_status runFrame(hipStream_t s, const FrameRequest& rq, Front&& front);
+    // the request's schedule key in key_ (reserved: no allocation) and the tiles its blend units cover
+    const ScheduleKey& requestKey(const FrameRequest& rq, uint32_t* tiles);
+    // the blend schedule's unit count for a frame of that key over `tiles` tiles (0 when cost order is off), the
+    // cost arrays cleared when the key is not the one they belong to
+    uint32_t scheduleUnits(hipStream_t s, const ScheduleKey& key, uint32_t tiles);
     static uint32_t tiles_of(uint32_t width, uint32_t height);  // tiles of a width x height frame
     // checks and arguments renderViews and renderBatch share: a view's size within the handle's, a batch's
     // tiles within its tile space and the key's 16-bit field, no set_tile_rows restriction, and the
@@ -236,22 +208,13 @@ class GlobalRenderer {
     const uint32_t* unsortedKeys_ = nullptr;
     const uint32_t* unsortedVals_ = nullptr;
     unsigned long long* traceBuf_ = nullptr;  // blend unit trace (profiling bit 2)
-    uint64_t schedKey_ = ~0ull;               // geometry the unit costs belong to
-    uint32_t schedViews_ = 0;                 // ... and the view count (0: a single frame)
+    ScheduleKey key_;                         // this call's schedule key
+    ScheduleState schedState_;                // the key the unit costs belong to
     std::vector<ViewArgs> viewHost_;          // the last batch's per-view terms (render_views)
     uint32_t maxViews_ = 0;                   // entries of arena_.viewArgs
     std::vector<BatchViewArgs> batchHost_;    // the last batch's per-view entries (render_batch)
     uint32_t maxBatchViews_ = 0;              // entries of arena_.batchArgs
-    std::vector<uint32_t> batchSig_;          // this call's batch signature: width, height, count of every view
-    std::vector<uint32_t> schedBatchSig_;     // the signature the unit costs belong to (schedBatch_)
-    bool schedBatch_ = false;                 // the unit costs belong to a batch of different views
     std::vector<ComposeObjectArgs> composeHost_;  // the last composite's per-object entries (render_composite)
-    std::vector<uint32_t> composeSig_;        // this call's composite signature: width, height, every object's count
-    std::vector<uint32_t> schedComposeSig_;   // the signature the unit costs belong to (schedCompose_)
-    bool schedCompose_ = false;               // the unit costs belong to a composite
-    bool schedPick_ = false;                  // the unit costs belong to a pick frame
-    bool schedOccluded_ = false;              // the unit costs belong to an occluded frame
-    bool schedStyled_ = false;                // the unit costs belong to a styled frame
     std::vector<uint32_t> composeObject_;     // the call's object index of every entry of composeHost_
     bool lastPick_ = false;                   // the last enqueued frame was a pick frame (pickOwner)
     bool lastPickComposite_ = false;          // ... of a composite: its owners are composeHost_ / composeObject_

@@ -8,6 +8,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "gsm_schedule_key.h"
+
 namespace gsm {
 
 // BridgingTypes.h:57-64 -- 48 B, align 16.
@@ -130,27 +132,27 @@ static_assert(offsetof(StereoTiledRenderData, colorR) == 24, "layout");
 
 // Tile-slab bookkeeping for one frame.
 struct FrameGeometry {
+    FrameKind kind = FrameKind::Single;  // which of the fields below the frame's sort and blend read
     uint32_t tilesX, tilesY, tileCount;
     uint32_t rowBegin, rowEnd;  // tile rows owned by this renderer: rowBegin, + rowStride, ... < rowEnd
     uint32_t rowStride, rowCount;
     uint32_t width, height;     // frame (camera) size
     uint32_t maxAssignments;
-    // A batch of views (gsm_global_render_views): `views` frames of tilesX x tilesY tiles
-    // in one tile space, tile v * tilesPerView + local tile; view v's targets start viewStride bytes
-    // after view v - 1's.  views == 0: a single frame.
+    // Views (gsm_global_render_views): `views` frames of tilesX x tilesY tiles in one tile space,
+    // tile v * tilesPerView + local tile; view v's targets start viewStride bytes after view v - 1's.
     uint32_t views = 0, tilesPerView = 0;
     size_t colorViewStride = 0, depthViewStride = 0;
-    // A batch of views of different scenes and sizes (gsm_global_render_batch): batchTiles > 0
-    // tiles in all, every view on its own grid; the blend reads a unit's view from batchTileView and its
-    // targets, size and grid from that view's entry of batchArgs (BatchViewArgs, device pointers).
+    // Batch (gsm_global_render_batch): batchTiles tiles in all, every view on its own grid; the
+    // blend reads a unit's view from batchTileView and its targets, size and grid from that view's entry of
+    // batchArgs (BatchViewArgs, device pointers).
     uint32_t batchTiles = 0;
     const void* batchArgs = nullptr;
     const uint16_t* batchTileView = nullptr;
 };
 // tiles the frame's sort and blend cover
 inline uint32_t frame_tiles(const FrameGeometry& g) {
-    if (g.batchTiles) return g.batchTiles;
-    return g.views ? g.views * g.tilesPerView : g.rowCount * g.tilesX;
+    if (g.kind == FrameKind::Batch) return g.batchTiles;
+    return g.kind == FrameKind::Views ? g.views * g.tilesPerView : g.rowCount * g.tilesX;
 }
 
 constexpr uint32_t kTileWidth = 32;   // GlobalRenderer.swift:74
