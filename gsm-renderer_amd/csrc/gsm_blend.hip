@@ -154,6 +154,11 @@ __device__ __forceinline__ uint32_t occ_open_mask(uint32_t bd, uint32_t keys) {
 #define GSM_BLEND_VIEWS 0
 #include "gsm_blend_px_body.h"
 #undef GSM_BLEND_VIEWS
+#undef GSM_BLEND_PICK
+#define GSM_BLEND_PICK 1
+#define GSM_BLEND_VIEWS 0
+#include "gsm_blend_px_body.h"
+#undef GSM_BLEND_VIEWS
 #undef GSM_BLEND_OCCLUDE
 #undef GSM_BLEND_PICK
 
@@ -234,6 +239,25 @@ int launch_blend(const FrameGeometry& g, const DeviceArena& A, const FrameTarget
     // A pick frame: the single frame's walk that also writes the pick target -- quadrant or
     // half-tile units by the rule above, no compaction, no pair walk.  (Whole frames of one GPU only: the host
     // refuses tile rows, and no batch or gathered frame has a pick entry.)
+    // A frame with a pick target and an occluder (gsm_global_render_frame): the occluded walk over the
+    // whole sorted runs that also tracks the pick -- the units and rules of both, the alignment flags of both.
+    if (o.pick && o.occluder) {
+        if (!o.sortedVals) return 0;  // (the host passes them with every occluder)
+        uint8_t* const pick = (uint8_t*)o.pick->pixels;
+        const size_t pickPitch = o.pick->pitch;
+        const uint8_t* const occluder = (const uint8_t*)o.occluder->pixels;
+        const size_t occluderPitch = o.occluder->pitch;
+        const int pflags = flags | (((((uintptr_t)pick) & 7u) == 0 && (pickPitch & 7u) == 0) ? 8192 : 0) |
+                           (((((uintptr_t)occluder) & 7u) == 0 && (occluderPitch & 7u) == 0) ? 16384 : 0);
+        dispatch_blend(waves, P, numTiles, numCUs, [&](auto NTH, auto PP, uint32_t grid) {
+            hipLaunchKernelGGL((k_blend_px_occ_pick<decltype(NTH)::value, decltype(PP)::value, false>), dim3(grid),
+                               dim3(decltype(NTH)::value), 0, s, A.tileStart, A.rec, A.expTable, A.tileQueue, numTiles,
+                               g.tilesX, g.width, g.height, color, colorPitch, depth, depthPitch, pick, pickPitch,
+                               occluder, occluderPitch, pflags, order, A.unitCost, A.blendTrace, A.halfVals[0],
+                               A.halfVals[1], A.halfCount, g.tileCount, A.costMax, o.sortedVals);
+        });
+        return kernel;
+    }
     if (o.pick) {
         uint8_t* const pick = (uint8_t*)o.pick->pixels;
         const size_t pickPitch = o.pick->pitch;

@@ -17,6 +17,10 @@
 // walk: whole frames on one GPU, no compaction.  It walks the tile's whole sorted run, not the half lists: an
 // entry that a half list drops (alpha 0 on the whole half) blends nothing, but it can close a pixel, and the
 // group break of the entries after it sees that pixel's transmittance as +0.
+// A sixth time with both (GSM_BLEND_OCCLUDE 1, GSM_BLEND_PICK 1): k_blend_px_occ_pick, the occluded walk that also
+// tracks the pick (gsm_global_render_frame).  The weight is taken after the open mask has zeroed the
+// alpha of a closed pixel, from the same w the colour FMA uses: a closed pixel never updates its pick, and colour
+// and depth are k_blend_px_occ's.
 #define GSM_BLEND_NOCOMPACT (GSM_BLEND_PICK || GSM_BLEND_OCCLUDE)
 #if GSM_BLEND_OCCLUDE
 #define GSM_LIST_ID(v) ((v) & kGidMask)  // the sorted run's values carry the half-tile skip flags
@@ -30,6 +34,22 @@
 #if GSM_BLEND_PICK
 #define GSM_PICK_PARAMS , uint32_t pk0, uint32_t pk1  // the pixel pair's picks travel with its colour
 #define GSM_PICK_ARGS(q) , pk[q][0], pk[q][1]
+#endif
+#if GSM_BLEND_PICK && GSM_BLEND_OCCLUDE
+template <int NT, int P, bool COMPACT = false>
+__global__ __launch_bounds__(NT) void k_blend_px_occ_pick(
+    const uint32_t* __restrict__ tileStart, const BlendRecord* __restrict__ rec,
+    const uint16_t* __restrict__ expTable, uint32_t* __restrict__ queue, uint32_t numTiles, uint32_t tilesX,
+    uint32_t W, uint32_t H, uint8_t* __restrict__ color, size_t colorPitch, uint8_t* __restrict__ depth,
+    size_t depthPitch, uint8_t* __restrict__ pickOut, size_t pickPitch, const uint8_t* __restrict__ occIn,
+    size_t occPitch, int flags, const uint32_t* __restrict__ order, uint16_t* __restrict__ unitCost,
+    unsigned long long* __restrict__ trace, const uint32_t* __restrict__ half0, const uint32_t* __restrict__ half1,
+    const uint32_t* __restrict__ halfCount, uint32_t tileCount, uint32_t* __restrict__ costMax,
+    const uint32_t* __restrict__ sortedVals) {
+    static_assert(!COMPACT, "the occluded pick walk keeps its unit layout");
+    constexpr uint32_t tileBegin = 0, rowBegin = 0, rowStride = 1;  // whole frames on one GPU: no tile rows, no gather
+    const MgArrive arrive{};
+#elif GSM_BLEND_PICK
 template <int NT, int P, bool COMPACT = false>
 __global__ __launch_bounds__(NT) void k_blend_px_pick(
     const uint32_t* __restrict__ tileStart, const BlendRecord* __restrict__ rec,
@@ -55,24 +75,6 @@ __global__ __launch_bounds__(NT) void k_blend_px_occ(
     static_assert(!COMPACT, "the occluded walk keeps its unit layout");
     constexpr uint32_t tileBegin = 0, rowBegin = 0, rowStride = 1;  // whole frames on one GPU: no tile rows, no gather
     const MgArrive arrive{};
-    // the limits of the pixel pair (px, py), (px + 1, py): the occluder's two floats as packed fp16 bits (one
-    // round-to-nearest-even conversion each, denormals kept); +inf for a pixel outside the frame, which is not
-    // read.  One 8-byte load where the occluder is aligned for it (flags bit 14; px is even).
-    auto load_limits = [&](uint32_t px, uint32_t py) -> uint32_t {
-        float z0 = __builtin_inff(), z1 = __builtin_inff();
-        if (py < H) {
-            const uint8_t* zrow = occIn + (size_t)py * occPitch + (size_t)px * 4;
-            if ((flags & 16384) && px + 1 < W) {
-                const float2 z = *(const float2*)zrow;
-                z0 = z.x;
-                z1 = z.y;
-            } else {
-                if (px < W) z0 = *(const float*)zrow;
-                if (px + 1 < W) z1 = *(const float*)(zrow + 4);
-            }
-        }
-        return as_u32(h2{(h1)z0, (h1)z1});
-    };
 #elif GSM_BLEND_VIEWS == 2
 // the blend of a batch of different views (gsm_global_render_batch): numTiles = the sum of the views' tiles
 template <int NT, int P, bool COMPACT = false>
@@ -116,6 +118,26 @@ __global__ __launch_bounds__(NT) void k_blend_px(
     unsigned long long* __restrict__ trace, const uint32_t* __restrict__ half0,
     const uint32_t* __restrict__ half1, const uint32_t* __restrict__ halfCount, uint32_t tileCount,
     uint32_t* __restrict__ costMax, uint32_t rowBegin, uint32_t rowStride, MgArrive arrive) {
+#endif
+#if GSM_BLEND_OCCLUDE
+    // the limits of the pixel pair (px, py), (px + 1, py): the occluder's two floats as packed fp16 bits (one
+    // round-to-nearest-even conversion each, denormals kept); +inf for a pixel outside the frame, which is not
+    // read.  One 8-byte load where the occluder is aligned for it (flags bit 14; px is even).
+    auto load_limits = [&](uint32_t px, uint32_t py) -> uint32_t {
+        float z0 = __builtin_inff(), z1 = __builtin_inff();
+        if (py < H) {
+            const uint8_t* zrow = occIn + (size_t)py * occPitch + (size_t)px * 4;
+            if ((flags & 16384) && px + 1 < W) {
+                const float2 z = *(const float2*)zrow;
+                z0 = z.x;
+                z1 = z.y;
+            } else {
+                if (px < W) z0 = *(const float*)zrow;
+                if (px + 1 < W) z1 = *(const float*)(zrow + 4);
+            }
+        }
+        return as_u32(h2{(h1)z0, (h1)z1});
+    };
 #endif
     static_assert(P == 1 || P == 2, "pairs per lane: quadrant or half-tile units (half-tile lists)");
     static_assert(!COMPACT || P == 2, "compaction: half tiles");
@@ -743,7 +765,10 @@ __global__ __launch_bounds__(NT) void k_blend_px(
     unit_end:
 #endif
         if (exactD)  // (rare: a record of inf / NaN fp16 depth; every pixel of the unit is written again)
-#if GSM_BLEND_OCCLUDE
+#if GSM_BLEND_OCCLUDE && GSM_BLEND_PICK
+            blend_exact::walk_unit_exact<P, true, true>(sortedVals + start, count, rec, tbl, lrecA[wv], lrecB[wv], ux,
+                                                        uy, thrBits, write_pair, litem[wv], load_limits, kGidMask);
+#elif GSM_BLEND_OCCLUDE
             blend_exact::walk_unit_exact<P, false, true>(sortedVals + start, count, rec, tbl, lrecA[wv], lrecB[wv], ux,
                                                          uy, thrBits, write_pair, nullptr, load_limits, kGidMask);
 #elif GSM_BLEND_PICK

@@ -190,6 +190,32 @@ gsm_status gsm_global_select_mask(gsm_renderer* r, void* stream, const gsm_gauss
                                style_count, and_mask, xor_mask, matched);
 }
 
+gsm_status gsm_global_render_frame(gsm_renderer* r, void* stream, const gsm_global_frame* f) {
+    if (!r || !r->impl || !f || f->flags != 0) return GSM_ERR_INVALID_ARGUMENT;
+    const gsm::PickTarget pt{f->pick_r32u, f->pick_pitch_bytes};
+    const gsm::OccluderSource os{f->occluder_r32f, f->occluder_pitch_bytes};
+    const gsm::StyleSource ss{f->states, f->styles, f->style_count};
+    gsm::FrameExtras extras;  // (a null pointer: the option is not given)
+    extras.pick = f->pick_r32u ? &pt : nullptr;
+    extras.occluder = f->occluder_r32f ? &os : nullptr;
+    extras.style = (f->states || f->styles) ? &ss : nullptr;  // (one without the other: the styled row refuses)
+    const gsm::FrameTargets targets{f->color, f->color_pitch_bytes, f->depth_r16f, f->depth_pitch_bytes};
+    if (f->object_count == 1 && f->objects)  // one object: the single frame
+        return r->impl->renderFrame((hipStream_t)stream, f->objects[0].input, f->objects[0].camera, f->width,
+                                    f->height, targets, extras);
+    return r->impl->composeFrame((hipStream_t)stream, f->objects, f->object_count, f->width, f->height, targets,
+                                 extras);
+}
+
+gsm_status gsm_global_select_pick(gsm_renderer* r, void* stream, const void* pick, size_t pick_pitch, uint32_t width,
+                                  uint32_t height, const void* mask, size_t mask_pitch, uint32_t object,
+                                  uint8_t* state, uint32_t gaussian_count, uint32_t and_mask, uint32_t xor_mask,
+                                  uint32_t* matched) {
+    if (!r || !r->impl) return GSM_ERR_INVALID_ARGUMENT;
+    return r->impl->selectPick((hipStream_t)stream, pick, pick_pitch, width, height, mask, mask_pitch, object, state,
+                               gaussian_count, and_mask, xor_mask, matched);
+}
+
 gsm_status gsm_global_pick_owner(gsm_renderer* r, const uint32_t* items, uint32_t n, uint32_t* object,
                                  uint32_t* gaussian) {
     if (!r || !r->impl || (n > 0 && (!items || !object || !gaussian))) return GSM_ERR_INVALID_ARGUMENT;

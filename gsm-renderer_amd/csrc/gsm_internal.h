@@ -345,6 +345,7 @@ struct DeviceArena {
     ComposeObjectArgs* composeArgs = nullptr;  // [min(ceil(maxG / 256), 65535)] per-object entries (render_composite; lazily)
     uint16_t* composeBlockObject = nullptr;    // [ceil(maxG / 256)] the entry of every projection block of a composite
     uint2* styleTable = nullptr;               // [kStyleEntries] packed styles (styled frames, select_mask; lazily)
+    uint32_t* selectBitmap = nullptr;          // [ceil(maxG / 32)] one bit per gaussian id (select_pick; lazily)
     uint16_t* expTable = nullptr;              // [65536]
     float2* sincosTable = nullptr;             // [kSincosEntries + 256]: sin/cos, then the byte table (det_byte_lut_entry)
 };
@@ -442,6 +443,13 @@ void launch_select_mask(bool halfInput, const void* world, const ProjectArgs& ar
                         size_t maskPitch, uint32_t width, uint32_t height, uint8_t* state, const uint2* styleTable,
                         uint32_t andMask, uint32_t xorMask, uint32_t* matched, const DeviceArena& A,
                         hipStream_t stream);
+// gsm_global_select_pick (k_select_pick_mark, k_select_pick_apply): the ids item - base < n of the
+// pick image's pixels under the mask (nullable: every pixel) are marked in `bitmap` (>= ceil(n / 32) words, cleared
+// here on the stream), then every marked id's state byte becomes (old & andMask) ^ xorMask, once; *matched
+// (nullable) receives their number.
+void launch_select_pick(const uint8_t* pick, size_t pickPitch, uint32_t width, uint32_t height, const uint8_t* mask,
+                        size_t maskPitch, uint32_t base, uint32_t n, uint32_t* bitmap, uint8_t* state,
+                        uint32_t andMask, uint32_t xorMask, uint32_t* matched, hipStream_t stream);
 // exclusive scan of the per-block sums, total + clamp into the header (GlobalShaders.metal:685-712)
 // project gaussians [0, a.count) of world/harm (already offset to the rank's range) and pack
 // the records of each slab's gaussians into `send` (slab-major, ascending id), counts to sendCounts

@@ -435,6 +435,43 @@ __global__ __launch_bounds__(kProjectBlock) void k_select_mask(
     }
 }
 
+// gsm_global_select_pick, pass 1: one thread per pixel of the pick image.  A pixel under the mask
+// (every pixel with mask NULL) whose item lies in [base, base + n) sets bit item - base of the bitmap: a vector
+// atomic OR, so an id that covers many pixels is marked once.  (item - base wraps for items below base and for
+// GSM_PICK_NONE: both land at or past n.)  The bitmap holds ceil(n / 32) words, cleared by the launcher.
+__global__ __launch_bounds__(256) void k_select_pick_mark(
+    const uint8_t* __restrict__ pick, size_t pickPitch, uint32_t width, uint32_t height,
+    const uint8_t* __restrict__ mask, size_t maskPitch, uint32_t base, uint32_t n, uint32_t* __restrict__ bitmap) {
+    const uint32_t x = blockIdx.x * 256u + threadIdx.x, y = blockIdx.y;
+    if (x >= width || y >= height) return;
+    if (mask && mask[(size_t)y * maskPitch + x] == 0) return;
+    const uint32_t id = *(const uint32_t*)(pick + (size_t)y * pickPitch + (size_t)x * 4) - base;
+    if (id < n) atomicOr(&bitmap[id >> 5], 1u << (id & 31u));
+}
+
+// pass 2: one thread per bitmap word.  Every marked id's state byte becomes (old & andMask) ^ xorMask, once;
+// *matched (nullable, zeroed by the launcher) receives the sum of the words' popcounts.
+__global__ __launch_bounds__(256) void k_select_pick_apply(
+    const uint32_t* __restrict__ bitmap, uint32_t words, uint32_t n, uint8_t* __restrict__ state, uint32_t andMask,
+    uint32_t xorMask, uint32_t* __restrict__ matched) {
+    __shared__ uint32_t lds[256 / 64];
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    uint32_t hit = 0;
+    if (i < words) {
+        uint32_t w = bitmap[i];
+        hit = (uint32_t)__builtin_popcount(w);
+        while (w) {
+            const uint32_t id = i * 32u + (uint32_t)__builtin_ctz(w);
+            w &= w - 1u;
+            if (id < n) state[id] = (uint8_t)(((state[id] & andMask) ^ xorMask) & 0xFFu);  // (marks lie below n)
+        }
+    }
+    if (matched) {  // (uniform)
+        const uint32_t s = block_reduce_add<256>(hit, lds);
+        if (threadIdx.x == 0 && s) atomicAdd(matched, s);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // 1b. multi-GPU partition: a rank projects its range of gaussians once,
 //     keeps every projected gaussian whose ellipse meets a tile of slab s, and sends its
@@ -1350,6 +1387,19 @@ void launch_select_mask(bool halfInput, const void* world, const ProjectArgs& a,
     else
         hipLaunchKernelGGL(k_select_mask<false>, dim3(blocks), dim3(kProjectBlock), 0, s, world, a, A.sincosTable, mask,
                            maskPitch, width, height, state, styleTable, andMask, xorMask, matched);
+}
+
+void launch_select_pick(const uint8_t* pick, size_t pickPitch, uint32_t width, uint32_t height, const uint8_t* mask,
+                        size_t maskPitch, uint32_t base, uint32_t n, uint32_t* bitmap, uint8_t* state,
+                        uint32_t andMask, uint32_t xorMask, uint32_t* matched, hipStream_t s) {
+    if (matched) hipMemsetAsync(matched, 0, sizeof(uint32_t), s);  // (overwritten, not added to)
+    if (n == 0) return;
+    const uint32_t words = (n + 31u) / 32u;
+    hipMemsetAsync(bitmap, 0, (size_t)words * sizeof(uint32_t), s);
+    hipLaunchKernelGGL(k_select_pick_mark, dim3((width + 255u) / 256u, height), dim3(256), 0, s, pick, pickPitch, width,
+                       height, mask, maskPitch, base, n, bitmap);
+    hipLaunchKernelGGL(k_select_pick_apply, dim3((words + 255u) / 256u), dim3(256), 0, s, bitmap, words, n, state,
+                       andMask, xorMask, matched);
 }
 
 // A (nullable): the arena whose blend units the launch also orders (a.schedUnits)

@@ -215,6 +215,43 @@ gsm_status GlobalRenderer::pickOwner(const uint32_t* items, uint32_t n, uint32_t
     return GSM_OK;
 }
 
+gsm_status GlobalRenderer::selectPick(hipStream_t s, const void* pick, size_t pickPitch, uint32_t width,
+                                      uint32_t height, const void* mask, size_t maskPitch, uint32_t object,
+                                      uint8_t* state, uint32_t gaussianCount, uint32_t andMask, uint32_t xorMask,
+                                      uint32_t* matched) {
+    if (!lastPick_) return GSM_ERR_RENDER_FAILED;  // (the handle's last enqueued frame wrote no pick target)
+    if (object >= lastPickObjects_) return GSM_ERR_INVALID_ARGUMENT;
+    if (gaussianCount > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
+    if (!frameSizeOk(width, height) || width != lastWidth_ || height != lastHeight_) return GSM_ERR_INVALID_DIMENSIONS;
+    if (!pick || (gaussianCount > 0 && !state)) return GSM_ERR_MISSING_REQUIRED_BUFFER;
+    if (pickPitch < (size_t)width * 4 || (pickPitch & 3u) || (((uintptr_t)pick) & 3u) || (mask && maskPitch < width) ||
+        (((uintptr_t)matched) & 3u))
+        return GSM_ERR_INVALID_BUFFER_SIZE;
+    // the object's items of the pick frame's layout: [256 * B_o, 256 * B_o + count_o); an object
+    // without gaussians has no entry and no item
+    uint32_t base = 0, count = 0;
+    if (!lastPickComposite_) {
+        count = lastCount_;
+    } else {
+        for (size_t e = 0; e < composeObject_.size(); ++e) {
+            if (composeObject_[e] != object) continue;
+            base = composeHost_[e].blockBase * (uint32_t)kProjectBlock;
+            count = composeHost_[e].count;
+        }
+    }
+    if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
+    if (!arena_.selectBitmap) {  // (the handle's first select_pick: one bit per gaussian the handle can hold)
+        const gsm_status st =
+            allocs_.alloc((void**)&arena_.selectBitmap, (((size_t)maxGaussians_ + 31) / 32) * sizeof(uint32_t));
+        if (st != GSM_OK) return st;
+    }
+    (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's)
+    launch_select_pick((const uint8_t*)pick, pickPitch, width, height, (const uint8_t*)mask, maskPitch, base,
+                       std::min(count, gaussianCount), arena_.selectBitmap, state, andMask, xorMask, matched, s);
+    if (hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;
+    return GSM_OK;
+}
+
 GlobalRenderer::FrameRequest GlobalRenderer::request(FrameKind kind, const ProjectArgs& args, uint32_t width,
                                                      uint32_t height, const FrameTargets& targets) const {
     FrameRequest rq;
@@ -858,6 +895,7 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const FrameRequest& rq, Front
     lastHeight_ = rq.height;
     lastPick_ = rq.pick != nullptr;
     lastPickComposite_ = rq.pick && comp;
+    lastPickObjects_ = !rq.pick ? 0u : comp ? comp->objects : 1u;
     // Blend schedule: the units ordered by the walk lengths the previous frame of the same
     // key measured (the image does not depend on the order, only the load balance does).
     // The ordering only needs those costs: one extra workgroup of the projection launch does it

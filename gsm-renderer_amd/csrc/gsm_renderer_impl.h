@@ -13,7 +13,8 @@
 
 namespace gsm {
 
-// What the entries of a family add to the plain frame, all nullable (pick and occluder never both):
+// What the entries of a family add to the plain frame, all nullable and independent (gsm_global_render_frame
+// passes any combination):
 // pick: a per-pixel pick target, the item of each pixel's heaviest contribution;
 // occluder: the frame cut, pixel by pixel, at the depth of an opaque surface, one float per pixel, read only
 // (DESIGN.md 21); style: the style of every gaussian's state byte applied in the projection --
@@ -59,6 +60,11 @@ class GlobalRenderer {
                           uint32_t width, uint32_t height, const void* mask, size_t maskPitch, uint8_t* state,
                           const gsm_global_style* styles, uint32_t styleCount, uint32_t andMask, uint32_t xorMask,
                           uint32_t* matched);
+    // state bytes of the gaussians of `object` that the last pick frame's image shows under the mask
+    // (gsm_global_select_pick)
+    gsm_status selectPick(hipStream_t stream, const void* pick, size_t pickPitch, uint32_t width, uint32_t height,
+                          const void* mask, size_t maskPitch, uint32_t object, uint8_t* state, uint32_t gaussianCount,
+                          uint32_t andMask, uint32_t xorMask, uint32_t* matched);
     // items of the last enqueued pick frame -> (object of the call, gaussian id within it); host only, no sync
     gsm_status pickOwner(const uint32_t* items, uint32_t n, uint32_t* object, uint32_t* gaussian) const;
 
@@ -218,6 +224,7 @@ class GlobalRenderer {
     std::vector<uint32_t> composeObject_;     // the call's object index of every entry of composeHost_
     bool lastPick_ = false;                   // the last enqueued frame was a pick frame (pickOwner)
     bool lastPickComposite_ = false;          // ... of a composite: its owners are composeHost_ / composeObject_
+    uint32_t lastPickObjects_ = 0;            // ... and the objects of that call (1 for a single frame)
 };
 
 }  // namespace gsm

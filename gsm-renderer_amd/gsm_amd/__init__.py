@@ -225,6 +225,20 @@ class _State(C.Structure):  # gsm_global_state
     _fields_ = [("state", C.c_void_p), ("default_state", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class _GlobalFrame(C.Structure):  # gsm_global_frame
+    _fields_ = [("objects", C.POINTER(_GlobalObject)), ("object_count", C.c_uint32), ("width", C.c_uint32),
+                ("height", C.c_uint32), ("color", C.c_void_p), ("color_pitch_bytes", C.c_size_t),
+                ("depth_r16f", C.c_void_p), ("depth_pitch_bytes", C.c_size_t),
+                ("pick_r32u", C.c_void_p), ("pick_pitch_bytes", C.c_size_t),
+                ("occluder_r32f", C.c_void_p), ("occluder_pitch_bytes", C.c_size_t),
+                ("states", C.POINTER(_State)), ("styles", C.POINTER(_Style)), ("style_count", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+GLOBAL_FRAME_BYTES = 112  # include/gsm_renderer.h: sizeof(gsm_global_frame), asserted there
+assert C.sizeof(_GlobalFrame) == GLOBAL_FRAME_BYTES
+
+
 class _Counters(C.Structure):
     _fields_ = [("total_assignments", C.c_uint32), ("max_capacity", C.c_uint32),
                 ("padded_count", C.c_uint32), ("overflow", C.c_uint32), ("tiles_x", C.c_uint32),
@@ -292,6 +306,10 @@ _SIGNATURES = {
     "gsm_global_select_mask": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera), C.c_uint32,
                                 C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(_Style), C.c_uint32,
                                 C.c_uint32, C.c_uint32, C.c_void_p], C.c_int),
+    "gsm_global_render_frame": ([C.c_void_p, C.c_void_p, C.POINTER(_GlobalFrame)], C.c_int),
+    "gsm_global_select_pick": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
+                                C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p],
+                               C.c_int),
     "gsm_global_render_stereo": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera),
                                   C.POINTER(_Camera), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                   C.c_void_p, C.c_size_t], C.c_int),
@@ -717,6 +735,56 @@ class GlobalRenderer(_Renderer):
                                            sn if style_count is None else int(style_count),
                                            int(and_mask) & 0xFFFFFFFF, int(xor_mask) & 0xFFFFFFFF, _ptr(matched))
         _check(st, "gsm_global_select_mask")
+
+    def render_frame(self, color_texture, depth_texture, objects, width: int, height: int, pick=None, occluder=None,
+                     states=None, styles=None, stream=None, color_pitch: Optional[int] = None,
+                     depth_pitch: Optional[int] = None, pick_pitch: Optional[int] = None,
+                     occluder_pitch: Optional[int] = None, style_count: Optional[int] = None, flags: int = 0,
+                     null_frame: bool = False):
+        """gsm_global_render_frame: one descriptor for every Single and Compose frame and every combination of a
+        pick target, an occluder and styles.  objects: a SceneObject list, or one (GaussianInput, CameraParams)
+        pair as a single object; None passes a NULL array with object_count 1.  pick / occluder: as for
+        `render_pick` / `render_occluded`, None leaves the option out.  states: one entry per object (a uint8 CUDA
+        tensor or an int), or a single such value for a single object; styles: a Style list.  null_frame passes a
+        NULL descriptor (the C entry's error path)."""
+        single = isinstance(objects, tuple) and len(objects) == 2 and isinstance(objects[0], GaussianInput)
+        if single:
+            objects = [SceneObject(objects[0], objects[1])]
+            if states is not None and not isinstance(states, (list, tuple)):
+                states = [states]
+        arr, n = _object_array(objects)
+        sarr, sn = _style_array(styles)
+        starr = None
+        if states is not None:
+            starr = (_State * max(len(states), 1))(*[_state_struct(s) for s in states])
+        f = _GlobalFrame()
+        f.objects = arr if arr is not None else C.POINTER(_GlobalObject)()
+        f.object_count, f.width, f.height = n, int(width), int(height)
+        f.color, f.depth_r16f = _ptr(color_texture), _ptr(depth_texture)
+        f.color_pitch_bytes = color_pitch if color_pitch is not None else int(width) * self._bpp
+        f.depth_pitch_bytes = depth_pitch if depth_pitch is not None else int(width) * 2
+        f.pick_r32u, f.occluder_r32f = _ptr(pick), _ptr(occluder)
+        f.pick_pitch_bytes = pick_pitch if pick_pitch is not None else int(width) * 4
+        f.occluder_pitch_bytes = occluder_pitch if occluder_pitch is not None else int(width) * 4
+        f.states = starr if starr is not None else C.POINTER(_State)()
+        f.styles = sarr if sarr is not None else C.POINTER(_Style)()
+        f.style_count = sn if style_count is None else int(style_count)
+        f.flags = int(flags)
+        st = _lib().gsm_global_render_frame(self._h, _stream_handle(stream), None if null_frame else C.byref(f))
+        _check(st, "gsm_global_render_frame")
+
+    def select_pick(self, pick, width: int, height: int, object: int, state, gaussian_count: int, and_mask: int,
+                    xor_mask: int, mask=None, matched=None, stream=None, pick_pitch: Optional[int] = None,
+                    mask_pitch: Optional[int] = None):
+        """gsm_global_select_pick: the state byte of every gaussian of `object` that the last pick frame's image
+        `pick` shows on a nonzero byte of `mask` (None: every pixel) becomes (old & and_mask) ^ xor_mask, once per
+        gaussian.  matched: an int32 / uint32 CUDA tensor of one element that receives the count."""
+        pp = pick_pitch if pick_pitch is not None else int(width) * 4
+        mp = mask_pitch if mask_pitch is not None else int(width)
+        st = _lib().gsm_global_select_pick(self._h, _stream_handle(stream), _ptr(pick), pp, int(width), int(height),
+                                           _ptr(mask), mp, int(object), _ptr(state), int(gaussian_count),
+                                           int(and_mask) & 0xFFFFFFFF, int(xor_mask) & 0xFFFFFFFF, _ptr(matched))
+        _check(st, "gsm_global_select_pick")
 
     def pick_owner(self, items):
         """gsm_global_pick_owner: items of the last enqueued pick frame (any integer array, host) ->

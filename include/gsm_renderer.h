@@ -343,8 +343,8 @@ gsm_status gsm_global_pick_owner(gsm_renderer *renderer, const uint32_t *items, 
  *   GSM_ERR_UNSUPPORTED              (both entries, after every other check) the handle is restricted to tile
  *                                    rows (gsm_global_set_tile_rows).
  * Enqueue-only and capturable like the plain entries; nothing is allocated per frame.  gsm_global_render_views,
- * gsm_global_render_batch, the pick entries, the DepthFirst and Local renderers and the multi-GPU frame have no
- * occluded entry. */
+ * gsm_global_render_batch, the DepthFirst and Local renderers and the multi-GPU frame have no occluded entry;
+ * gsm_global_render_frame (below) combines an occluder with a pick target and with styles. */
 gsm_status gsm_global_render_occluded(gsm_renderer *renderer, void *stream, const gsm_gaussian_input *input,
                                       const gsm_camera_params *camera, uint32_t width, uint32_t height,
                                       void *color, size_t color_pitch_bytes, void *depth_r16f,
@@ -385,8 +385,9 @@ gsm_status gsm_global_render_composite_occluded(gsm_renderer *renderer, void *st
  *   GSM_ERR_UNSUPPORTED       the handle is restricted to tile rows (gsm_global_set_tile_rows).
  * Enqueue-only and capturable; a captured frame replays the table and the state pointers it was captured with.
  * Nothing is allocated per frame (the handle's first styled frame allocates the 2 KiB table).
- * gsm_global_render_views, gsm_global_render_batch, the occluded entries, the DepthFirst and Local renderers and
- * the multi-GPU frame have no styled entry; a style changes neither position nor scale. */
+ * gsm_global_render_views, gsm_global_render_batch, the DepthFirst and Local renderers and the multi-GPU frame
+ * have no styled entry; gsm_global_render_frame (below) combines styles with an occluder.  A style changes neither
+ * position nor scale. */
 typedef struct {
     uint8_t tint_r, tint_g, tint_b; /* in the u8 colour space of GaussianRenderData: after the SH evaluation and,
                                        for gaussian_color_space SRGB, after the decode to linear */
@@ -447,6 +448,88 @@ gsm_status gsm_global_select_mask(gsm_renderer *renderer, void *stream, const gs
                                   const gsm_camera_params *camera, uint32_t width, uint32_t height,
                                   const void *mask_u8, size_t mask_pitch_bytes, uint8_t *state,
                                   const gsm_global_style *styles, uint32_t style_count,
+                                  uint32_t and_mask, uint32_t xor_mask, uint32_t *matched);
+
+/* One descriptor for every Single and Compose frame (no reference analogue): the plain, pick,
+ * occluded and styled entries above and every combination of their options, which those entries do not offer --
+ * an occluder with a pick target, an occluder with styles, all three.  `frame` is host memory, consumed before the
+ * call returns, as are the arrays it points to (objects, states, styles); the targets, the occluder and the state
+ * bytes are device memory.
+ *
+ * Semantics, composed from the rules above: styles apply in the projection (the styled entries' rule); the list is
+ * the composite's (one object: gsm_global_render's); with an occluder the walk is the occluded one; the pick is the
+ * pick entries' rule applied to the walk that runs.  Under an occluder a closed pixel's alpha is +0, so its weight
+ * alpha * T is 0 and never wins: the pick of a pixel is the heaviest contribution in front of the surface, and a
+ * pixel closed before its first entry holds GSM_PICK_NONE.  No arithmetic is added to the numeric contract.
+ *
+ * Identities: with object_count == 1 the bytes are those of the single-scene entries; with an option NULL the bytes
+ * are those of the entry without it (colour, depth and pick equal gsm_global_render, _pick, _occluded, _styled and
+ * their composite forms for the same arguments); an occluder of all +inf gives the pick frame's three targets; an
+ * identity style table gives the unstyled frame.  gsm_global_pick_owner and gsm_global_select_pick work after any
+ * frame of this entry that had a pick target.
+ *
+ * Checked before anything is enqueued; the first failing check in this order decides:
+ *   GSM_ERR_INVALID_ARGUMENT         frame NULL or flags != 0 (before everything else);
+ *   then the checks of gsm_global_render (object_count == 1 with objects non-NULL) or gsm_global_render_composite
+ *   (every other object_count, 0 included), in that entry's order, each optional buffer joining its rows --
+ *   GSM_ERR_INVALID_GAUSSIAN_COUNT   as that entry;
+ *   GSM_ERR_INVALID_DIMENSIONS       as that entry;
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  as that entry (a NULL pick, occluder or depth pointer is "not given", never
+ *                                    missing);
+ *   GSM_ERR_INVALID_BUFFER_SIZE      also: pick_pitch_bytes < 4 * width or occluder_pitch_bytes < 4 * width, or
+ *                                    either pointer or pitch not 4-byte aligned;
+ *   GSM_ERR_INVALID_ARGUMENT         objects that differ in sh_components; then the styled row: styles without
+ *                                    states, states without styles, style_count 0 or above 256, or a default_state
+ *                                    above 255 (both NULL: no styles, style_count ignored);
+ *   GSM_ERR_UNSUPPORTED              last: the handle is restricted to tile rows (gsm_global_set_tile_rows) and
+ *                                    the frame has a pick target, an occluder or styles, or more than one object.
+ * Enqueue-only and capturable; nothing is allocated per frame beyond what the entries above allocate once.
+ * Out of scope: gsm_global_render_views, gsm_global_render_batch, gsm_global_render_records, the DepthFirst and
+ * Local renderers and the multi-GPU frame take no pick target, occluder or styles. */
+typedef struct {
+    const gsm_global_object *objects;  uint32_t object_count;   /* 1 object = a single frame */
+    uint32_t width, height;
+    void *color;  size_t color_pitch_bytes;
+    void *depth_r16f;  size_t depth_pitch_bytes;                /* nullable */
+    void *pick_r32u;  size_t pick_pitch_bytes;                  /* nullable */
+    const void *occluder_r32f;  size_t occluder_pitch_bytes;    /* nullable */
+    const gsm_global_state *states;                             /* [object_count], nullable with styles */
+    const gsm_global_style *styles;  uint32_t style_count;      /* nullable */
+    uint32_t flags;                                             /* must be 0 */
+} gsm_global_frame;
+#ifdef __cplusplus
+static_assert(sizeof(gsm_global_frame) == 112, "gsm_global_frame is 112 bytes");
+#else
+_Static_assert(sizeof(gsm_global_frame) == 112, "gsm_global_frame is 112 bytes");
+#endif
+gsm_status gsm_global_render_frame(gsm_renderer *renderer, void *stream, const gsm_global_frame *frame);
+
+/* Select what is visible: the state bytes of the gaussians of one object that a pick image shows
+ * under a mask.  The handle's last enqueued frame must be a pick frame (any entry with a pick target) of
+ * width x height; pick_r32u is that frame's pick target or a copy of it.  With the composite layout above -- object
+ * o's items start at 256 * B_o and number count_o; a single frame is object 0 with B_0 = 0 -- let
+ *   S = { item - 256 * B_object : pixel (x, y) of width x height has a nonzero mask byte (or mask_u8 is NULL), and
+ *         item = pick[y][x] lies in [256 * B_object, 256 * B_object + min(count_object, gaussian_count)) }.
+ * Every id in S gets state[id] = ((old & and_mask) ^ xor_mask) & 0xFF exactly once, however many pixels it covers
+ * (a toggle does not cancel itself); every other byte of `state`, and every byte at or past gaussian_count, keeps
+ * its value.  `matched` (device, nullable) receives |S|: overwritten, not added to.  After an occluded pick frame S
+ * holds only splats in front of the surface: "select the visible surface".  The layout is host state of the last
+ * pick frame, as for gsm_global_pick_owner.  Enqueue-only and capturable; the handle's first call allocates a
+ * bitmap of max_gaussians / 8 bytes, nothing after it.
+ *
+ * Checks, in this order:
+ *   GSM_ERR_RENDER_FAILED            the handle's last enqueued frame was not a pick frame;
+ *   GSM_ERR_INVALID_ARGUMENT         object at or past that frame's object count;
+ *   GSM_ERR_INVALID_GAUSSIAN_COUNT   gaussian_count > max_gaussians;
+ *   GSM_ERR_INVALID_DIMENSIONS       width or height zero, above max_width / max_height, or not the pick frame's;
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  pick_r32u NULL, or state NULL with a count > 0;
+ *   GSM_ERR_INVALID_BUFFER_SIZE      pick_pitch_bytes < 4 * width, the pick pointer or pitch not 4-byte aligned,
+ *                                    mask_pitch_bytes < width (mask_u8 non-NULL), or matched not 4-byte aligned.
+ * A count of 0 is a no-op that writes *matched = 0. */
+gsm_status gsm_global_select_pick(gsm_renderer *renderer, void *stream,
+                                  const void *pick_r32u, size_t pick_pitch_bytes, uint32_t width, uint32_t height,
+                                  const void *mask_u8, size_t mask_pitch_bytes,
+                                  uint32_t object, uint8_t *state, uint32_t gaussian_count,
                                   uint32_t and_mask, uint32_t xor_mask, uint32_t *matched);
 
 /* GlobalRenderer.renderStereo (GlobalRenderer.swift:240-255) calls fatalError for
