@@ -159,6 +159,10 @@ __device__ __forceinline__ uint32_t occ_open_mask(uint32_t bd, uint32_t keys) {
 #define GSM_BLEND_VIEWS 0
 #include "gsm_blend_px_body.h"
 #undef GSM_BLEND_VIEWS
+// a batch of views with per-view options (gsm_global_render_frames): k_blend_px_batch_occ_pick
+#define GSM_BLEND_VIEWS 2
+#include "gsm_blend_px_body.h"
+#undef GSM_BLEND_VIEWS
 #undef GSM_BLEND_OCCLUDE
 #undef GSM_BLEND_PICK
 
@@ -238,9 +242,25 @@ int launch_blend(const FrameGeometry& g, const DeviceArena& A, const FrameTarget
     // longest units and latency (config 2: 121 -> 129-147 us at every split tried).
     // A pick frame: the single frame's walk that also writes the pick target -- quadrant or
     // half-tile units by the rule above, no compaction, no pair walk.  (Whole frames of one GPU only: the host
-    // refuses tile rows, and no batch or gathered frame has a pick entry.)
+    // refuses tile rows, no gathered frame has a pick entry, and a batch with options takes the kernel below.)
     // A frame with a pick target and an occluder (gsm_global_render_frame): the occluded walk over the
     // whole sorted runs that also tracks the pick -- the units and rules of both, the alignment flags of both.
+    // A batch in which some view has a pick target or an occluder (gsm_global_render_frames): one
+    // union kernel, the occluded pick walk with every option looked up per view.  A view without an occluder
+    // walks with a limit of +inf and a view without a pick target stores none, so each view's bytes are those of
+    // its own entry; a pick-only batch pays the walk over the whole sorted runs for six instances instead of
+    // eighteen.  The alignment bits 13 and 14 are per view (BatchExtras::align), as bits 0 and 11 are.
+    if (g.kind == FrameKind::Batch && o.batchExtras) {
+        if (!o.sortedVals) return 0;  // (the host keeps them for every such batch)
+        dispatch_blend(waves, P, numTiles, numCUs, [&](auto NTH, auto PP, uint32_t grid) {
+            hipLaunchKernelGGL((k_blend_px_batch_occ_pick<decltype(NTH)::value, decltype(PP)::value, false>),
+                               dim3(grid), dim3(decltype(NTH)::value), 0, s, A.tileStart, A.rec, A.expTable,
+                               A.tileQueue, numTiles, (const BatchViewArgs*)g.batchArgs, g.batchTileView,
+                               o.batchExtras, flags & ~(1 | 2048), order, A.unitCost, A.blendTrace, A.halfVals[0],
+                               A.halfVals[1], A.halfCount, g.tileCount, A.costMax, o.sortedVals);
+        });
+        return kernel;
+    }
     if (o.pick && o.occluder) {
         if (!o.sortedVals) return 0;  // (the host passes them with every occluder)
         uint8_t* const pick = (uint8_t*)o.pick->pixels;

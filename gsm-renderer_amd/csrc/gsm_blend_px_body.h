@@ -35,7 +35,33 @@
 #define GSM_PICK_PARAMS , uint32_t pk0, uint32_t pk1  // the pixel pair's picks travel with its colour
 #define GSM_PICK_ARGS(q) , pk[q][0], pk[q][1]
 #endif
-#if GSM_BLEND_PICK && GSM_BLEND_OCCLUDE
+#if GSM_BLEND_PICK && GSM_BLEND_OCCLUDE && GSM_BLEND_VIEWS == 2
+// A seventh time with all three (GSM_BLEND_VIEWS 2, GSM_BLEND_OCCLUDE 1, GSM_BLEND_PICK 1):
+// k_blend_px_batch_occ_pick, the occluded pick walk over a batch of different views whose frames carry their own
+// nullable pick target and occluder (gsm_global_render_frames).  A unit looks its view up as
+// k_blend_px_batch does and reads that view's 64-B options line next to its target line (scalar loads): a view
+// without an occluder walks with a limit of +inf everywhere (DESIGN.md 21's identity: the plain bytes), a view
+// without a pick target stores no pick, and the pick store writes item - 256 * blockBase, the view's gaussian id.
+template <int NT, int P, bool COMPACT = false>
+__global__ __launch_bounds__(NT) void k_blend_px_batch_occ_pick(
+    const uint32_t* __restrict__ tileStart, const BlendRecord* __restrict__ rec,
+    const uint16_t* __restrict__ expTable, uint32_t* __restrict__ queue, uint32_t numTiles,
+    const BatchViewArgs* __restrict__ views, const uint16_t* __restrict__ tileView,
+    const BatchExtras* __restrict__ extras, int flags, const uint32_t* __restrict__ order,
+    uint16_t* __restrict__ unitCost, unsigned long long* __restrict__ trace, const uint32_t* __restrict__ half0,
+    const uint32_t* __restrict__ half1, const uint32_t* __restrict__ halfCount, uint32_t tileCount,
+    uint32_t* __restrict__ costMax, const uint32_t* __restrict__ sortedVals) {
+    static_assert(!COMPACT, "the occluded pick walk keeps its unit layout");
+    constexpr uint32_t tileBegin = 0;  // whole frames on one GPU: no tile rows, no gather
+    const MgArrive arrive{};
+    // the current unit's view: its targets, pitches and size, its options (pickOut / occIn null: not given), the
+    // first item of its scene, and which wide accesses are aligned in it (flags bits 0, 13, 14)
+    uint8_t *color = nullptr, *depth = nullptr, *pickOut = nullptr;
+    const uint8_t* occIn = nullptr;
+    size_t colorPitch = 0, depthPitch = 0, pickPitch = 0, occPitch = 0;
+    uint32_t W = 0, H = 0, itemBase = 0;
+    const int flags0 = flags & ~(1 | 8192 | 16384);
+#elif GSM_BLEND_PICK && GSM_BLEND_OCCLUDE
 template <int NT, int P, bool COMPACT = false>
 __global__ __launch_bounds__(NT) void k_blend_px_occ_pick(
     const uint32_t* __restrict__ tileStart, const BlendRecord* __restrict__ rec,
@@ -125,7 +151,11 @@ __global__ __launch_bounds__(NT) void k_blend_px(
     // read.  One 8-byte load where the occluder is aligned for it (flags bit 14; px is even).
     auto load_limits = [&](uint32_t px, uint32_t py) -> uint32_t {
         float z0 = __builtin_inff(), z1 = __builtin_inff();
+#if GSM_BLEND_VIEWS == 2
+        if (py < H && occIn) {  // (a view without an occluder: +inf everywhere)
+#else
         if (py < H) {
+#endif
             const uint8_t* zrow = occIn + (size_t)py * occPitch + (size_t)px * 4;
             if ((flags & 16384) && px + 1 < W) {
                 const float2 z = *(const float2*)zrow;
@@ -237,6 +267,12 @@ __global__ __launch_bounds__(NT) void k_blend_px(
         }
 #if GSM_BLEND_PICK
         // the pick pair: one 8-byte store where the target is aligned for it (flags bit 13; px is even)
+#if GSM_BLEND_VIEWS == 2
+        if (!pickOut) return;  // (this view has no pick target)
+        // the walk tracked batch items: the view's gaussian id is the item less its scene's first (NONE stays)
+        pk0 = pk0 == GSM_PICK_NONE ? pk0 : pk0 - itemBase;
+        pk1 = pk1 == GSM_PICK_NONE ? pk1 : pk1 - itemBase;
+#endif
         uint8_t* prow = pickOut + (size_t)py * pickPitch + (size_t)px * 4;
         if ((flags & 8192) && px + 1 < W) {
             *(uint2*)prow = make_uint2(pk0, pk1);
@@ -306,6 +342,17 @@ __global__ __launch_bounds__(NT) void k_blend_px(
         W = VT.width;
         H = VT.height;
         flags = flags0 | (int)(VT.vec & 1u);
+#if GSM_BLEND_PICK && GSM_BLEND_OCCLUDE
+        {  // the view's options line (the same uniform index: scalar loads)
+            const BatchExtras& VE = extras[__builtin_amdgcn_readfirstlane((uint32_t)tileView[tile])];
+            pickOut = VE.pick;
+            pickPitch = VE.pickPitch;
+            occIn = VE.occluder;
+            occPitch = VE.occluderPitch;
+            itemBase = VE.itemBase;
+            flags |= (int)(VE.align & (8192u | 16384u));
+        }
+#endif
         const uint32_t tilesX = VT.tilesX, ltile = tile - VT.tileBase;
         const uint32_t tileX = ltile % tilesX, tileY = ltile / tilesX;
 #elif GSM_BLEND_VIEWS

@@ -216,6 +216,21 @@ gsm_status gsm_global_select_pick(gsm_renderer* r, void* stream, const void* pic
                                gaussian_count, and_mask, xor_mask, matched);
 }
 
+gsm_status gsm_global_render_frames(gsm_renderer* r, void* stream, const gsm_global_frame* frames,
+                                    uint32_t frame_count) {
+    if (!r || !r->impl) return GSM_ERR_INVALID_ARGUMENT;
+    return r->impl->renderFrames((hipStream_t)stream, frames, frame_count);
+}
+
+gsm_status gsm_global_select_pick_ids(gsm_renderer* r, void* stream, const void* pick, size_t pick_pitch,
+                                      uint32_t width, uint32_t height, const void* mask, size_t mask_pitch,
+                                      uint8_t* state, uint32_t gaussian_count, uint32_t and_mask, uint32_t xor_mask,
+                                      uint32_t* matched) {
+    if (!r || !r->impl) return GSM_ERR_INVALID_ARGUMENT;
+    return r->impl->selectPickIds((hipStream_t)stream, pick, pick_pitch, width, height, mask, mask_pitch, state,
+                                  gaussian_count, and_mask, xor_mask, matched);
+}
+
 gsm_status gsm_global_pick_owner(gsm_renderer* r, const uint32_t* items, uint32_t n, uint32_t* object,
                                  uint32_t* gaussian) {
     if (!r || !r->impl || (n > 0 && (!items || !object || !gaussian))) return GSM_ERR_INVALID_ARGUMENT;

@@ -86,6 +86,29 @@ constexpr uint32_t kBatchChunk = 10;
 struct BatchChunk {
     BatchViewArgs v[kBatchChunk];
 };
+// What a frame of gsm_global_render_frames adds to its view: one 64-B line per view in a device
+// array parallel to the BatchViewArgs array, read by the kernels of a batch with options only -- the plain batch
+// kernels never see it.  A projection block reads the state terms, a blend unit the pick and occluder terms, both
+// with the view index they already hold (uniform: scalar loads).
+struct BatchExtras {
+    uint8_t* pick;            // null: this view has no pick target
+    size_t pickPitch;
+    const uint8_t* occluder;  // null: this view has no occluder (its walk sees a limit of +inf everywhere)
+    size_t occluderPitch;
+    const uint8_t* state;     // a styled view's state bytes, or null and defaultState for all its gaussians
+    uint32_t defaultState;
+    uint32_t styled;          // nonzero: the view's projection applies the batch's style table
+    uint32_t align;           // the blend's flags bit 13 (8192): 8-byte pick stores, bit 14 (16384): 8-byte occluder
+                              // loads are aligned in this view's own pointer and pitch
+    uint32_t itemBase;        // 256 * blockBase: what the pick store subtracts from an item
+    uint32_t pad[2];
+};
+static_assert(sizeof(BatchExtras) == 64, "BatchExtras: one 64-B line");
+// the array is filled by kernel arguments, kExtrasChunk entries per launch (a kernel argument block holds 4 KiB)
+constexpr uint32_t kExtrasChunk = 32;
+struct ExtrasChunk {
+    BatchExtras v[kExtrasChunk];
+};
 struct BatchFrame {
     uint32_t views = 0;
     uint32_t blocks = 0;  // projection / scatter blocks of the batch: sum of ceil(count_v / 256)
@@ -93,6 +116,7 @@ struct BatchFrame {
     const BatchViewArgs* args = nullptr;   // device, [views]
     const uint16_t* blockView = nullptr;   // device, [blocks]: the view of every block
     const uint16_t* tileView = nullptr;    // device, [tiles]: the view of every tile
+    const BatchExtras* extras = nullptr;   // device, [views]: a batch with options (render_frames), else null
 };
 
 // Several posed objects in one frame (gsm_global_render_composite): what differs per object --
@@ -342,6 +366,7 @@ struct DeviceArena {
     BatchViewArgs* batchArgs = nullptr;        // [maxBatchViews] per-view entries (render_batch; lazily)
     uint16_t* batchBlockView = nullptr;        // [ceil(maxG / 256)] the view of every projection block of a batch
     uint16_t* batchTileView = nullptr;         // [tileCount] the view of every tile of a batch
+    BatchExtras* batchExtras = nullptr;        // [maxBatchViews] per-view options (render_frames; lazily)
     ComposeObjectArgs* composeArgs = nullptr;  // [min(ceil(maxG / 256), 65535)] per-object entries (render_composite; lazily)
     uint16_t* composeBlockObject = nullptr;    // [ceil(maxG / 256)] the entry of every projection block of a composite
     uint2* styleTable = nullptr;               // [kStyleEntries] packed styles (styled frames, select_mask; lazily)
@@ -419,6 +444,13 @@ void launch_project_batch(bool halfInput, uint32_t shDegree, const ProjectArgs& 
                           const DeviceArena& A, hipStream_t stream);
 void launch_fill_batch(const BatchChunk& chunk, uint32_t first, uint32_t n, BatchViewArgs* dst, uint16_t* blockView,
                        uint32_t maxBlocks, uint16_t* tileView, uint32_t maxTiles, hipStream_t stream);
+// a batch with options (gsm_global_render_frames): launch_fill_batch_extras writes entries [first,
+// first + n) of the per-view options array from `chunk` (n <= kExtrasChunk); launch_project_batch_styled is
+// k_project_batch with the style step of the views whose line says so (bf.extras, styleTable: both required)
+void launch_fill_batch_extras(const ExtrasChunk& chunk, uint32_t first, uint32_t n, BatchExtras* dst,
+                              hipStream_t stream);
+void launch_project_batch_styled(bool halfInput, uint32_t shDegree, const ProjectArgs& args, const BatchFrame& bf,
+                                 const uint2* styleTable, const DeviceArena& A, hipStream_t stream);
 // several posed objects on the frame's own tile grid (k_project_compose): every block's scene,
 // count and camera terms come from its object's entry; `args` holds the frame's (the grid, the rows, the
 // thresholds, the capacity, the schedule).  launch_fill_compose writes entries [first, first + n) of the device
@@ -506,6 +538,9 @@ struct BlendOptions {
     // DESIGN.md 21); sortedVals: the frame's sorted values, which that walk reads in place of the half-tile lists
     const OccluderSource* occluder = nullptr;
     const uint32_t* sortedVals = nullptr;
+    // nullable: a Batch in which some view has a pick target or an occluder (gsm_global_render_frames, DESIGN.md
+    // 25) -- the per-view options array; the walk is k_blend_px_batch_occ_pick over sortedVals
+    const BatchExtras* batchExtras = nullptr;
     int numCUs = 0;
 };
 int launch_blend(const FrameGeometry& geo, const DeviceArena& A, const FrameTargets& targets,

@@ -342,6 +342,10 @@ __device__ __forceinline__ float2 band_of(const BlendRecordA& ra, short4 r, cons
 #define GSM_VIEWS 3
 #include "gsm_project_body.h"
 #undef GSM_VIEWS
+// and the batch's, for a batch with styled views (gsm_global_render_frames)
+#define GSM_VIEWS 2
+#include "gsm_project_body.h"
+#undef GSM_VIEWS
 #undef GSM_STYLED
 
 // entries [first, first + n) of the per-view array from a kernel argument (plain vector stores): the host's
@@ -374,6 +378,16 @@ __global__ __launch_bounds__(256) void k_fill_batch(BatchChunk chunk, uint32_t f
         const uint32_t t1 = min(V.tg.tileBase + V.tg.tilesX * V.tg.tilesY, maxTiles);
         for (uint32_t i = t0 + threadIdx.x; i < t1; i += 256u) tileView[i] = view;
     }
+}
+
+// The per-view options of a batch (gsm_global_render_frames), the same way: entries [first, first +
+// n) of the array parallel to the per-view entries, one 64-B line each.  No table: the kernels index it by the view
+// they already looked up.
+__global__ __launch_bounds__(256) void k_fill_batch_extras(ExtrasChunk chunk, uint32_t first, uint32_t n,
+                                                           BatchExtras* __restrict__ dst) {
+    constexpr uint32_t kWords = sizeof(BatchExtras) / 4u;
+    const uint32_t* src = (const uint32_t*)&chunk;
+    for (uint32_t i = threadIdx.x; i < n * kWords; i += 256u) ((uint32_t*)(dst + first))[i] = src[i];
 }
 
 // The same for a composite (gsm_global_render_composite): entries [first, first + n) of the
@@ -1329,6 +1343,23 @@ void launch_fill_batch(const BatchChunk& chunk, uint32_t first, uint32_t n, Batc
     if (n == 0) return;
     hipLaunchKernelGGL(k_fill_batch, dim3(1), dim3(256), 0, s, chunk, first, n > kBatchChunk ? kBatchChunk : n, dst,
                        blockView, maxBlocks, tileView, maxTiles);
+}
+
+void launch_fill_batch_extras(const ExtrasChunk& chunk, uint32_t first, uint32_t n, BatchExtras* dst, hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_fill_batch_extras, dim3(1), dim3(256), 0, s, chunk, first, n > kExtrasChunk ? kExtrasChunk : n,
+                       dst);
+}
+
+void launch_project_batch_styled(bool halfInput, uint32_t deg, const ProjectArgs& a, const BatchFrame& bf,
+                                 const uint2* styleTable, const DeviceArena& A, hipStream_t s) {
+    if (bf.blocks == 0 && a.schedUnits == 0) return;  // (an empty batch still orders its blend units)
+    dispatch_sh(halfInput, deg, [&](auto H, auto D) {
+        hipLaunchKernelGGL((k_project_batch_styled<decltype(H)::value, decltype(D)::value>),
+                           project_grid(bf.blocks, a), dim3(kProjectBlock), 0, s, a, bf.args, bf.blockView, bf.extras,
+                           A.renderData, A.bounds, A.rec, A.tileCounts, A.tileMasks, A.blockSums, A.sincosTable,
+                           A.unitCost, A.unitOrder, A.costMax, styleTable);
+    });
 }
 
 void launch_project_compose(bool halfInput, uint32_t deg, const ProjectArgs& a, const ComposeFrame& cf,

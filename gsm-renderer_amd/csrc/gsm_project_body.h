@@ -3,10 +3,27 @@
 // gaussian id), as the projection of a batch of views of one scene (GSM_VIEWS 1: k_project_views), as the
 // projection of a batch of views of different scenes and sizes (GSM_VIEWS 2: k_project_batch) and as the
 // projection of several posed objects into one frame (GSM_VIEWS 3: k_project_compose).  No include guard.
-// With GSM_STYLED defined (GSM_VIEWS 0 and 3 only) the same text gives k_project_styled and
-// k_project_compose_styled: one more argument, the style table -- and for the single frame the
-// scene's state bytes and default -- and project_gaussian's kProjStyled mode; nothing else differs.
-#if defined(GSM_STYLED) && GSM_VIEWS == 3
+// With GSM_STYLED defined (GSM_VIEWS 0, 2 and 3 only) the same text gives k_project_styled, k_project_batch_styled
+//  and k_project_compose_styled: one more argument, the style table -- for the single
+// frame the scene's state bytes and default too, for a batch the per-view options array that holds them -- and
+// project_gaussian's kProjStyled mode; nothing else differs.
+#if defined(GSM_STYLED) && GSM_VIEWS == 2
+// The styled projection of a batch with options (gsm_global_render_frames): k_project_batch with the
+// style step.  A block reads its view's state pointer, default state and styled flag from the view's options line
+// (BatchExtras; the block's view index is uniform: scalar loads).  A view that is not styled takes the identity
+// style without a table load -- c * 255 / 255 and o * 255 / 255 in the style rule's integers: the plain bytes.
+template <bool HALF, int DEG>
+__global__ __launch_bounds__(kProjectBlock) void k_project_batch_styled(
+    ProjectArgs P, const BatchViewArgs* __restrict__ views, const uint16_t* __restrict__ blockView,
+    const BatchExtras* __restrict__ extras, GaussianRenderData* __restrict__ outRD, short4* __restrict__ outBounds,
+    BlendRecord* __restrict__ outRec, uint32_t* __restrict__ counts, uint32_t* __restrict__ masks,
+    uint32_t* __restrict__ blockSums, const float2* __restrict__ sincos, const uint16_t* __restrict__ unitCost,
+    uint32_t* __restrict__ unitOrder, uint32_t* __restrict__ costMax, const uint2* __restrict__ styleTable) {
+    const void* __restrict__ world = nullptr;  // the block's scene: its view's (below)
+    const void* __restrict__ harm = nullptr;
+    const uint8_t* __restrict__ stateBytes = nullptr;  // the block's state bytes and default: its view's
+    uint32_t defaultState = 0, styledView = 0;
+#elif defined(GSM_STYLED) && GSM_VIEWS == 3
 template <bool HALF, int DEG>
 __global__ __launch_bounds__(kProjectBlock) void k_project_compose_styled(
     ProjectArgs P, const ComposeObjectArgs* __restrict__ objects, const uint16_t* __restrict__ blockObject,
@@ -123,6 +140,14 @@ __global__ __launch_bounds__(kProjectBlock) void k_project(
         gblk = blk - V.blockBase;
         world = V.world;
         harm = V.harm;
+#ifdef GSM_STYLED
+        {
+            const BatchExtras& E = extras[__builtin_amdgcn_readfirstlane((uint32_t)blockView[blk])];
+            stateBytes = E.state;
+            defaultState = E.defaultState;
+            styledView = E.styled;
+        }
+#endif
         P.cam = V.cam;
         P.bin = V.bin;
         P.rowBegin = 0;
@@ -175,7 +200,12 @@ __global__ __launch_bounds__(kProjectBlock) void k_project(
     uint32_t stateByte = defaultState;
     if (stateBytes && gblk * kProjectBlock + threadIdx.x < P.count)
         stateByte = stateBytes[gblk * kProjectBlock + threadIdx.x];
+#if GSM_VIEWS == 2
+    // (uniform per block: an unstyled view of a styled batch reads neither its state nor the table)
+    const uint2 style = styledView ? styleTable[stateByte & (kStyleEntries - 1u)] : make_uint2(0u, kStyleIdentityY);
+#else
     const uint2 style = styleTable[stateByte & (kStyleEntries - 1u)];
+#endif
 #endif
     fill_byte_lut(lut, sincos);
     const uint32_t tid = threadIdx.x;

@@ -239,6 +239,30 @@ gsm_status GlobalRenderer::selectPick(hipStream_t s, const void* pick, size_t pi
             count = composeHost_[e].count;
         }
     }
+    return enqueueSelectPick(s, pick, pickPitch, width, height, mask, maskPitch, base, std::min(count, gaussianCount),
+                             state, andMask, xorMask, matched);
+}
+
+gsm_status GlobalRenderer::selectPickIds(hipStream_t s, const void* pick, size_t pickPitch, uint32_t width,
+                                         uint32_t height, const void* mask, size_t maskPitch, uint8_t* state,
+                                         uint32_t gaussianCount, uint32_t andMask, uint32_t xorMask,
+                                         uint32_t* matched) {
+    // selectPick's rows in its order, without those that read the last pick frame: the image holds gaussian ids
+    // (a frame of renderFrames), so the items are [0, gaussianCount) and the handle's pick state is not consulted
+    if (gaussianCount > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
+    if (!frameSizeOk(width, height)) return GSM_ERR_INVALID_DIMENSIONS;
+    if (!pick || (gaussianCount > 0 && !state)) return GSM_ERR_MISSING_REQUIRED_BUFFER;
+    if (pickPitch < (size_t)width * 4 || (pickPitch & 3u) || (((uintptr_t)pick) & 3u) || (mask && maskPitch < width) ||
+        (((uintptr_t)matched) & 3u))
+        return GSM_ERR_INVALID_BUFFER_SIZE;
+    return enqueueSelectPick(s, pick, pickPitch, width, height, mask, maskPitch, 0u, gaussianCount, state, andMask,
+                             xorMask, matched);
+}
+
+gsm_status GlobalRenderer::enqueueSelectPick(hipStream_t s, const void* pick, size_t pickPitch, uint32_t width,
+                                             uint32_t height, const void* mask, size_t maskPitch, uint32_t base,
+                                             uint32_t n, uint8_t* state, uint32_t andMask, uint32_t xorMask,
+                                             uint32_t* matched) {
     if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
     if (!arena_.selectBitmap) {  // (the handle's first select_pick: one bit per gaussian the handle can hold)
         const gsm_status st =
@@ -246,8 +270,8 @@ gsm_status GlobalRenderer::selectPick(hipStream_t s, const void* pick, size_t pi
         if (st != GSM_OK) return st;
     }
     (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's)
-    launch_select_pick((const uint8_t*)pick, pickPitch, width, height, (const uint8_t*)mask, maskPitch, base,
-                       std::min(count, gaussianCount), arena_.selectBitmap, state, andMask, xorMask, matched, s);
+    launch_select_pick((const uint8_t*)pick, pickPitch, width, height, (const uint8_t*)mask, maskPitch, base, n,
+                       arena_.selectBitmap, state, andMask, xorMask, matched, s);
     if (hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;
     return GSM_OK;
 }
@@ -452,6 +476,67 @@ gsm_status GlobalRenderer::renderViews(hipStream_t s, const gsm_gaussian_input& 
 }
 
 gsm_status GlobalRenderer::renderBatch(hipStream_t s, const gsm_global_view* views, uint32_t viewCount) {
+    return enqueueBatch(s, views, viewCount, nullptr);
+}
+
+gsm_status GlobalRenderer::renderFrames(hipStream_t s, const gsm_global_frame* frames, uint32_t frameCount) {
+    // The rows of this entry that come before the batch's, each over all frames: the first failing
+    // row decides, within it the lowest frame.  (frame_count == 0 falls through to the batch's first row.)
+    if (frameCount >= 1 && !frames) return GSM_ERR_MISSING_REQUIRED_BUFFER;
+    for (uint32_t v = 0; v < frameCount; ++v)
+        if (frames[v].flags != 0) return GSM_ERR_INVALID_ARGUMENT;
+    for (uint32_t v = 0; v < frameCount; ++v)  // (composites inside a batch: out of scope)
+        if (frames[v].object_count != 1) return GSM_ERR_UNSUPPORTED;
+    for (uint32_t v = 0; v < frameCount; ++v)
+        if (!frames[v].objects) return GSM_ERR_MISSING_REQUIRED_BUFFER;
+    // the frames as batch views plus what each adds: host copies only (reserved by the handle's first such call
+    // for the most views it can hold, so no later call allocates)
+    if (framesViews_.capacity() == 0) {
+        const uint32_t mv = std::min(tileCount_, 65535u);
+        framesViews_.reserve(mv);
+        framesOptions_.reserve(mv);
+    }
+    if (frameCount > framesViews_.capacity()) {
+        // more frames than the handle's tile space has tiles: the batch's rows up to the tile row, which such a
+        // batch cannot pass (every view takes a tile), read from the frames themselves
+        uint64_t items = 0;
+        for (uint32_t v = 0; v < frameCount; ++v) {
+            const uint32_t n = frames[v].objects[0].input.gaussian_count;
+            if (n > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
+            items += ((uint64_t)n + kProjectBlock - 1) / kProjectBlock * kProjectBlock;
+        }
+        if (items > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
+        for (uint32_t v = 0; v < frameCount; ++v)
+            if (!frameSizeOk(frames[v].width, frames[v].height)) return GSM_ERR_INVALID_DIMENSIONS;
+        return GSM_ERR_INVALID_TILE_COUNT;
+    }
+    framesViews_.resize(frameCount);
+    framesOptions_.resize(frameCount);
+    bool any = false;
+    for (uint32_t v = 0; v < frameCount; ++v) {
+        const gsm_global_frame& F = frames[v];
+        gsm_global_view& V = framesViews_[v];
+        V.input = F.objects[0].input;
+        V.camera = F.objects[0].camera;
+        V.width = F.width;
+        V.height = F.height;
+        V.color = F.color;
+        V.color_pitch_bytes = F.color_pitch_bytes;
+        V.depth = F.depth_r16f;
+        V.depth_pitch_bytes = F.depth_pitch_bytes;
+        BatchViewOptions& O = framesOptions_[v];
+        O.pick = PickTarget{F.pick_r32u, F.pick_pitch_bytes};  // (a null pointer: the option is not given)
+        O.occluder = OccluderSource{F.occluder_r32f, F.occluder_pitch_bytes};
+        O.styled = F.states || F.styles;  // (one without the other: the styled row refuses)
+        O.style = StyleSource{F.states, F.styles, F.style_count};
+        any = any || F.pick_r32u || F.occluder_r32f || O.styled;
+    }
+    // every option NULL in every frame: the plain batch, its path and its device code
+    return enqueueBatch(s, framesViews_.data(), frameCount, any ? framesOptions_.data() : nullptr);
+}
+
+gsm_status GlobalRenderer::enqueueBatch(hipStream_t s, const gsm_global_view* views, uint32_t viewCount,
+                                        const BatchViewOptions* options) {
     // Every check before anything is enqueued, one kind of check after another over all views (the first
     // failing kind decides, within it the lowest view): counts, dimensions, tiles, missing buffers, sizes,
     // sh_components, tile rows.  (The counts of a NULL array cannot be read: that is the missing buffer.)
@@ -476,13 +561,35 @@ gsm_status GlobalRenderer::renderBatch(hipStream_t s, const gsm_global_view* vie
     }
     for (uint32_t v = 0; v < viewCount; ++v) {  // (everything above passed: what is left of validate_frame is sizes)
         const gsm_global_view& V = views[v];
+        // (a view's pick target and occluder, where given, join the size row as for gsm_global_render_frame)
+        const PickTarget* pick = options && options[v].pick.pixels ? &options[v].pick : nullptr;
+        const OccluderSource* occluder = options && options[v].occluder.pixels ? &options[v].occluder : nullptr;
         const gsm_status st = validate_frame(config_, maxGaussians_, maxWidth_, maxHeight_, V.input.gaussian_count,
                                              true, false, V.width, V.height, V.color, V.color_pitch_bytes, 1, V.depth,
-                                             V.depth_pitch_bytes);
+                                             V.depth_pitch_bytes, pick, occluder);
         if (st != GSM_OK) return st;
     }
     for (uint32_t v = 1; v < viewCount; ++v)
         if (views[v].input.sh_components != views[0].input.sh_components) return GSM_ERR_INVALID_ARGUMENT;
+    // the styled row, per view; the batch has one style table, so every styled view must give the same one (the
+    // six meaningful bytes of every style; pad is ignored)
+    bool anyPick = false, anyOccluder = false;
+    const StyleSource* table = nullptr;
+    for (uint32_t v = 0; options && v < viewCount; ++v) {
+        const BatchViewOptions& O = options[v];
+        anyPick = anyPick || O.pick.pixels;
+        anyOccluder = anyOccluder || O.occluder.pixels;
+        if (!O.styled) continue;
+        if (!styleSourceOk(O.style, 1)) return GSM_ERR_INVALID_ARGUMENT;
+        if (!table) {
+            table = &O.style;
+            continue;
+        }
+        if (O.style.styleCount != table->styleCount) return GSM_ERR_INVALID_ARGUMENT;
+        for (uint32_t i = 0; i < table->styleCount; ++i)
+            if (std::memcmp(&O.style.styles[i], &table->styles[i], offsetof(gsm_global_style, pad)) != 0)
+                return GSM_ERR_INVALID_ARGUMENT;
+    }
     if (tileRowsRestricted()) return GSM_ERR_UNSUPPORTED;  // (set_tile_rows)
     if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
     // the per-view array and the two lookup tables: allocated by the handle's first batch, for the most views
@@ -504,6 +611,12 @@ gsm_status GlobalRenderer::renderBatch(hipStream_t s, const gsm_global_view* vie
         arena_.batchBlockView = bv;
         arena_.batchTileView = tv;
         maxBatchViews_ = mv;
+    }
+    // the per-view options array: allocated by the handle's first batch with options, one line per view it can hold
+    if (options && !arena_.batchExtras) {
+        const gsm_status st = allocs_.alloc((void**)&arena_.batchExtras, (size_t)maxBatchViews_ * sizeof(BatchExtras));
+        if (st != GSM_OK) return st;
+        extrasHost_.reserve(maxBatchViews_);
     }
     (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's)
     // the host copy of the per-view entries (`views` is consumed before the call returns): each view's own
@@ -562,6 +675,44 @@ gsm_status GlobalRenderer::renderBatch(hipStream_t s, const gsm_global_view* vie
     bf.tileView = arena_.batchTileView;
     const uint32_t deg = sh_degree(sh);
     const bool half = config_.precision == GSM_PRECISION_FLOAT16;
+    if (options) {
+        // the host copy of the per-view options, to the device array in kernel-argument chunks as the entries
+        // above; the alignment bits follow each view's own pointer and pitch, as launch_blend's for a single frame
+        extrasHost_.resize(viewCount);
+        for (uint32_t v = 0; v < viewCount; ++v) {
+            const BatchViewOptions& O = options[v];
+            BatchExtras& e = extrasHost_[v];
+            std::memset(&e, 0, sizeof(e));
+            e.pick = (uint8_t*)O.pick.pixels;
+            e.pickPitch = O.pick.pixels ? O.pick.pitch : 0;
+            e.occluder = (const uint8_t*)O.occluder.pixels;
+            e.occluderPitch = O.occluder.pixels ? O.occluder.pitch : 0;
+            if (O.styled) {  // (one object per frame: states[0], as renderFrame)
+                e.styled = 1u;
+                e.state = O.style.states[0].state;
+                e.defaultState = O.style.states[0].default_state;
+            }
+            e.align = ((O.pick.pixels && (((uintptr_t)O.pick.pixels) & 7u) == 0 && (O.pick.pitch & 7u) == 0) ? 8192u : 0u) |
+                      ((O.occluder.pixels && (((uintptr_t)O.occluder.pixels) & 7u) == 0 && (O.occluder.pitch & 7u) == 0)
+                           ? 16384u
+                           : 0u);
+            e.itemBase = batchHost_[v].blockBase * (uint32_t)kProjectBlock;
+        }
+        fill_chunks<ExtrasChunk>(extrasHost_, viewCount, [&](const ExtrasChunk& c, uint32_t v0, uint32_t n) {
+            launch_fill_batch_extras(c, v0, n, arena_.batchExtras, s);
+        });
+        bf.extras = arena_.batchExtras;
+        rq.anyPick = anyPick;
+        rq.anyOccluder = anyOccluder;
+        if (table) {
+            const gsm_status st = fillStyleTable(s, table->styles, table->styleCount);
+            if (st != GSM_OK) return st;
+            rq.styled = true;
+            return runFrame(s, rq, [&](const ProjectArgs& pa) {
+                launch_project_batch_styled(half, deg, pa, bf, arena_.styleTable, arena_, s);
+            });
+        }
+    }
     return runFrame(s, rq, [&](const ProjectArgs& pa) { launch_project_batch(half, deg, pa, bf, arena_, s); });
 }
 
@@ -844,8 +995,9 @@ const ScheduleKey& GlobalRenderer::requestKey(const FrameRequest& rq, uint32_t* 
     }
     // (a pick frame walks without compaction or pairs, an occluded frame's walks end at the occluder, a styled
     // frame hides and fades gaussians: their costs are their own, either way round)
-    key_[ScheduleKey::kPick] = rq.pick ? 1u : 0u;
-    key_[ScheduleKey::kOccluded] = rq.occluder ? 1u : 0u;
+    // (a batch with options: the union over its views, so such batches keep unit costs of their own)
+    key_[ScheduleKey::kPick] = (rq.pick || rq.anyPick) ? 1u : 0u;
+    key_[ScheduleKey::kOccluded] = (rq.occluder || rq.anyOccluder) ? 1u : 0u;
     key_[ScheduleKey::kStyled] = rq.styled ? 1u : 0u;
     key_[ScheduleKey::kUnitsPerTile] = blend_units_per_tile(*tiles, dev_.numCUs);
     key_[ScheduleKey::kWidth] = rq.width;
@@ -968,6 +1120,10 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const FrameRequest& rq, Front
     const bool fullRadix = tuning_.fullRadix;
     // an occluded frame's blend walks the tiles' whole sorted runs: the tile sort writes them out
     // as it does for a captured frame
+    // (a batch in which some view has a pick target or an occluder walks them too: its one union kernel is the
+    // occluded pick walk)
+    const bool unionWalk = batch && batch->extras && (rq.anyPick || rq.anyOccluder);
+    const bool keepRuns = rq.occluder || unionWalk;
     const uint32_t* blendRun = nullptr;
     const bool ballot = tuning_.ballotRank;
     if (!fullRadix) {
@@ -981,10 +1137,10 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const FrameRequest& rq, Front
         if (res == kSortNoSpace) return GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;  // (nothing of the sort launched)
         tile_depth_sort(kb[res], vb[res], kb[res ^ 1], vb[res ^ 1], arena_.tileStart, 0u, localTiles, s, ballot,
                         arena_.halfVals[0], arena_.halfVals[1],
-                        arena_.halfCount, tileCount_, capture || rq.occluder, dev_.numCUs);
+                        arena_.halfCount, tileCount_, capture || keepRuns, dev_.numCUs);
         sortedKeys_ = capture ? kb[res ^ 1] : nullptr;
         sortedVals_ = capture ? vb[res ^ 1] : nullptr;
-        blendRun = rq.occluder ? vb[res ^ 1] : nullptr;
+        blendRun = keepRuns ? vb[res ^ 1] : nullptr;
     } else {
         const int res = radix_sort_pairs(kb, vb, &arena_.header->totalAssignments, maxAssignments_, 0,
                                          sortPassCount(), sort_space(arena_), s, ballot,
@@ -1015,6 +1171,7 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const FrameRequest& rq, Front
     bo.pick = rq.pick;
     bo.occluder = rq.occluder;
     bo.sortedVals = blendRun;
+    bo.batchExtras = unionWalk ? batch->extras : nullptr;
     bo.numCUs = dev_.numCUs;
     lastBlendKernel_ = launch_blend(g, arena_, tg, bo, s);
     timer_.record(6, s, true);

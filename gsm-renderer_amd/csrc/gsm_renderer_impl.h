@@ -54,6 +54,9 @@ class GlobalRenderer {
 
     // views of different scenes and sizes in one frame (gsm_global_render_batch)
     gsm_status renderBatch(hipStream_t stream, const gsm_global_view* views, uint32_t viewCount);
+    // the same batch from frame descriptors, each with its own nullable pick target, occluder and styles
+    // (gsm_global_render_frames)
+    gsm_status renderFrames(hipStream_t stream, const gsm_global_frame* frames, uint32_t frameCount);
 
     // state bytes of the gaussians whose projected centre lies on a nonzero mask byte (gsm_global_select_mask)
     gsm_status selectMask(hipStream_t stream, const gsm_gaussian_input* input, const gsm_camera_params* camera,
@@ -65,6 +68,10 @@ class GlobalRenderer {
     gsm_status selectPick(hipStream_t stream, const void* pick, size_t pickPitch, uint32_t width, uint32_t height,
                           const void* mask, size_t maskPitch, uint32_t object, uint8_t* state, uint32_t gaussianCount,
                           uint32_t andMask, uint32_t xorMask, uint32_t* matched);
+    // the stateless form for pick images that hold gaussian ids (gsm_global_select_pick_ids)
+    gsm_status selectPickIds(hipStream_t stream, const void* pick, size_t pickPitch, uint32_t width, uint32_t height,
+                             const void* mask, size_t maskPitch, uint8_t* state, uint32_t gaussianCount,
+                             uint32_t andMask, uint32_t xorMask, uint32_t* matched);
     // items of the last enqueued pick frame -> (object of the call, gaussian id within it); host only, no sync
     gsm_status pickOwner(const uint32_t* items, uint32_t n, uint32_t* object, uint32_t* gaussian) const;
 
@@ -148,6 +155,9 @@ class GlobalRenderer {
         const PickTarget* pick = nullptr;
         const OccluderSource* occluder = nullptr;
         bool styled = false;  // the projection applies styles: the walks are the frame's own (schedule key)
+        // a Batch with options (renderFrames): some view has a pick target / an occluder.  The targets themselves
+        // are per view (BatchFrame::extras); these are the union the schedule key and the blend's kernel follow.
+        bool anyPick = false, anyOccluder = false;
         // the records path: the count on the device, the units ordered by an earlier partitionCounts, the barrier
         // the blend's waves arrive at
         const uint32_t* devCount = nullptr;
@@ -173,6 +183,22 @@ class GlobalRenderer {
     bool tileRowsRestricted() const { return rowBegin_ != 0 || rowEnd_ != tilesY_ || rowStride_ != 1; }
     ProjectArgs batchSharedArgs(const gsm_camera_params& camera0, uint32_t width0, uint32_t height0, uint32_t count,
                                 uint32_t shComponents) const;
+    // What a frame of renderFrames adds to its view (host memory of the caller, consumed by the call); pixels null:
+    // the option is not given; styled: states and styles as gsm_global_render_frame takes them for one object.
+    struct BatchViewOptions {
+        PickTarget pick{nullptr, 0};
+        OccluderSource occluder{nullptr, 0};
+        bool styled = false;
+        StyleSource style{nullptr, nullptr, 0};
+    };
+    // renderBatch and renderFrames: every check, the per-view entries and tables, the request, the frame.
+    // options (nullable, [viewCount]): null is the plain batch, device code and all.
+    gsm_status enqueueBatch(hipStream_t s, const gsm_global_view* views, uint32_t viewCount,
+                            const BatchViewOptions* options);
+    // the tail selectPick and selectPickIds share: the bitmap (allocated by the first call) and the two launches
+    gsm_status enqueueSelectPick(hipStream_t s, const void* pick, size_t pickPitch, uint32_t width, uint32_t height,
+                                 const void* mask, size_t maskPitch, uint32_t base, uint32_t n, uint8_t* state,
+                                 uint32_t andMask, uint32_t xorMask, uint32_t* matched);
     PartitionBuffers part_;
     uint32_t partCount_ = 0;  // ids of the last partitionCounts
     SlabTable partSlabs_{};
@@ -220,6 +246,9 @@ class GlobalRenderer {
     uint32_t maxViews_ = 0;                   // entries of arena_.viewArgs
     std::vector<BatchViewArgs> batchHost_;    // the last batch's per-view entries (render_batch)
     uint32_t maxBatchViews_ = 0;              // entries of arena_.batchArgs
+    std::vector<BatchExtras> extrasHost_;     // the last batch's per-view options (render_frames)
+    std::vector<gsm_global_view> framesViews_;      // render_frames: the call's frames as batch views ...
+    std::vector<BatchViewOptions> framesOptions_;   // ... and what each adds
     std::vector<ComposeObjectArgs> composeHost_;  // the last composite's per-object entries (render_composite)
     std::vector<uint32_t> composeObject_;     // the call's object index of every entry of composeHost_
     bool lastPick_ = false;                   // the last enqueued frame was a pick frame (pickOwner)

@@ -176,6 +176,28 @@ class SceneObject:
 
 
 @dataclass
+class Frame:
+    """gsm_global_frame: one descriptor of GlobalRenderer.render_frames -- `render_frame`'s arguments as a value.
+    objects: one (GaussianInput, CameraParams) pair (or a SceneObject list of one); pick / occluder / states /
+    styles None: that option is not given; pitches None: width * bytes per pixel."""
+    objects: object
+    width: int
+    height: int
+    color: "torch.Tensor"
+    depth: Optional["torch.Tensor"] = None
+    pick: Optional["torch.Tensor"] = None
+    occluder: Optional["torch.Tensor"] = None
+    states: object = None
+    styles: object = None
+    color_pitch: Optional[int] = None
+    depth_pitch: Optional[int] = None
+    pick_pitch: Optional[int] = None
+    occluder_pitch: Optional[int] = None
+    style_count: Optional[int] = None
+    flags: int = 0
+
+
+@dataclass
 class Style:
     """gsm_global_style: one entry of a styled frame's table.  tint is (r, g, b) in the u8 colour space of the
     projected gaussians; tint_amount 0 leaves the colour, 255 replaces it; opacity_scale 255 leaves the opacity, 0
@@ -310,6 +332,10 @@ _SIGNATURES = {
     "gsm_global_select_pick": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
                                 C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p],
                                C.c_int),
+    "gsm_global_render_frames": ([C.c_void_p, C.c_void_p, C.POINTER(_GlobalFrame), C.c_uint32], C.c_int),
+    "gsm_global_select_pick_ids": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                    C.c_void_p], C.c_int),
     "gsm_global_render_stereo": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera),
                                   C.POINTER(_Camera), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                   C.c_void_p, C.c_size_t], C.c_int),
@@ -747,6 +773,18 @@ class GlobalRenderer(_Renderer):
         `render_pick` / `render_occluded`, None leaves the option out.  states: one entry per object (a uint8 CUDA
         tensor or an int), or a single such value for a single object; styles: a Style list.  null_frame passes a
         NULL descriptor (the C entry's error path)."""
+        f = _GlobalFrame()
+        keep = self._fill_frame(f, color_texture, depth_texture, objects, width, height, pick, occluder, states, styles,
+                                color_pitch, depth_pitch, pick_pitch, occluder_pitch, style_count, flags)
+        st = _lib().gsm_global_render_frame(self._h, _stream_handle(stream), None if null_frame else C.byref(f))
+        del keep
+        _check(st, "gsm_global_render_frame")
+
+    def _fill_frame(self, f, color_texture, depth_texture, objects, width, height, pick=None, occluder=None,
+                    states=None, styles=None, color_pitch=None, depth_pitch=None, pick_pitch=None,
+                    occluder_pitch=None, style_count=None, flags=0):
+        """Fills the gsm_global_frame `f` (render_frame's arguments); returns the ctypes arrays it points to, which
+        the caller keeps alive until the C call has returned."""
         single = isinstance(objects, tuple) and len(objects) == 2 and isinstance(objects[0], GaussianInput)
         if single:
             objects = [SceneObject(objects[0], objects[1])]
@@ -757,7 +795,6 @@ class GlobalRenderer(_Renderer):
         starr = None
         if states is not None:
             starr = (_State * max(len(states), 1))(*[_state_struct(s) for s in states])
-        f = _GlobalFrame()
         f.objects = arr if arr is not None else C.POINTER(_GlobalObject)()
         f.object_count, f.width, f.height = n, int(width), int(height)
         f.color, f.depth_r16f = _ptr(color_texture), _ptr(depth_texture)
@@ -770,8 +807,38 @@ class GlobalRenderer(_Renderer):
         f.styles = sarr if sarr is not None else C.POINTER(_Style)()
         f.style_count = sn if style_count is None else int(style_count)
         f.flags = int(flags)
-        st = _lib().gsm_global_render_frame(self._h, _stream_handle(stream), None if null_frame else C.byref(f))
-        _check(st, "gsm_global_render_frame")
+        return arr, sarr, starr
+
+    def render_frames(self, frames, stream=None):
+        """gsm_global_render_frames: the Frame list `frames` -- each a scene, camera, size and targets with its own
+        optional pick target, occluder and styles -- in one batch; every frame's bytes equal those of
+        `render_frame` for that frame alone, and a pick pixel holds the gaussian id of its frame's scene.  frames
+        None: a NULL array with frame_count 1 (the C entry's error path)."""
+        n = 1 if frames is None else len(frames)
+        arr, keep = None, []
+        if frames is not None:
+            arr = (_GlobalFrame * max(n, 1))()
+            for f, d in zip(arr, frames):
+                keep.append(self._fill_frame(f, d.color, d.depth, d.objects, d.width, d.height, d.pick, d.occluder,
+                                             d.states, d.styles, d.color_pitch, d.depth_pitch, d.pick_pitch,
+                                             d.occluder_pitch, d.style_count, d.flags))
+        st = _lib().gsm_global_render_frames(self._h, _stream_handle(stream), arr, n)
+        del keep
+        _check(st, "gsm_global_render_frames")
+
+    def select_pick_ids(self, pick, width: int, height: int, state, gaussian_count: int, and_mask: int,
+                        xor_mask: int, mask=None, matched=None, stream=None, pick_pitch: Optional[int] = None,
+                        mask_pitch: Optional[int] = None):
+        """gsm_global_select_pick_ids: `select_pick` for a pick image that holds gaussian ids (a frame of
+        `render_frames`): every id below gaussian_count that the image shows on a nonzero byte of `mask` (None:
+        every pixel) gets (old & and_mask) ^ xor_mask, once.  Reads no state of the handle's last frame."""
+        pp = pick_pitch if pick_pitch is not None else int(width) * 4
+        mp = mask_pitch if mask_pitch is not None else int(width)
+        st = _lib().gsm_global_select_pick_ids(self._h, _stream_handle(stream), _ptr(pick), pp, int(width),
+                                               int(height), _ptr(mask), mp, _ptr(state), int(gaussian_count),
+                                               int(and_mask) & 0xFFFFFFFF, int(xor_mask) & 0xFFFFFFFF,
+                                               _ptr(matched))
+        _check(st, "gsm_global_select_pick_ids")
 
     def select_pick(self, pick, width: int, height: int, object: int, state, gaussian_count: int, and_mask: int,
                     xor_mask: int, mask=None, matched=None, stream=None, pick_pitch: Optional[int] = None,

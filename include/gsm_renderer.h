@@ -291,8 +291,9 @@ gsm_status gsm_global_render_composite(gsm_renderer *renderer, void *stream,
  *                                    4-byte aligned;
  *   GSM_ERR_UNSUPPORTED              (both entries, after every other check) the handle is restricted to tile
  *                                    rows (gsm_global_set_tile_rows).
- * Enqueue-only and capturable like the plain entries; nothing is allocated per frame.  gsm_global_render_views,
- * gsm_global_render_batch, the DepthFirst and Local renderers and the multi-GPU frame have no pick entry. */
+ * Enqueue-only and capturable like the plain entries; nothing is allocated per frame.  A batch of views with pick
+ * targets is gsm_global_render_frames (below); gsm_global_render_views, the DepthFirst and Local renderers and the
+ * multi-GPU frame have no pick entry. */
 #define GSM_PICK_NONE 0xFFFFFFFFu
 gsm_status gsm_global_render_pick(gsm_renderer *renderer, void *stream, const gsm_gaussian_input *input,
                                   const gsm_camera_params *camera, uint32_t width, uint32_t height,
@@ -342,9 +343,10 @@ gsm_status gsm_global_pick_owner(gsm_renderer *renderer, const uint32_t *items, 
  *                                    4-byte aligned;
  *   GSM_ERR_UNSUPPORTED              (both entries, after every other check) the handle is restricted to tile
  *                                    rows (gsm_global_set_tile_rows).
- * Enqueue-only and capturable like the plain entries; nothing is allocated per frame.  gsm_global_render_views,
- * gsm_global_render_batch, the DepthFirst and Local renderers and the multi-GPU frame have no occluded entry;
- * gsm_global_render_frame (below) combines an occluder with a pick target and with styles. */
+ * Enqueue-only and capturable like the plain entries; nothing is allocated per frame.  gsm_global_render_frame
+ * (below) combines an occluder with a pick target and with styles, gsm_global_render_frames does so for a batch of
+ * views; gsm_global_render_views, the DepthFirst and Local renderers and the multi-GPU frame have no occluded
+ * entry. */
 gsm_status gsm_global_render_occluded(gsm_renderer *renderer, void *stream, const gsm_gaussian_input *input,
                                       const gsm_camera_params *camera, uint32_t width, uint32_t height,
                                       void *color, size_t color_pitch_bytes, void *depth_r16f,
@@ -385,9 +387,9 @@ gsm_status gsm_global_render_composite_occluded(gsm_renderer *renderer, void *st
  *   GSM_ERR_UNSUPPORTED       the handle is restricted to tile rows (gsm_global_set_tile_rows).
  * Enqueue-only and capturable; a captured frame replays the table and the state pointers it was captured with.
  * Nothing is allocated per frame (the handle's first styled frame allocates the 2 KiB table).
- * gsm_global_render_views, gsm_global_render_batch, the DepthFirst and Local renderers and the multi-GPU frame
- * have no styled entry; gsm_global_render_frame (below) combines styles with an occluder.  A style changes neither
- * position nor scale. */
+ * gsm_global_render_frame (below) combines styles with an occluder, gsm_global_render_frames does so for a batch
+ * of views; gsm_global_render_views, the DepthFirst and Local renderers and the multi-GPU frame have no styled
+ * entry.  A style changes neither position nor scale. */
 typedef struct {
     uint8_t tint_r, tint_g, tint_b; /* in the u8 colour space of GaussianRenderData: after the SH evaluation and,
                                        for gaussian_color_space SRGB, after the decode to linear */
@@ -484,8 +486,9 @@ gsm_status gsm_global_select_mask(gsm_renderer *renderer, void *stream, const gs
  *   GSM_ERR_UNSUPPORTED              last: the handle is restricted to tile rows (gsm_global_set_tile_rows) and
  *                                    the frame has a pick target, an occluder or styles, or more than one object.
  * Enqueue-only and capturable; nothing is allocated per frame beyond what the entries above allocate once.
- * Out of scope: gsm_global_render_views, gsm_global_render_batch, gsm_global_render_records, the DepthFirst and
- * Local renderers and the multi-GPU frame take no pick target, occluder or styles. */
+ * Several descriptors in one batch -- a quad view, a stereo pair -- are gsm_global_render_frames (below).  Out of
+ * scope: gsm_global_render_views, gsm_global_render_records, the DepthFirst and Local renderers and the multi-GPU
+ * frame take no pick target, occluder or styles. */
 typedef struct {
     const gsm_global_object *objects;  uint32_t object_count;   /* 1 object = a single frame */
     uint32_t width, height;
@@ -531,6 +534,80 @@ gsm_status gsm_global_select_pick(gsm_renderer *renderer, void *stream,
                                   const void *mask_u8, size_t mask_pitch_bytes,
                                   uint32_t object, uint8_t *state, uint32_t gaussian_count,
                                   uint32_t and_mask, uint32_t xor_mask, uint32_t *matched);
+
+/* Several frame descriptors in one batch (no reference analogue): a quad view, a main view with
+ * thumbnails, a stereo pair -- every viewport with its own selection shown, its own mesh cutting the splats and
+ * its own pick image.  frame_count frames are rendered by one launch chain over the combined item and tile space of
+ * gsm_global_render_batch; each frame has its own scene, camera, size and targets and its own nullable pick target,
+ * occluder and states.  gsm_global_frame is used unchanged; every frame has object_count == 1.
+ *
+ * Bytes.  For every frame v the colour, depth and pick bytes equal those of gsm_global_render_frame(&frames[v])
+ * called alone.  A pick pixel therefore holds the gaussian id of frame v's scene, or GSM_PICK_NONE -- never the
+ * batch item: the walk subtracts the view's first item before the store.  The options are independent per frame:
+ * one frame may have a pick target and no occluder while its neighbour has the reverse, or neither; the depth, pick
+ * and occluder pointers of different frames may be NULL in any mixture.  With every option NULL in every frame the
+ * bytes equal gsm_global_render_batch of the same views (and that entry's path runs); with frame_count == 1 they
+ * equal gsm_global_render_frame.
+ *
+ * Layout: gsm_global_render_batch's.  Frame v's items start at 256 * B_v, B_v = sum over u < v of
+ * ceil(count_u / 256), its tiles at the sum of the tiles of the frames before it, on its own grid.
+ *
+ * Memory.  Targets of different frames must not overlap, pick targets included; this is not checked, as for the
+ * batch.  Occluders and state arrays are only read and may be shared between frames.  A side-by-side stereo pair is
+ * two frames into one colour, one depth and one pick image and out of one occluder image: the second frame's
+ * pointers start `width` pixels into the row and both use the shared pitch.
+ *
+ * Styles.  The batch has one style table: every frame whose `styles` is non-NULL must give the same style_count and
+ * the same six meaningful bytes per style (pad is ignored).  A frame with styles == NULL and states == NULL is
+ * unstyled; a frame with styles uses states[0], as gsm_global_render_frame does for one object.
+ *
+ * Enqueue-only and capturable; `frames` and what it points to in host memory are consumed before the call returns.
+ * Nothing is allocated per frame beyond small per-view arrays on the handle's first such call.  After the call the
+ * handle's "last pick frame" state is cleared: gsm_global_pick_owner and gsm_global_select_pick return
+ * GSM_ERR_RENDER_FAILED, as after any frame without a pick target -- the pick pixels already are gaussian ids of the
+ * view's scene, so no owner lookup is needed, and gsm_global_select_pick_ids (below) selects from them.
+ *
+ * Checked before anything is enqueued; the first failing row decides, within a row the lowest frame index:
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  frames NULL with frame_count >= 1;
+ *   GSM_ERR_INVALID_ARGUMENT         a frame with flags != 0;
+ *   GSM_ERR_UNSUPPORTED              a frame with object_count != 1 (composites inside a batch are out of scope);
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  a frame's objects NULL;
+ *   then the rows of gsm_global_render_batch, in its order, applied to (objects[0].input, objects[0].camera, width,
+ *   height, color, depth_r16f) of every frame -- frame_count == 0 gives GSM_ERR_INVALID_GAUSSIAN_COUNT -- with the
+ *   pick target and the occluder joining the rows as they do for gsm_global_render_frame:
+ *   GSM_ERR_INVALID_BUFFER_SIZE      also: pick_pitch_bytes < 4 * width or occluder_pitch_bytes < 4 * width, or
+ *                                    either pointer or pitch not 4-byte aligned (NULL: not given, never missing);
+ *   GSM_ERR_INVALID_ARGUMENT         frames that differ in sh_components;
+ *   GSM_ERR_INVALID_ARGUMENT         the styled row of gsm_global_render_frame, per frame; or two frames whose
+ *                                    style tables differ;
+ *   GSM_ERR_UNSUPPORTED              the handle is restricted to tile rows (gsm_global_set_tile_rows).
+ * Out of scope: composites inside a batch (object_count > 1); gsm_global_render_views keeps its signature and
+ * stays without options. */
+gsm_status gsm_global_render_frames(gsm_renderer *renderer, void *stream,
+                                    const gsm_global_frame *frames, uint32_t frame_count);
+
+/* The stateless form of gsm_global_select_pick, for pick images that hold gaussian ids (a frame of
+ * gsm_global_render_frames, or a single-scene pick frame).  With
+ *   S = { id : pixel (x, y) of width x height has a nonzero mask byte (or mask_u8 is NULL) and
+ *         id = pick[y][x] < gaussian_count },
+ * every id of S gets state[id] = ((old & and_mask) ^ xor_mask) & 0xFF exactly once, however many pixels it covers;
+ * every other byte of `state`, and every byte at or past gaussian_count, keeps its value.  `matched` (device,
+ * nullable) receives |S|: overwritten, not added to.  GSM_PICK_NONE never matches.  It neither reads nor changes
+ * the handle's last-pick state; it shares the handle's bitmap with gsm_global_select_pick.  Enqueue-only and
+ * capturable.
+ *
+ * Checks, in this order:
+ *   GSM_ERR_INVALID_GAUSSIAN_COUNT   gaussian_count > max_gaussians;
+ *   GSM_ERR_INVALID_DIMENSIONS       width or height zero, or above max_width / max_height;
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  pick_r32u NULL, or state NULL with a count > 0;
+ *   GSM_ERR_INVALID_BUFFER_SIZE      pick_pitch_bytes < 4 * width, the pick pointer or pitch not 4-byte aligned,
+ *                                    mask_pitch_bytes < width (mask_u8 non-NULL), or matched not 4-byte aligned.
+ * A count of 0 is a no-op that writes *matched = 0. */
+gsm_status gsm_global_select_pick_ids(gsm_renderer *renderer, void *stream,
+                                      const void *pick_r32u, size_t pick_pitch_bytes, uint32_t width, uint32_t height,
+                                      const void *mask_u8, size_t mask_pitch_bytes,
+                                      uint8_t *state, uint32_t gaussian_count,
+                                      uint32_t and_mask, uint32_t xor_mask, uint32_t *matched);
 
 /* GlobalRenderer.renderStereo (GlobalRenderer.swift:240-255) calls fatalError for
  * every target; this entry returns GSM_ERR_UNSUPPORTED instead. */
