@@ -156,7 +156,7 @@ def ink_margin(op, det, depth, near, far):
 
 
 def project(world, harm, sh_components, cam, w, h, color_space=0, renderer="global", scene_transform=None,
-            sh_center=None):
+            sh_center=None, pose=False):
     """Every gaussian of the scene through the reference's projection, in float64.
 
     Returns a dict of arrays over all n gaussians (culled ones included; their later fields may hold
@@ -170,7 +170,12 @@ def project(world, harm, sh_components, cam, w, h, color_space=0, renderer="glob
     scene_transform (column-major flat 4x4, scene -> world) moves the positions and multiplies the scales by
     the length of its first column; its rotation does not turn the covariance and the SH direction is taken
     from the untransformed position (both the reference's choices).  sh_center: the point the SH direction
-    is taken from, the camera position by default."""
+    is taken from, the camera position by default.
+    pose=True takes scene_transform as the model matrix M of a composite's object and does what
+    the mathematics does: the covariance becomes A Sigma A^T with A the upper 3x3 of M (for a similarity, the
+    scales times its factor and the axes turned by its rotation), and the SH direction is that from the
+    gaussian to the camera seen in the object's frame, A^-1 (camera - M p).  The scale cull stays on the
+    scales as stored."""
     n = len(world)
     k = max(int(sh_components), 1)
     pos, scale, quat, op = unpack_world(world)
@@ -193,7 +198,11 @@ def project(world, harm, sh_components, cam, w, h, color_space=0, renderer="glob
         mean = (ndc + 1.0) * 0.5 * np.array([W, H]) - shift
 
         R = rotation_from_quaternion(quat)
-        cov3d = R @ (scale[:, :, None] ** 2 * np.transpose(R, (0, 2, 1)))
+        if pose and scene_transform is not None:
+            A = S[:3, :3]
+            cov3d = A @ (R @ (model_scale[:, :, None] ** 2 * np.transpose(R, (0, 2, 1)))) @ A.T
+        else:
+            cov3d = R @ (scale[:, :, None] ** 2 * np.transpose(R, (0, 2, 1)))
 
         vx, vy, vz = view4[:, 0], view4[:, 1], view4[:, 2]
         az = np.maximum(np.abs(vz), 1e-4)
@@ -264,7 +273,10 @@ def project(world, harm, sh_components, cam, w, h, color_space=0, renderer="glob
         visible = margin > 0.0
 
         center = cam["position"] if sh_center is None else sh_center
-        dirs = np.asarray(center, np.float64)[None] - scene_pos
+        if pose and scene_transform is not None and sh_center is None:
+            dirs = (np.asarray(center, np.float64)[None] - pos) @ np.linalg.inv(S[:3, :3]).T
+        else:
+            dirs = np.asarray(center, np.float64)[None] - scene_pos
         dirs = dirs / np.linalg.norm(dirs, axis=1, keepdims=True)
         coef = unpack_harmonics(harm, n, k)
         if k == 1:
@@ -381,14 +393,71 @@ def _composite(rec, ids, alpha, live, rules):
     return rgb, out_alpha, dep, unsure
 
 
-def blend_lists(records, lists, tile_w, tile_h, w, h, clear, rules, on_tile=None) -> dict:
+PICK_NONE = -1  # the model's "none" (the implementation's GSM_PICK_NONE is 0xFFFFFFFF)
+
+
+def occluder_limits(occluder, xs, ys, w, h):
+    """Z per pixel of (xs, ys): the occluder rounded once to fp16; +inf outside the frame (never read there)."""
+    Z = np.full(len(xs), np.inf)
+    if occluder is not None:
+        inside = (xs < w) & (ys < h)
+        Z[inside] = round_h(np.asarray(occluder, np.float64)[ys[inside], xs[inside]])
+    return Z
+
+
+def occlusion(Z, dep, how="sticky"):
+    """(shut [k, p], closed_before [k, p]) of entries with fp16 depths dep [k] under limits Z [p].  An entry is
+    shut at a pixel when it does not contribute there; closed_before is what the break test ahead of the entry
+    sees.  how='sticky': a pixel closes at the first entry with Z < depth and stays closed (the contract's flag);
+    how='entry': each entry is compared on its own, and the break test sees the previous entry's comparison (the
+    kernel's form).  A NaN Z compares false: it occludes nothing."""
+    with np.errstate(invalid="ignore"):
+        behind = Z[None, :] < np.asarray(dep, np.float64)[:, None]
+    shut = np.logical_or.accumulate(behind, axis=0) if how == "sticky" else behind
+    before = np.zeros_like(shut)
+    before[1:] = shut[:-1]
+    return shut, before
+
+
+def _pick(ids, wgt, query=None):
+    """From the weights wgt [k, p] (alpha times the transmittance before the entry, zero where the entry is not
+    live or is shut): the first entry of the largest weight per pixel (PICK_NONE where no weight is positive),
+    that weight, the largest weight of any other entry, and -- for query [p], an id per pixel or PICK_NONE --
+    the weight of the first occurrence of that id (-1 where the id is not in ids)."""
+    k, p = wgt.shape
+    cols = np.arange(p)
+    first = np.argmax(wgt, axis=0)
+    top = wgt[first, cols]
+    rest = wgt.copy()
+    rest[first, cols] = -1.0
+    second = np.maximum(rest.max(0), 0.0) if k > 1 else np.zeros(p)
+    pick = np.where(top > 0.0, np.asarray(ids)[first], PICK_NONE)
+    out = dict(pick=pick, pick_weight=np.maximum(top, 0.0), pick_second=second)
+    if query is not None:
+        hit = np.asarray(ids)[:, None] == np.asarray(query)[None, :]
+        at = np.argmax(hit, axis=0)
+        out["query_in"], out["query_at"] = hit.any(0), at
+        out["query_weight"] = np.where(out["query_in"], wgt[at, cols], -1.0)
+    return out
+
+
+def blend_lists(records, lists, tile_w, tile_h, w, h, clear, rules, on_tile=None, occluder=None, pick=False,
+                pick_query=None, occlusion_form="sticky") -> dict:
     """Front-to-back compositing of each tile's list.  lists: iterable of (tile index, gaussian ids in blend
     order); tiles are numbered row-major over ceil(w / tile_w) columns.  A pixel group (rules['group'], in
     pixels) stops before the first entry at which the largest transmittance among its pixels is below
     rules['break_below'].  Pixels outside every listed tile hold `clear` (depth 0).  rules['r2_max'], if
     present, is the quadratic form beyond which alpha is zero.  on_tile(tile, ids, xs, ys, alpha, live) is
     called for every non-empty list with the [entries, pixels] arrays of that tile.
-    Returns color [h,w,3], alpha [h,w], depth [h,w], covered [h,w] (inside a listed tile) and depth_unsure."""
+    Returns color [h,w,3], alpha [h,w], depth [h,w], covered [h,w] (inside a listed tile) and depth_unsure.
+    occluder [h, w]: Z is the occluder rounded once to fp16; an entry contributes at a pixel only
+    if not (Z < the entry's fp16 depth), by the sticky flag (occlusion_form 'entry': compared entry by entry);
+    the break test sees a closed pixel's transmittance as 0.  Adds closed [h,w] (closed at the list's end) and
+    closed_first [h,w] (closed by the first entry).
+    pick: adds pick [h,w] (the first entry of the largest weight alpha * T_before among the live,
+    unoccluded entries; PICK_NONE where no weight is positive), pick_weight, pick_second (the largest weight of
+    any other entry) and, for pick_query [h,w] (ids or PICK_NONE), query_weight (that id's weight; -1 where it
+    is not in the pixel's list) and query_open (it is a live, unoccluded entry of the list)."""
     tiles_x = (w + tile_w - 1) // tile_w
     color = np.empty((h, w, 3))
     color[:] = clear[:3]
@@ -396,6 +465,14 @@ def blend_lists(records, lists, tile_w, tile_h, w, h, clear, rules, on_tile=None
     depth = np.zeros((h, w))
     covered = np.zeros((h, w), bool)
     unsure = np.zeros((h, w), bool)
+    extra = {}
+    if occluder is not None:
+        extra.update(closed=np.zeros((h, w), bool), closed_first=np.zeros((h, w), bool))
+    if pick:
+        extra.update(pick=np.full((h, w), PICK_NONE, np.int64), pick_weight=np.zeros((h, w)),
+                     pick_second=np.zeros((h, w)))
+        if pick_query is not None:
+            extra.update(query_weight=np.full((h, w), -1.0), query_open=np.zeros((h, w), bool))
     gw, gh = rules["group"]
     for tile, ids in lists:
         ids = np.asarray(ids, np.int64)
@@ -407,49 +484,107 @@ def blend_lists(records, lists, tile_w, tile_h, w, h, clear, rules, on_tile=None
             continue
         # the shaders form pixel coordinates in half precision
         a = _alphas(records, ids, round_h(xs), round_h(ys), rules["alpha_max"], rules.get("r2_max"))
+        inside = (xs < w) & (ys < h)
+        shut = None
+        if occluder is not None:
+            shut, closed_before = occlusion(occluder_limits(occluder, xs, ys, w, h), records["depth"][ids],
+                                            occlusion_form)
+            a = np.where(shut, 0.0, a)
         T_before = np.ones_like(a)
         np.cumprod(1.0 - a[:-1], axis=0, out=T_before[1:])
+        T_seen = T_before if shut is None else np.where(closed_before, 0.0, T_before)
         group = ((ys - y0) // gh) * (tile_w // gw) + (xs - x0) // gw
         gmax = np.zeros((len(ids), group.max() + 1))
         for g in range(group.max() + 1):  # pixels outside the frame vote too, as the shader's lanes do
-            gmax[:, g] = T_before[:, group == g].max(1)
+            gmax[:, g] = T_seen[:, group == g].max(1)
         live = (gmax >= rules["break_below"])[:, group]
+        if shut is not None and occlusion_form != "sticky":
+            live = np.logical_and.accumulate(live, axis=0)  # a walk that has stopped does not start again
         # T is non-increasing, so `live` is a prefix of the list; entries past it do not change T
         if on_tile is not None:
             on_tile(tile, ids, xs, ys, a, live)
         rgb, al, dep, uns = _composite(records, ids, a, live, rules)
-        inside = (xs < w) & (ys < h)
         color[ys[inside], xs[inside]] = rgb[inside]
         alpha[ys[inside], xs[inside]] = al[inside]
         depth[ys[inside], xs[inside]] = dep[inside]
         unsure[ys[inside], xs[inside]] = uns[inside]
-    return dict(color=color, alpha=alpha, depth=depth, covered=covered, depth_unsure=unsure)
+        if shut is not None:
+            extra["closed"][ys[inside], xs[inside]] = shut[-1][inside]
+            extra["closed_first"][ys[inside], xs[inside]] = shut[0][inside]
+        if pick:
+            wgt = np.where(live, a, 0.0) * T_before
+            q = None if pick_query is None else np.where(inside, pick_query[np.minimum(ys, h - 1),
+                                                                            np.minimum(xs, w - 1)], PICK_NONE)
+            res = _pick(ids, wgt, q)
+            for key in ("pick", "pick_weight", "pick_second"):
+                extra[key][ys[inside], xs[inside]] = res[key][inside]
+            if q is not None:
+                extra["query_weight"][ys[inside], xs[inside]] = res["query_weight"][inside]
+                ok = live if shut is None else live & ~shut
+                extra["query_open"][ys[inside], xs[inside]] = (res["query_in"] & ok[res["query_at"],
+                                                                                    np.arange(len(xs))])[inside]
+    return dict(color=color, alpha=alpha, depth=depth, covered=covered, depth_unsure=unsure, **extra)
 
 
-def blend_untiled(records, order, w, h, clear, rules=GLOBAL_RULES, rows=8) -> dict:
+def blend_untiled(records, order, w, h, clear, rules=GLOBAL_RULES, rows=8, occluder=None, pick=False,
+                  occlusion_form="sticky", surface_doubt=None) -> dict:
     """Every gaussian of `order` applied to every pixel, front to back in that order: no tiles, no
     rectangles, no saturation break.  `clear` fills the frame only when `order` is empty (a frame nothing
-    was drawn into); compare drawn frames over the tiles that were active."""
+    was drawn into); compare drawn frames over the tiles that were active.
+    occluder, pick, occlusion_form: as for blend_lists, every entry being live (closed, closed_first, pick,
+    pick_weight, pick_second).  Every gaussian of the frame is an entry here, so 'closed' says little; of the
+    entries whose alpha at the pixel is 1/255 or more, cut_any [h,w] says that one is shut, cut_first that the
+    first is, and drawn_any that one is not.  surface_doubt = (depths [n], eps): adds at_surface [h,w], the
+    pixels on which a gaussian of alpha >= 1e-3 has such a depth within eps (relative) of the pixel's Z."""
     order = np.asarray(order, np.int64)
     color = np.zeros((h, w, 3))
     alpha = np.zeros((h, w))
     depth = np.zeros((h, w))
     unsure = np.zeros((h, w), bool)
+    extra = {}
+    if occluder is not None:
+        extra.update({k: np.zeros((h, w), bool) for k in ("closed", "closed_first", "at_surface", "cut_any",
+                                                          "cut_first", "drawn_any")})
+    if pick:
+        extra.update(pick=np.full((h, w), PICK_NONE, np.int64), pick_weight=np.zeros((h, w)),
+                     pick_second=np.zeros((h, w)))
     if len(order) == 0:
         color[:] = clear[:3]
         alpha[:] = clear[3]
-        return dict(color=color, alpha=alpha, depth=depth, depth_unsure=unsure)
+        return dict(color=color, alpha=alpha, depth=depth, depth_unsure=unsure, **extra)
     for y0 in range(0, h, rows):
         ys, xs = np.mgrid[y0:min(y0 + rows, h), 0:w]
         shp = xs.shape
         xs, ys = xs.reshape(-1), ys.reshape(-1)
         a = _alphas(records, order, round_h(xs), round_h(ys), rules["alpha_max"])
+        if occluder is not None:
+            Z = occluder_limits(occluder, xs, ys, w, h)
+            if surface_doubt is not None:
+                d = np.asarray(surface_doubt[0], np.float64)[order][:, None]
+                with np.errstate(invalid="ignore"):
+                    near = (np.abs(d - Z[None, :]) <= surface_doubt[1] * np.abs(d)) & (a >= 1e-3)
+                extra["at_surface"][y0:y0 + shp[0]] = near.any(0).reshape(shp)
+            shut, _ = occlusion(Z, records["depth"][order], occlusion_form)
+            seen = a >= 1.0 / 255.0
+            first = np.argmax(seen, axis=0)
+            extra["cut_any"][y0:y0 + shp[0]] = (seen & shut).any(0).reshape(shp)
+            extra["drawn_any"][y0:y0 + shp[0]] = (seen & ~shut).any(0).reshape(shp)
+            extra["cut_first"][y0:y0 + shp[0]] = (seen.any(0) & shut[first, np.arange(len(xs))]).reshape(shp)
+            a = np.where(shut, 0.0, a)
+            extra["closed"][y0:y0 + shp[0]] = shut[-1].reshape(shp)
+            extra["closed_first"][y0:y0 + shp[0]] = shut[0].reshape(shp)
         rgb, al, dep, uns = _composite(records, order, a, np.ones(a.shape, bool), rules)
         color[y0:y0 + shp[0]] = rgb.reshape(shp + (3,))
         alpha[y0:y0 + shp[0]] = al.reshape(shp)
         depth[y0:y0 + shp[0]] = dep.reshape(shp)
         unsure[y0:y0 + shp[0]] = uns.reshape(shp)
-    return dict(color=color, alpha=alpha, depth=depth, depth_unsure=unsure)
+        if pick:
+            T_before = np.ones_like(a)
+            np.cumprod(1.0 - a[:-1], axis=0, out=T_before[1:])
+            res = _pick(order, a * T_before)
+            for key in ("pick", "pick_weight", "pick_second"):
+                extra[key][y0:y0 + shp[0]] = res[key].reshape(shp)
+    return dict(color=color, alpha=alpha, depth=depth, depth_unsure=unsure, **extra)
 
 
 def lists_from_headers(headers, sorted_values):
@@ -460,3 +595,145 @@ def lists_from_headers(headers, sorted_values):
 def lists_from_local(tile_counts, tile_lists, max_per_tile=2048):
     return [(t, np.asarray(tile_lists[t, :min(c, max_per_tile)])) for t, c in enumerate(np.asarray(tile_counts).tolist())
             if c]
+
+
+# ---------------------------------------------------------------------------------------------------
+# the composite of posed scenes
+# ---------------------------------------------------------------------------------------------------
+ITEM_BLOCK = 256  # object o's items start at 256 * B_o, B_o = the blocks of the objects before it
+
+
+def item_layout(counts):
+    """(first item of every object, items in all): B_o = sum over u < o of ceil(count_u / 256)."""
+    blocks = [(int(c) + ITEM_BLOCK - 1) // ITEM_BLOCK for c in counts]
+    base = ITEM_BLOCK * np.concatenate([[0], np.cumsum(blocks)]).astype(np.int64)
+    return base[:-1], int(base[-1])
+
+
+def project_composite(objects, sh_components, cam, w, h, color_space=0):
+    """objects: [(world, harmonics, model matrix (column-major flat 4x4) or None)], all seen by the frame camera
+    `cam`.  Each object is projected from its model matrix (project(..., scene_transform=M, pose=True)) and the
+    projections are laid out by item.  Returns (projection over all items -- entries that belong to no gaussian
+    are not visible and hold NaN --, visible [items], owner [items, 2] = (object, gaussian), -1 for no owner)."""
+    counts = [len(o[0]) for o in objects]
+    base, items = item_layout(counts)
+    owner = np.full((items, 2), -1, np.int64)
+    out = None
+    for o, (world, harm, model) in enumerate(objects):
+        if len(world) == 0:
+            continue
+        pr = project(world, harm, sh_components, cam, w, h, color_space, scene_transform=model,
+                     pose=model is not None)
+        if out is None:
+            out = {}
+            for k, v in pr.items():
+                if k == "margins":
+                    out[k] = {m: np.full(items, -np.inf) for m in v}
+                else:
+                    fill = False if v.dtype == bool else (-np.inf if k == "margin" else np.nan)
+                    out[k] = np.full((items,) + v.shape[1:], fill, v.dtype)
+        sl = slice(int(base[o]), int(base[o]) + len(world))
+        for k, v in pr.items():
+            if k == "margins":
+                for m in v:
+                    out[k][m][sl] = v[m]
+            else:
+                out[k][sl] = v
+        owner[sl, 0], owner[sl, 1] = o, np.arange(len(world))
+    return out, out["visible"].copy(), owner
+
+
+# ---------------------------------------------------------------------------------------------------
+# styles and the selects (DESIGN.md 22, 24)
+# ---------------------------------------------------------------------------------------------------
+# a style: (tint r, g, b, tint amount k, opacity scale s, hidden), all bytes
+IDENTITY_STYLE = (0, 0, 0, 0, 255, 0)
+
+
+def styles_of(states, styles, style_count=None):
+    """[n, 6] int64: every gaussian's style; states at or above style_count take the identity."""
+    table = np.asarray(list(styles), np.int64).reshape(-1, 6)
+    count = len(table) if style_count is None else int(style_count)
+    states = np.asarray(states, np.int64)
+    out = np.tile(np.asarray(IDENTITY_STYLE, np.int64), (len(states), 1))
+    known = states < count
+    out[known] = table[states[known]]
+    return out
+
+
+def apply_styles(pr, states, styles, style_count=None):
+    """A projection under a style table (rows of six bytes as IDENTITY_STYLE) and one state byte per entry.
+    Hidden gaussians leave the visible set (margin 'style').  Each colour byte becomes
+    (c (255 - k) + t k + 127) // 255 and the opacity byte (o s + 127) // 255, on the truncated bytes of
+    quantise_global; 'color' and 'opacity' of the result hold byte / 255, 'styled_bytes' [n, 4] the bytes
+    (r, g, b, opacity) themselves, 'plain_color' and 'plain_opacity' the values before the style.  A gaussian whose styled opacity byte is 0 stays visible ('no_tiles')."""
+    st = styles_of(states, styles, style_count)
+    hidden = st[:, 5] != 0
+    byte = lambda v: np.floor(np.clip(np.nan_to_num(v) * 255.0, 0.0, 255.0)).astype(np.int64)
+    c, o = byte(pr["color"]), byte(pr["opacity"])
+    k = st[:, 3:4]
+    c2 = (c * (255 - k) + st[:, 0:3] * k + 127) // 255
+    o2 = (o * st[:, 4] + 127) // 255
+    out = dict(pr)
+    out["margins"] = dict(pr["margins"], style=np.where(hidden, -np.inf, np.inf))
+    out["margin"] = np.where(hidden, -np.inf, pr["margin"])
+    out["visible"] = pr["visible"] & ~hidden
+    out["styled_bytes"] = np.concatenate([c2, o2[:, None]], 1)
+    out["plain_color"], out["plain_opacity"] = pr["color"], pr["opacity"]
+    out["color"], out["opacity"] = c2 / 255.0, o2 / 255.0
+    out["no_tiles"] = out["visible"] & (o2 == 0)
+    return out
+
+
+def quantise_styled(spr) -> dict:
+    """quantise_global of a styled projection: the colour and opacity bytes are already whole."""
+    q = quantise_global(spr)
+    q["color"], q["opacity"] = spr["styled_bytes"][:, :3] / 255.0, spr["styled_bytes"][:, 3] / 255.0
+    return q
+
+
+def _update(states, match, and_mask, xor_mask):
+    out = np.asarray(states, np.uint8).copy()
+    out[match] = ((out[match].astype(np.int64) & (and_mask & 0xFFFFFFFF)) ^ (xor_mask & 0xFFFFFFFF)) & 0xFF
+    return out
+
+
+def select_mask(pr, states, mask, w, h, and_mask, xor_mask, styles=None, style_count=None, eps=0.0):
+    """gsm_global_select_mask on a model projection: a gaussian matches when it is visible, its current style is
+    not hidden, its fp16 mean is finite and floor(mean + 0.5) names a pixel of the frame whose mask byte is
+    nonzero.  Returns (new states, matches, in doubt [n]): in doubt is a visible gaussian whose mean lies within
+    eps of a rounding boundary of its fp16 value or of a k + 0.5 (the pixel could be the neighbour)."""
+    states = np.asarray(states, np.uint8)
+    match = pr["visible"].copy()
+    if styles is not None:
+        match &= styles_of(states, styles, style_count)[:, 5] == 0
+    with np.errstate(invalid="ignore", over="ignore"):
+        m16 = round_h(pr["mean"])
+        match &= np.isfinite(m16).all(1)
+        px = np.floor(m16 + 0.5)
+        inside = (px[:, 0] >= 0) & (px[:, 0] < w) & (px[:, 1] >= 0) & (px[:, 1] < h)
+        match &= inside
+        ix = np.where(match, px[:, 0], 0).astype(np.int64)
+        iy = np.where(match, px[:, 1], 0).astype(np.int64)
+        match &= np.asarray(mask)[iy, ix] != 0
+        m = pr["mean"]
+        f = np.mod(m + 0.5, 1.0)
+        doubt = (np.abs(np.abs(m - m16) - 0.5 * h_ulp(m)) < eps) | (np.minimum(f, 1.0 - f) < eps)
+        doubt = doubt.any(1) & np.isfinite(m).all(1)
+    return _update(states, match, and_mask, xor_mask), int(match.sum()), doubt
+
+
+def select_pick(items, counts, obj, states, gaussian_count, and_mask, xor_mask, mask=None):
+    """gsm_global_select_pick from its rule: with object o's items at
+    [256 B_o, 256 B_o + count_o), S is the set of ids item - 256 B_o of the pixels under the mask (None: every
+    pixel) that lie below min(count_o, gaussian_count); every id of S is updated once.  The rule reads an image,
+    not the scene, so nothing of it is in doubt: returns (new states, |S|, in doubt = all False)."""
+    base, _ = item_layout(counts)
+    items = np.asarray(items).astype(np.int64)
+    hh, ww = items.shape
+    under = np.ones((hh, ww), bool) if mask is None else np.asarray(mask)[:hh, :ww] != 0
+    ids = items[under] - int(base[obj])
+    ids = np.unique(ids[(ids >= 0) & (ids < min(int(counts[obj]), int(gaussian_count)))])
+    match = np.zeros(len(states), bool)
+    match[ids] = True
+    return _update(states, match, and_mask, xor_mask), int(len(ids)), np.zeros(len(states), bool)

@@ -185,6 +185,14 @@ def measure_records(pr, view, w, h):
         step += dtheta * np.abs(i2 - i1)
         out["conic"] = ((dc.max(1) - step) / i2).max()
         trunc = lambda got, want: np.maximum(got - want, want - 1.0 / 255.0 - got).max()  # got in (want - 1/255, want]
+        if "styled_bytes" in pr:
+            # a styled projection (M.apply_styles) holds whole bytes: equal, except where the byte the style
+            # started from is in doubt (the plain value within float32's reach of a truncation boundary)
+            sure = ~_u8_doubt(pr["plain_color"][g], BOUNDARY_EPS["color"]).any(1)
+            out["color"] = np.abs(r["color"] - pr["color"][g])[sure].max(initial=0.0)
+            sure = ~_u8_doubt(pr["plain_opacity"][g], BOUNDARY_EPS["opacity"])
+            out["opacity"] = np.abs(r["opacity"] - pr["opacity"][g])[sure].max(initial=0.0)
+            return out
         out["color"] = trunc(r["color"], np.minimum(pr["color"][g], 1.0))
         out["opacity"] = trunc(r["opacity"], np.minimum(pr["opacity"][g], 1.0))
     else:
@@ -205,8 +213,10 @@ def check_records(pr, view, w, h):
         assert v <= RECORD_TOL[view["kind"]][k], (k, v, RECORD_TOL[view["kind"]][k])
 
 
-def check_order(pr, view):
-    """Each list ascends in (fp16(model depth) ^ 0x8000, id).  A model depth within 2^-20 relative of a
+def check_order(pr, view, owner=None):
+    """Each list ascends in (fp16(model depth) ^ 0x8000, id).  For a composite the ids are items, which ascend
+    by object and then by gaussian -- the composite's tie rule; owner [items, 2] (M.project_composite) names the
+    (object, gaussian) pairs in the message.  A model depth within 2^-20 relative of a
     rounding boundary (float32 evaluates clip w to about 2^-23) may round either way: such a gaussian is
     left out and the sequence is judged by the others."""
     d = pr["depth"]
@@ -220,7 +230,9 @@ def check_order(pr, view):
         g = g[~unsure[g]]
         k = key[g] * (1 << 32) + g
         bad = np.nonzero(k[1:] <= k[:-1])[0]
-        assert bad.size == 0, f"tile {tile}: entries {bad[:3].tolist()} out of order, ids {g[bad[:3]].tolist()}"
+        assert bad.size == 0, (f"tile {tile}: entries {bad[:3].tolist()} out of order, ids {g[bad[:3]].tolist()}"
+                               + ("" if owner is None else f", (object, gaussian) {owner[g[bad[:3]]].tolist()} before "
+                                  f"{owner[g[bad[:3] + 1]].tolist()}"))
         worst = max(worst, len(lst))
     print(f"order: {len(view['lists'])} lists, deepest {worst}, {int(unsure.sum())} gaussians at a rounding boundary")
 
@@ -234,15 +246,22 @@ def _diffs(view, model, where):
     return float(rgb), float(al), float(dep)
 
 
-def measure_lists(view, w, h, lists=None):
+def measure_lists(view, w, h, lists=None, occluder=None):
     tw, th = view["rules"]["tile"]
     lists = view["lists"] if lists is None else lists
-    m = M.blend_lists(view["rec"], lists, tw, th, w, h, view["clear"], view["rules"])
+    m = M.blend_lists(view["rec"], lists, tw, th, w, h, view["clear"], view["rules"], occluder=occluder)
     if len(lists) == len(view["lists"]):  # the whole frame: the clear value outside the lists too
         where = np.ones((h, w), bool)
     else:
         where = m["covered"]
     return _diffs(view, m, where)
+
+
+def _u8_doubt(v, eps):
+    """v * 255 within eps * 255 of a whole number: the truncated byte may be the neighbour."""
+    with np.errstate(invalid="ignore"):
+        f = np.mod(np.clip(v, 0.0, 1.0) * 255.0, 1.0)
+        return (np.minimum(f, 1.0 - f) / 255.0 < eps) & (v < 1.0 + eps)
 
 
 def at_rounding_boundary(pr, kind, w, h):
@@ -257,15 +276,16 @@ def at_rounding_boundary(pr, kind, w, h):
     def fp16(v, eps):
         return np.abs(np.abs(v - M.round_h(v)) - 0.5 * M.h_ulp(v)) < eps
 
-    def u8(v, eps):
-        f = np.mod(np.clip(v, 0.0, 1.0) * 255.0, 1.0)
-        return (np.minimum(f, 1.0 - f) / 255.0 < eps) & (v < 1.0 + eps)
+    u8 = _u8_doubt
     with np.errstate(invalid="ignore"):
         near = fp16(pr["mean"], tol["mean"] * max(w, h)).any(1) | fp16(pr["depth"], tol["depth"] * np.abs(pr["depth"]))
         if kind == "global":
+            # (a styled projection is judged by the values its bytes started from: the styled byte of a plain
+            # byte in doubt is in doubt)
+            col, opa = pr.get("plain_color", pr["color"]), pr.get("plain_opacity", pr["opacity"])
             # an opacity whose 255-fold is a whole number (1.0) is exact in float32 too: no doubt there
-            near |= u8(pr["color"], tol["color"]).any(1) | \
-                (u8(pr["opacity"], tol["opacity"]) & (np.mod(pr["opacity"] * 255.0, 1.0) != 0.0))
+            near |= u8(col, tol["color"]).any(1) | \
+                (u8(opa, tol["opacity"]) & (np.mod(opa * 255.0, 1.0) != 0.0))
         else:
             near |= fp16(pr["color"], tol["color"]).any(1) | fp16(pr["opacity"], tol["opacity"])
     return near & pr["visible"]
@@ -278,13 +298,23 @@ BOUNDARY_EPS = dict(mean=1e-7, depth=2.0 ** -22, color=2.0 ** -21, opacity=2.0 *
 MAX_PIXELS_LEFT_OUT = 0.25  # the densest scene (3000 gaussians on 128x64) leaves out 17%
 
 
-def measure_frame(pr, view, w, h):
+def measure_frame(pr, view, w, h, occluder=None, model_out=None):
     """The model alone: projection, record quantisation, one global order, every gaussian on every pixel;
     compared over the tiles the implementation drew, less the pixels on which a gaussian at a rounding
-    boundary has an alpha of 1e-3 or more (what it can change elsewhere is below 1e-3 of a neighbour's alpha)."""
-    q = M.quantise_global(pr) if view["kind"] == "global" else M.quantise_local(pr)
+    boundary has an alpha of 1e-3 or more (what it can change elsewhere is below 1e-3 of a neighbour's alpha).
+    Under an occluder, also less the pixels on which a gaussian of alpha >= 1e-3 has a model depth within
+    BOUNDARY_EPS['depth'] (relative) of the pixel's Z.  A styled projection (M.apply_styles) is quantised with
+    its bytes.  model_out: a dict that receives the model's frame and the pixels compared ('where')."""
+    if view["kind"] != "global":
+        q = M.quantise_local(pr)
+    else:
+        q = M.quantise_styled(pr) if "styled_bytes" in pr else M.quantise_global(pr)
     vis = np.nonzero(pr["visible"])[0]
-    m = M.blend_untiled(q, M.depth_order(q["depth"], vis), w, h, view["clear"], view["rules"])
+    if occluder is None:
+        m = M.blend_untiled(q, M.depth_order(q["depth"], vis), w, h, view["clear"], view["rules"])
+    else:
+        m = M.blend_untiled(q, M.depth_order(q["depth"], vis), w, h, view["clear"], view["rules"],
+                            occluder=occluder, surface_doubt=(pr["depth"], BOUNDARY_EPS["depth"]))
     tw, th = view["rules"]["tile"]
     tiles_x = (w + tw - 1) // tw
     drawn = np.zeros((h, w), bool)
@@ -297,6 +327,10 @@ def measure_frame(pr, view, w, h):
     if flip.size:
         a = M._alphas(q, flip, xs.reshape(-1).astype(float), ys.reshape(-1).astype(float), 1.0)
         unsure = (a >= 1e-3).any(0).reshape(h, w)
+    if occluder is not None:
+        unsure |= m["at_surface"]
+    if model_out is not None:
+        model_out.update(m, where=drawn & ~unsure)
     share = float((unsure & drawn).sum()) / max(int(drawn.sum()), 1)
     print(f"whole frame: {flip.size} gaussians at a rounding boundary, {share:.2%} of the drawn pixels left out")
     assert share <= MAX_PIXELS_LEFT_OUT, share
