@@ -190,8 +190,18 @@ gsm_status gsm_global_select_mask(gsm_renderer* r, void* stream, const gsm_gauss
                                style_count, and_mask, xor_mask, matched);
 }
 
+gsm_status gsm_global_select_mask_ortho(gsm_renderer* r, void* stream, const gsm_gaussian_input* input,
+                                        const gsm_camera_params* camera, uint32_t width, uint32_t height,
+                                        const void* mask, size_t mask_pitch, uint8_t* state,
+                                        const gsm_global_style* styles, uint32_t style_count, uint32_t and_mask,
+                                        uint32_t xor_mask, uint32_t* matched) {
+    if (!r || !r->impl) return GSM_ERR_INVALID_ARGUMENT;
+    return r->impl->selectMask((hipStream_t)stream, input, camera, width, height, mask, mask_pitch, state, styles,
+                               style_count, and_mask, xor_mask, matched, true);
+}
+
 gsm_status gsm_global_render_frame(gsm_renderer* r, void* stream, const gsm_global_frame* f) {
-    if (!r || !r->impl || !f || f->flags != 0) return GSM_ERR_INVALID_ARGUMENT;
+    if (!r || !r->impl || !f || (f->flags & ~GSM_FRAME_ORTHOGRAPHIC)) return GSM_ERR_INVALID_ARGUMENT;
     const gsm::PickTarget pt{f->pick_r32u, f->pick_pitch_bytes};
     const gsm::OccluderSource os{f->occluder_r32f, f->occluder_pitch_bytes};
     const gsm::StyleSource ss{f->states, f->styles, f->style_count};
@@ -199,6 +209,7 @@ gsm_status gsm_global_render_frame(gsm_renderer* r, void* stream, const gsm_glob
     extras.pick = f->pick_r32u ? &pt : nullptr;
     extras.occluder = f->occluder_r32f ? &os : nullptr;
     extras.style = (f->states || f->styles) ? &ss : nullptr;  // (one without the other: the styled row refuses)
+    extras.orthographic = (f->flags & GSM_FRAME_ORTHOGRAPHIC) != 0;
     const gsm::FrameTargets targets{f->color, f->color_pitch_bytes, f->depth_r16f, f->depth_pitch_bytes};
     if (f->object_count == 1 && f->objects)  // one object: the single frame
         return r->impl->renderFrame((hipStream_t)stream, f->objects[0].input, f->objects[0].camera, f->width,

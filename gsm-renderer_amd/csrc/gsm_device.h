@@ -206,10 +206,14 @@ __device__ __forceinline__ float mul_h_hi(uint32_t w, float b) {
 
 // computeSHColor (GaussianShared.h:38-116) specialised by degree like the
 // SH_DEGREE function constant (GlobalProjectCullEncoder.swift:19-45).
+// uniformDir (an orthographic frame; a compile-time constant in every caller but the mixed batch's,
+// where it is uniform over the block): all rays are parallel, so `cam` holds the unit direction itself -- normalised
+// once per camera on the host by the same sequence -- and neither the difference, the square root nor the divisions
+// run per gaussian; `pos` is not read.
 template <bool HALF, int DEG>
 __device__ __forceinline__ void sh_color(const void* __restrict__ harm, uint32_t gid,
                                          const float pos[3], const float cam[3], uint32_t shk,
-                                         float col[3]) {
+                                         float col[3], bool uniformDir = false) {
     if (DEG == 0 || shk == 0) {
         const size_t base = (size_t)gid * 3u;
         col[0] = load_harm<HALF>(harm, base) * SH_C0;
@@ -218,12 +222,17 @@ __device__ __forceinline__ void sh_color(const void* __restrict__ harm, uint32_t
         return;
     }
     constexpr int K = DEG == 1 ? 4 : (DEG == 2 ? 9 : 16);
-    float d0 = cam[0] - pos[0], d1 = cam[1] - pos[1], d2 = cam[2] - pos[2];
-    float dd = d0 * d0 + d1 * d1;
-    dd = dd + d2 * d2;
-    float n = __builtin_sqrtf(dd);
-    float dn3[3] = {d0, d1, d2};
-    div_many(dn3, n);  // d / n, each correctly rounded
+    float dn3[3] = {cam[0], cam[1], cam[2]};
+    if (!uniformDir) {
+        float d0 = cam[0] - pos[0], d1 = cam[1] - pos[1], d2 = cam[2] - pos[2];
+        float dd = d0 * d0 + d1 * d1;
+        dd = dd + d2 * d2;
+        float n = __builtin_sqrtf(dd);
+        dn3[0] = d0;
+        dn3[1] = d1;
+        dn3[2] = d2;
+        div_many(dn3, n);  // d / n, each correctly rounded
+    }
     float x = dn3[0], y = dn3[1], z = dn3[2];
     float xx = x * x, yy = y * y, zz = z * z;
     float xy = x * y, yz = y * z, xz = x * z;
@@ -357,6 +366,36 @@ __device__ __forceinline__ Cov2 project_cov2d(const M3& C3, const float vp[3], c
     J.m[2][0] = -focalX * xCl * signZ * invAbsZ2;
     J.m[2][1] = -focalY * yCl * signZ * invAbsZ2;
     J.m[2][2] = 0.0f;
+    M3 T = m3_mul(J, W);
+    M3 M1 = m3_mul(T, C3);
+    M3 Tt;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int rr = 0; rr < 3; ++rr) Tt.m[c][rr] = T.m[rr][c];
+    M3 F = m3_mul(M1, Tt);
+    Cov2 cov;
+    cov.a = F.m[0][0] + 0.3f;
+    cov.b = F.m[0][1];
+    cov.c = F.m[1][0];
+    cov.d = F.m[1][1] + 0.3f;
+    return cov;
+}
+
+// The orthographic frame's projectCovariance2D: the Jacobian of an affine projection is the same for
+// every gaussian -- J = diag(j00, j11) with j00 = W * proj[0] * 0.5f, j11 = H * proj[5] * 0.5f, the signed entries,
+// formed on the host -- so there is no reciprocal of the depth, no tan clamp and no third column.  T = J W, T C3 T^T
+// and the + 0.3f are project_cov2d's own m3_mul sequence with that J: the same operations in the same order.
+__device__ __forceinline__ Cov2 project_cov2d_ortho(const M3& C3, const float* view, float j00, float j11) {
+    M3 W;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int rr = 0; rr < 3; ++rr) W.m[c][rr] = view[c * 4 + rr];
+    M3 J;
+    J.m[0][0] = j00; J.m[0][1] = 0.0f; J.m[0][2] = 0.0f;
+    J.m[1][0] = 0.0f; J.m[1][1] = j11; J.m[1][2] = 0.0f;
+    J.m[2][0] = 0.0f; J.m[2][1] = 0.0f; J.m[2][2] = 0.0f;
     M3 T = m3_mul(J, W);
     M3 M1 = m3_mul(T, C3);
     M3 Tt;

@@ -30,6 +30,10 @@ struct ProjectArgs {
     // per-frame constants of projectCovariance2D / stabilizeCovariance2D / computeDepthFactor,
     // evaluated once on the host with the same IEEE fp32 operations the kernels would repeat
     // per gaussian (GaussianShared.h:326-375, 655-714, 275-278)
+    // An orthographic frame (GSM_FRAME_ORTHOGRAPHIC; frameArgs) sends its uniforms in the same fields,
+    // here and in ComposeObjectArgs / BatchViewArgs: limX = sigma (+1 when proj[10] >= 0, else -1), limY = 0,
+    // focalX = J[0][0] = W * proj[0] * 0.5f, focalY = J[1][1] = H * proj[5] * 0.5f (signed), and cam.cameraCenter =
+    // normalize3(-sigma * (view[2], view[6], view[10])), the uniform SH direction; maxEig, adjFar, adjDen as above.
     float limX, limY, focalX, focalY, maxEig, adjFar, adjDen;
 };
 
@@ -75,7 +79,8 @@ struct BatchViewArgs {
     float limX, limY, focalX, focalY, maxEig, adjFar, adjDen;
     uint32_t count;      // gaussians of this view's scene
     TileBinningParams bin;  // on the view's own tile grid
-    uint32_t blockBase, pad0;
+    uint32_t blockBase;
+    uint32_t ortho;  // nonzero: the view is orthographic (read by k_project_batch_ortho(_styled) only)
     const void* world;
     const void* harm;
     BatchTarget tg;
@@ -428,8 +433,12 @@ constexpr size_t kSortTotalsWords = kWideBins;
 inline SortSpace sort_space(const DeviceArena& A) { return SortSpace{A.radixHist, A.radixHistBytes, A.radixBinTotals, kSortTotalsWords}; }
 
 // project + cull + SH + tile count + per-block count sums (GlobalShaders.metal:19-123, 563-616)
+// ortho / anyOrtho (every projection launcher below but the views'): the orthographic instances --
+// k_project_ortho and its styled / compose forms for a frame whose flag is set (args and the compose entries then
+// carry the orthographic uniforms, see ProjectArgs), k_project_batch_ortho(_styled) for a batch in which some view's
+// `ortho` word is set.  false launches the kernels the frame launched before the flag existed.
 void launch_project(bool halfInput, uint32_t shDegree, const void* world, const void* harmonics,
-                    const ProjectArgs& args, const DeviceArena& A, hipStream_t stream);
+                    const ProjectArgs& args, const DeviceArena& A, hipStream_t stream, bool ortho = false);
 // the same for a batch of views (k_project_views): args.count gaussians per view, vb.views views; entries
 // [first, first + n) of the device array filled from `chunk` by launch_fill_views (n <= kViewChunk)
 void launch_project_views(bool halfInput, uint32_t shDegree, const void* world, const void* harmonics,
@@ -441,7 +450,7 @@ void launch_fill_views(const ViewChunk& chunk, uint32_t first, uint32_t n, ViewA
 // `chunk` (n <= kBatchChunk) and those views' ranges of the block and tile tables (at most maxBlocks / maxTiles
 // entries of either table are written, whatever the entries say).
 void launch_project_batch(bool halfInput, uint32_t shDegree, const ProjectArgs& args, const BatchFrame& bf,
-                          const DeviceArena& A, hipStream_t stream);
+                          const DeviceArena& A, hipStream_t stream, bool anyOrtho = false);
 void launch_fill_batch(const BatchChunk& chunk, uint32_t first, uint32_t n, BatchViewArgs* dst, uint16_t* blockView,
                        uint32_t maxBlocks, uint16_t* tileView, uint32_t maxTiles, hipStream_t stream);
 // a batch with options (gsm_global_render_frames): launch_fill_batch_extras writes entries [first,
@@ -450,23 +459,26 @@ void launch_fill_batch(const BatchChunk& chunk, uint32_t first, uint32_t n, Batc
 void launch_fill_batch_extras(const ExtrasChunk& chunk, uint32_t first, uint32_t n, BatchExtras* dst,
                               hipStream_t stream);
 void launch_project_batch_styled(bool halfInput, uint32_t shDegree, const ProjectArgs& args, const BatchFrame& bf,
-                                 const uint2* styleTable, const DeviceArena& A, hipStream_t stream);
+                                 const uint2* styleTable, const DeviceArena& A, hipStream_t stream,
+                                 bool anyOrtho = false);
 // several posed objects on the frame's own tile grid (k_project_compose): every block's scene,
 // count and camera terms come from its object's entry; `args` holds the frame's (the grid, the rows, the
 // thresholds, the capacity, the schedule).  launch_fill_compose writes entries [first, first + n) of the device
 // array from `chunk` (n <= kComposeChunk) and those objects' ranges of the block table (at most maxBlocks
 // entries of it are written, whatever the entries say).
 void launch_project_compose(bool halfInput, uint32_t shDegree, const ProjectArgs& args, const ComposeFrame& cf,
-                            const DeviceArena& A, hipStream_t stream);
+                            const DeviceArena& A, hipStream_t stream, bool ortho = false);
 void launch_fill_compose(const ComposeChunk& chunk, uint32_t first, uint32_t n, ComposeObjectArgs* dst,
                          uint16_t* blockObject, uint32_t maxBlocks, hipStream_t stream);
 // the styled frames (k_project_styled, k_project_compose_styled): the projections above with the
 // style of every gaussian's state byte applied where its four u8 bytes are formed; a composite's state pointers
 // travel in its entries.  launch_fill_styles writes the 256-entry table from `chunk`.
 void launch_project_styled(bool halfInput, uint32_t shDegree, const void* world, const void* harmonics,
-                           const ProjectArgs& args, const StyleArgs& style, const DeviceArena& A, hipStream_t stream);
+                           const ProjectArgs& args, const StyleArgs& style, const DeviceArena& A, hipStream_t stream,
+                           bool ortho = false);
 void launch_project_compose_styled(bool halfInput, uint32_t shDegree, const ProjectArgs& args, const ComposeFrame& cf,
-                                   const uint2* styleTable, const DeviceArena& A, hipStream_t stream);
+                                   const uint2* styleTable, const DeviceArena& A, hipStream_t stream,
+                                   bool ortho = false);
 void launch_fill_styles(const StyleChunk& chunk, uint2* dst, hipStream_t stream);
 // gsm_global_select_mask (k_select_mask): the state bytes of the gaussians whose fp16 mean lies on
 // a nonzero mask byte become (old & andMask) ^ xorMask; *matched (nullable, zeroed by the caller) counts them.
@@ -474,7 +486,7 @@ void launch_fill_styles(const StyleChunk& chunk, uint2* dst, hipStream_t stream)
 void launch_select_mask(bool halfInput, const void* world, const ProjectArgs& args, const uint8_t* mask,
                         size_t maskPitch, uint32_t width, uint32_t height, uint8_t* state, const uint2* styleTable,
                         uint32_t andMask, uint32_t xorMask, uint32_t* matched, const DeviceArena& A,
-                        hipStream_t stream);
+                        hipStream_t stream, bool ortho = false);
 // gsm_global_select_pick (k_select_pick_mark, k_select_pick_apply): the ids item - base < n of the
 // pick image's pixels under the mask (nullable: every pixel) are marked in `bitmap` (>= ceil(n / 32) words, cleared
 // here on the stream), then every marked id's state byte becomes (old & andMask) ^ xorMask, once; *matched

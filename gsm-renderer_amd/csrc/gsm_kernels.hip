@@ -68,14 +68,23 @@ __device__ __forceinline__ void fill_byte_lut(ByteLut& L, const float2* __restri
 // gaussian's state (`style`: StyleChunk's words) applied where the four u8 bytes are formed, a hidden style being
 // one more cull; kProjMean -- stop after the screen-bounds cull with only vis and the fp16 mean (rd.x) set, for
 // gsm_global_select_mask: no SH, no record, no tile rect, and the mean's bits are the frame's.
+// ORTHO: the orthographic rule, chosen at compile time beside MODE -- kOrthoOff: the perspective rule,
+// the code it was; kOrthoOn: depth is d = sigma * vp.z (P.limX carries sigma = +-1), the screen position is clip.xy
+// without a division, the covariance takes the diagonal J (P.focalX, P.focalY carry its two signed entries) and the SH
+// direction is the camera's uniform one (P.cam.cameraCenter carries it, normalised on the host): no div_many, no
+// reciprocal, no clamp; kOrthoPerView: a batch that mixes the two -- `orthoView`, uniform over the block, chooses at
+// each of the four places by a scalar branch, so the text the rules share is compiled once.
 constexpr int kProjPlain = 0, kProjStyled = 1, kProjMean = 2;
-template <bool HALF, int DEG, int MODE = kProjPlain>
+constexpr int kOrthoOff = 0, kOrthoOn = 1, kOrthoPerView = 2;
+template <bool HALF, int DEG, int MODE = kProjPlain, int ORTHO = kOrthoOff>
 __device__ __forceinline__ ProjOut project_gaussian(const void* __restrict__ world,
                                                     const void* __restrict__ harm, uint32_t gid,
                                                     const ProjectArgs& P,
                                                     const float2* __restrict__ sincos,
                                                     const ByteLut& lut, const uint4* preWorld = nullptr,
-                                                    uint2 style = make_uint2(0u, kStyleIdentityY)) {
+                                                    uint2 style = make_uint2(0u, kStyleIdentityY),
+                                                    uint32_t orthoView = 0) {
+    const bool ortho = ORTHO == kOrthoOn || (ORTHO == kOrthoPerView && orthoView != 0);  // (kOrthoOff: false)
     ProjOut o;
     o.vis = false;
     o.countable = false;
@@ -119,12 +128,16 @@ __device__ __forceinline__ ProjOut project_gaussian(const void* __restrict__ wor
             const float p4[4] = {pos[0], pos[1], pos[2], 1.0f};
             m4_mul_v(cam.view, p4, vp);
             m4_mul_v(cam.proj, vp, clip);
+            // orthographic: the depth d = sigma * vp.z (sigma = +-1: exact) takes clip.w's place everywhere below --
+            // the near cull, the ink cull's depth, the fp16 depth of the sort key and the depth target; row 3 of
+            // proj is not used
+            if (ortho) clip[3] = P.limX * vp[2];
             if (!(clip[3] > cam.nearPlane)) vis = false;  // isInFrontOfCameraClipW
         }
         float sx = 0.f, sy = 0.f;
         if (vis) {
             float ndc[2] = {clip[0], clip[1]};
-            div_many(ndc, clip[3]);  // clip / w, each correctly rounded (w > near > 0)
+            if (!ortho) div_many(ndc, clip[3]);  // clip / w, each correctly rounded (w > near > 0)
             const float ndcx = ndc[0], ndcy = ndc[1];
             sx = ((ndcx + 1.0f) * cam.width - 1.0f) * 0.5f;  // ndcToScreenCentered
             sy = ((ndcy + 1.0f) * cam.height - 1.0f) * 0.5f;
@@ -136,7 +149,8 @@ __device__ __forceinline__ ProjOut project_gaussian(const void* __restrict__ wor
             // buildCovariance3D, projectCovariance2D, stabilizeCovariance2D, covarianceToThetaSigmas
             // (GaussianShared.h:289-324, 326-375, 655-714, 446-488; gsm_device.h)
             const M3 C3 = build_cov3d(scale, rot);
-            cov = project_cov2d(C3, vp, cam.view, P.limX, P.limY, P.focalX, P.focalY);
+            if (ortho) cov = project_cov2d_ortho(C3, cam.view, P.focalX, P.focalY);
+            else cov = project_cov2d(C3, vp, cam.view, P.limX, P.limY, P.focalX, P.focalY);
             cov = stabilize_cov2d(cov, P.maxEig);
             if (!theta_sigmas(cov, &theta, &s1, &s2)) vis = false;
         }
@@ -170,7 +184,7 @@ __device__ __forceinline__ ProjOut project_gaussian(const void* __restrict__ wor
         }
         if (vis) {
             float col[3];
-            sh_color<HALF, DEG>(harm, gid, pos, cam.cameraCenter, cam.shComponents, col);
+            sh_color<HALF, DEG>(harm, gid, pos, cam.cameraCenter, cam.shComponents, col, ortho);
             col[0] = __builtin_fmaxf(col[0] + 0.5f, 0.0f);
             col[1] = __builtin_fmaxf(col[1] + 0.5f, 0.0f);
             col[2] = __builtin_fmaxf(col[2] + 0.5f, 0.0f);
@@ -347,6 +361,30 @@ __device__ __forceinline__ float2 band_of(const BlendRecordA& ra, short4 r, cons
 #include "gsm_project_body.h"
 #undef GSM_VIEWS
 #undef GSM_STYLED
+// the orthographic frames: the single frame's text, the composite's and the batch's again under
+// GSM_ORTHO, plain and styled.  A batch's instances serve a batch in which at least one view is orthographic.
+#define GSM_ORTHO 1
+#define GSM_VIEWS 0
+#include "gsm_project_body.h"
+#undef GSM_VIEWS
+#define GSM_VIEWS 2
+#include "gsm_project_body.h"
+#undef GSM_VIEWS
+#define GSM_VIEWS 3
+#include "gsm_project_body.h"
+#undef GSM_VIEWS
+#define GSM_STYLED 1
+#define GSM_VIEWS 0
+#include "gsm_project_body.h"
+#undef GSM_VIEWS
+#define GSM_VIEWS 2
+#include "gsm_project_body.h"
+#undef GSM_VIEWS
+#define GSM_VIEWS 3
+#include "gsm_project_body.h"
+#undef GSM_VIEWS
+#undef GSM_STYLED
+#undef GSM_ORTHO
 
 // entries [first, first + n) of the per-view array from a kernel argument (plain vector stores): the host's
 // copy of the cameras is consumed when the frame is enqueued, so the call needs no staging buffer that a
@@ -414,40 +452,12 @@ __global__ __launch_bounds__(kStyleEntries) void k_fill_styles(StyleChunk chunk,
     dst[threadIdx.x] = chunk.v[threadIdx.x];
 }
 
-// gsm_global_select_mask: one thread per gaussian.  project_gaussian's kProjMean mode runs the
-// frame's culls and forms the fp16 mean with the frame's own functions; the mean's pixel is looked up in the mask
-// and a matching gaussian's state byte becomes (old & andMask) ^ xorMask.  No SH, no record, no tile test; byte
-// loads and stores, one integer add per workgroup for the count (*matched: zeroed by the launcher).
-template <bool HALF>
-__global__ __launch_bounds__(kProjectBlock) void k_select_mask(
-    const void* __restrict__ world, ProjectArgs P, const float2* __restrict__ sincos,
-    const uint8_t* __restrict__ mask, size_t maskPitch, uint32_t width, uint32_t height, uint8_t* __restrict__ state,
-    const uint2* __restrict__ styleTable, uint32_t andMask, uint32_t xorMask, uint32_t* __restrict__ matched) {
-    __shared__ uint32_t lds[kProjectBlock / 64];
-    __shared__ ByteLut lut;  // (kProjMean reads no entry of it)
-    const uint32_t gid = blockIdx.x * kProjectBlock + threadIdx.x;
-    uint32_t hit = 0;
-    if (gid < P.count) {
-        const ProjOut o = project_gaussian<HALF, 0, kProjMean>(world, nullptr, gid, P, sincos, lut);
-        const uint32_t old = state[gid];
-        bool match = o.vis;
-        if (styleTable && ((styleTable[old].y >> 8) & 0xFFu)) match = false;  // hidden: not selectable
-        const uint16_t hmx = (uint16_t)(o.rd.x & 0xFFFFu), hmy = (uint16_t)(o.rd.x >> 16);
-        if ((hmx & 0x7C00u) == 0x7C00u || (hmy & 0x7C00u) == 0x7C00u) match = false;  // inf or NaN
-        // floor(m + 0.5): exact in fp32 for every finite fp16 m
-        const float fx = __builtin_floorf(hbits_to_f(hmx) + 0.5f), fy = __builtin_floorf(hbits_to_f(hmy) + 0.5f);
-        if (!(fx >= 0.0f && fx < (float)width && fy >= 0.0f && fy < (float)height)) match = false;
-        if (match) {
-            match = mask[(size_t)(uint32_t)fy * maskPitch + (uint32_t)fx] != 0;
-            if (match) state[gid] = (uint8_t)(((old & andMask) ^ xorMask) & 0xFFu);
-        }
-        hit = match ? 1u : 0u;
-    }
-    if (matched) {  // (uniform)
-        const uint32_t s = block_reduce_add<kProjectBlock>(hit, lds);
-        if (threadIdx.x == 0 && s) atomicAdd(matched, s);
-    }
-}
+// gsm_global_select_mask (k_select_mask) and its orthographic form (k_select_mask_ortho):
+// one text, compiled twice
+#include "gsm_select_mask_body.h"
+#define GSM_ORTHO 1
+#include "gsm_select_mask_body.h"
+#undef GSM_ORTHO
 
 // gsm_global_select_pick, pass 1: one thread per pixel of the pick image.  A pixel under the mask
 // (every pixel with mask NULL) whose item lies in [base, base + n) sets bit item - base of the bitmap: a vector
@@ -1301,11 +1311,13 @@ static void dispatch_sh(bool halfInput, uint32_t deg, F&& f) {
 static dim3 project_grid(uint32_t blocks, const ProjectArgs& a) { return dim3(blocks + (a.schedUnits ? 1u : 0u)); }
 
 void launch_project(bool halfInput, uint32_t deg, const void* world, const void* harm,
-                    const ProjectArgs& a, const DeviceArena& A, hipStream_t s) {
+                    const ProjectArgs& a, const DeviceArena& A, hipStream_t s, bool ortho) {
     const uint32_t blocks = (a.count + kProjectBlock - 1) / kProjectBlock;
     if (blocks == 0 && a.schedUnits == 0) return;  // (an empty frame still orders its blend units)
     dispatch_sh(halfInput, deg, [&](auto H, auto D) {
-        hipLaunchKernelGGL((k_project<decltype(H)::value, decltype(D)::value>), project_grid(blocks, a),
+        const auto k = ortho ? k_project_ortho<decltype(H)::value, decltype(D)::value>
+                             : k_project<decltype(H)::value, decltype(D)::value>;
+        hipLaunchKernelGGL(k, project_grid(blocks, a),
                            dim3(kProjectBlock), 0, s, world, harm, a, A.renderData, A.bounds, A.rec, A.tileCounts,
                            A.tileMasks, A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax);
     });
@@ -1329,10 +1341,12 @@ void launch_fill_views(const ViewChunk& chunk, uint32_t first, uint32_t n, ViewA
 }
 
 void launch_project_batch(bool halfInput, uint32_t deg, const ProjectArgs& a, const BatchFrame& bf,
-                          const DeviceArena& A, hipStream_t s) {
+                          const DeviceArena& A, hipStream_t s, bool anyOrtho) {
     if (bf.blocks == 0 && a.schedUnits == 0) return;  // (an empty batch still orders its blend units)
     dispatch_sh(halfInput, deg, [&](auto H, auto D) {
-        hipLaunchKernelGGL((k_project_batch<decltype(H)::value, decltype(D)::value>), project_grid(bf.blocks, a),
+        const auto k = anyOrtho ? k_project_batch_ortho<decltype(H)::value, decltype(D)::value>
+                                : k_project_batch<decltype(H)::value, decltype(D)::value>;
+        hipLaunchKernelGGL(k, project_grid(bf.blocks, a),
                            dim3(kProjectBlock), 0, s, a, bf.args, bf.blockView, A.renderData, A.bounds, A.rec,
                            A.tileCounts, A.tileMasks, A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax);
     });
@@ -1352,10 +1366,12 @@ void launch_fill_batch_extras(const ExtrasChunk& chunk, uint32_t first, uint32_t
 }
 
 void launch_project_batch_styled(bool halfInput, uint32_t deg, const ProjectArgs& a, const BatchFrame& bf,
-                                 const uint2* styleTable, const DeviceArena& A, hipStream_t s) {
+                                 const uint2* styleTable, const DeviceArena& A, hipStream_t s, bool anyOrtho) {
     if (bf.blocks == 0 && a.schedUnits == 0) return;  // (an empty batch still orders its blend units)
     dispatch_sh(halfInput, deg, [&](auto H, auto D) {
-        hipLaunchKernelGGL((k_project_batch_styled<decltype(H)::value, decltype(D)::value>),
+        const auto k = anyOrtho ? k_project_batch_ortho_styled<decltype(H)::value, decltype(D)::value>
+                                : k_project_batch_styled<decltype(H)::value, decltype(D)::value>;
+        hipLaunchKernelGGL(k,
                            project_grid(bf.blocks, a), dim3(kProjectBlock), 0, s, a, bf.args, bf.blockView, bf.extras,
                            A.renderData, A.bounds, A.rec, A.tileCounts, A.tileMasks, A.blockSums, A.sincosTable,
                            A.unitCost, A.unitOrder, A.costMax, styleTable);
@@ -1363,10 +1379,12 @@ void launch_project_batch_styled(bool halfInput, uint32_t deg, const ProjectArgs
 }
 
 void launch_project_compose(bool halfInput, uint32_t deg, const ProjectArgs& a, const ComposeFrame& cf,
-                            const DeviceArena& A, hipStream_t s) {
+                            const DeviceArena& A, hipStream_t s, bool ortho) {
     if (cf.blocks == 0 && a.schedUnits == 0) return;  // (an empty composite still orders its blend units)
     dispatch_sh(halfInput, deg, [&](auto H, auto D) {
-        hipLaunchKernelGGL((k_project_compose<decltype(H)::value, decltype(D)::value>), project_grid(cf.blocks, a),
+        const auto k = ortho ? k_project_compose_ortho<decltype(H)::value, decltype(D)::value>
+                             : k_project_compose<decltype(H)::value, decltype(D)::value>;
+        hipLaunchKernelGGL(k, project_grid(cf.blocks, a),
                            dim3(kProjectBlock), 0, s, a, cf.args, cf.blockObject, A.renderData, A.bounds, A.rec,
                            A.tileCounts, A.tileMasks, A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax);
     });
@@ -1380,11 +1398,13 @@ void launch_fill_compose(const ComposeChunk& chunk, uint32_t first, uint32_t n, 
 }
 
 void launch_project_styled(bool halfInput, uint32_t deg, const void* world, const void* harm, const ProjectArgs& a,
-                           const StyleArgs& st, const DeviceArena& A, hipStream_t s) {
+                           const StyleArgs& st, const DeviceArena& A, hipStream_t s, bool ortho) {
     const uint32_t blocks = (a.count + kProjectBlock - 1) / kProjectBlock;
     if (blocks == 0 && a.schedUnits == 0) return;  // (an empty frame still orders its blend units)
     dispatch_sh(halfInput, deg, [&](auto H, auto D) {
-        hipLaunchKernelGGL((k_project_styled<decltype(H)::value, decltype(D)::value>), project_grid(blocks, a),
+        const auto k = ortho ? k_project_ortho_styled<decltype(H)::value, decltype(D)::value>
+                             : k_project_styled<decltype(H)::value, decltype(D)::value>;
+        hipLaunchKernelGGL(k, project_grid(blocks, a),
                            dim3(kProjectBlock), 0, s, world, harm, a, A.renderData, A.bounds, A.rec, A.tileCounts,
                            A.tileMasks, A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax, st.table,
                            st.state, st.defaultState);
@@ -1392,10 +1412,12 @@ void launch_project_styled(bool halfInput, uint32_t deg, const void* world, cons
 }
 
 void launch_project_compose_styled(bool halfInput, uint32_t deg, const ProjectArgs& a, const ComposeFrame& cf,
-                                   const uint2* styleTable, const DeviceArena& A, hipStream_t s) {
+                                   const uint2* styleTable, const DeviceArena& A, hipStream_t s, bool ortho) {
     if (cf.blocks == 0 && a.schedUnits == 0) return;  // (an empty composite still orders its blend units)
     dispatch_sh(halfInput, deg, [&](auto H, auto D) {
-        hipLaunchKernelGGL((k_project_compose_styled<decltype(H)::value, decltype(D)::value>),
+        const auto k = ortho ? k_project_compose_ortho_styled<decltype(H)::value, decltype(D)::value>
+                             : k_project_compose_styled<decltype(H)::value, decltype(D)::value>;
+        hipLaunchKernelGGL(k,
                            project_grid(cf.blocks, a), dim3(kProjectBlock), 0, s, a, cf.args, cf.blockObject,
                            A.renderData, A.bounds, A.rec, A.tileCounts, A.tileMasks, A.blockSums, A.sincosTable,
                            A.unitCost, A.unitOrder, A.costMax, styleTable);
@@ -1408,16 +1430,14 @@ void launch_fill_styles(const StyleChunk& chunk, uint2* dst, hipStream_t s) {
 
 void launch_select_mask(bool halfInput, const void* world, const ProjectArgs& a, const uint8_t* mask, size_t maskPitch,
                         uint32_t width, uint32_t height, uint8_t* state, const uint2* styleTable, uint32_t andMask,
-                        uint32_t xorMask, uint32_t* matched, const DeviceArena& A, hipStream_t s) {
+                        uint32_t xorMask, uint32_t* matched, const DeviceArena& A, hipStream_t s, bool ortho) {
     if (matched) hipMemsetAsync(matched, 0, sizeof(uint32_t), s);  // (overwritten, not added to)
     const uint32_t blocks = (a.count + kProjectBlock - 1) / kProjectBlock;
     if (blocks == 0) return;
-    if (halfInput)
-        hipLaunchKernelGGL(k_select_mask<true>, dim3(blocks), dim3(kProjectBlock), 0, s, world, a, A.sincosTable, mask,
-                           maskPitch, width, height, state, styleTable, andMask, xorMask, matched);
-    else
-        hipLaunchKernelGGL(k_select_mask<false>, dim3(blocks), dim3(kProjectBlock), 0, s, world, a, A.sincosTable, mask,
-                           maskPitch, width, height, state, styleTable, andMask, xorMask, matched);
+    const auto k = halfInput ? (ortho ? k_select_mask_ortho<true> : k_select_mask<true>)
+                             : (ortho ? k_select_mask_ortho<false> : k_select_mask<false>);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(kProjectBlock), 0, s, world, a, A.sincosTable, mask, maskPitch, width,
+                       height, state, styleTable, andMask, xorMask, matched);
 }
 
 void launch_select_pick(const uint8_t* pick, size_t pickPitch, uint32_t width, uint32_t height, const uint8_t* mask,

@@ -7,13 +7,24 @@
 //  and k_project_compose_styled: one more argument, the style table -- for the single
 // frame the scene's state bytes and default too, for a batch the per-view options array that holds them -- and
 // project_gaussian's kProjStyled mode; nothing else differs.
+// With GSM_ORTHO defined (GSM_VIEWS 0, 2 and 3, plain and styled) the text gives the orthographic
+// instances: k_project_ortho, k_project_ortho_styled, k_project_compose_ortho and k_project_compose_ortho_styled call
+// project_gaussian's ORTHO variant for every gaussian -- the uniforms travel in the fields of ProjectArgs and
+// ComposeObjectArgs that carry the perspective terms -- and k_project_batch_ortho, k_project_batch_ortho_styled, the
+// projections of a batch in which some view is orthographic, choose the variant by the view's `ortho` word (uniform
+// per block: a scalar branch).  The kernels without GSM_ORTHO are the text they were.
+#ifdef GSM_ORTHO
+#define GSM_PK(plain, ortho) ortho
+#else
+#define GSM_PK(plain, ortho) plain
+#endif
 #if defined(GSM_STYLED) && GSM_VIEWS == 2
 // The styled projection of a batch with options (gsm_global_render_frames): k_project_batch with the
 // style step.  A block reads its view's state pointer, default state and styled flag from the view's options line
 // (BatchExtras; the block's view index is uniform: scalar loads).  A view that is not styled takes the identity
 // style without a table load -- c * 255 / 255 and o * 255 / 255 in the style rule's integers: the plain bytes.
 template <bool HALF, int DEG>
-__global__ __launch_bounds__(kProjectBlock) void k_project_batch_styled(
+__global__ __launch_bounds__(kProjectBlock) void GSM_PK(k_project_batch_styled, k_project_batch_ortho_styled)(
     ProjectArgs P, const BatchViewArgs* __restrict__ views, const uint16_t* __restrict__ blockView,
     const BatchExtras* __restrict__ extras, GaussianRenderData* __restrict__ outRD, short4* __restrict__ outBounds,
     BlendRecord* __restrict__ outRec, uint32_t* __restrict__ counts, uint32_t* __restrict__ masks,
@@ -25,7 +36,7 @@ __global__ __launch_bounds__(kProjectBlock) void k_project_batch_styled(
     uint32_t defaultState = 0, styledView = 0;
 #elif defined(GSM_STYLED) && GSM_VIEWS == 3
 template <bool HALF, int DEG>
-__global__ __launch_bounds__(kProjectBlock) void k_project_compose_styled(
+__global__ __launch_bounds__(kProjectBlock) void GSM_PK(k_project_compose_styled, k_project_compose_ortho_styled)(
     ProjectArgs P, const ComposeObjectArgs* __restrict__ objects, const uint16_t* __restrict__ blockObject,
     GaussianRenderData* __restrict__ outRD, short4* __restrict__ outBounds, BlendRecord* __restrict__ outRec,
     uint32_t* __restrict__ counts, uint32_t* __restrict__ masks, uint32_t* __restrict__ blockSums,
@@ -37,7 +48,7 @@ __global__ __launch_bounds__(kProjectBlock) void k_project_compose_styled(
     uint32_t defaultState = 0;
 #elif defined(GSM_STYLED)
 template <bool HALF, int DEG>
-__global__ __launch_bounds__(kProjectBlock) void k_project_styled(
+__global__ __launch_bounds__(kProjectBlock) void GSM_PK(k_project_styled, k_project_ortho_styled)(
     const void* __restrict__ world, const void* __restrict__ harm, ProjectArgs P,
     GaussianRenderData* __restrict__ outRD, short4* __restrict__ outBounds,
     BlendRecord* __restrict__ outRec, uint32_t* __restrict__ counts,
@@ -52,7 +63,7 @@ __global__ __launch_bounds__(kProjectBlock) void k_project_styled(
 // thresholds stay P's, as the single frame's.  The per-gaussian arrays are written at the block's items, b * 256
 // + thread; the tile tests and counts are those of k_project for that scene and camera.
 template <bool HALF, int DEG>
-__global__ __launch_bounds__(kProjectBlock) void k_project_compose(
+__global__ __launch_bounds__(kProjectBlock) void GSM_PK(k_project_compose, k_project_compose_ortho)(
     ProjectArgs P, const ComposeObjectArgs* __restrict__ objects, const uint16_t* __restrict__ blockObject,
     GaussianRenderData* __restrict__ outRD, short4* __restrict__ outBounds, BlendRecord* __restrict__ outRec,
     uint32_t* __restrict__ counts, uint32_t* __restrict__ masks, uint32_t* __restrict__ blockSums,
@@ -68,7 +79,7 @@ __global__ __launch_bounds__(kProjectBlock) void k_project_compose(
 // per-gaussian arrays are written at the block's items, b * 256 + thread; the tile tests and counts are those
 // of k_project for that scene, camera and size.
 template <bool HALF, int DEG>
-__global__ __launch_bounds__(kProjectBlock) void k_project_batch(
+__global__ __launch_bounds__(kProjectBlock) void GSM_PK(k_project_batch, k_project_batch_ortho)(
     ProjectArgs P, const BatchViewArgs* __restrict__ views, const uint16_t* __restrict__ blockView,
     GaussianRenderData* __restrict__ outRD, short4* __restrict__ outBounds, BlendRecord* __restrict__ outRec,
     uint32_t* __restrict__ counts, uint32_t* __restrict__ masks, uint32_t* __restrict__ blockSums,
@@ -91,7 +102,7 @@ __global__ __launch_bounds__(kProjectBlock) void k_project_views(
     uint32_t* __restrict__ unitOrder, uint32_t* __restrict__ costMax) {
 #else
 template <bool HALF, int DEG>
-__global__ __launch_bounds__(kProjectBlock) void k_project(
+__global__ __launch_bounds__(kProjectBlock) void GSM_PK(k_project, k_project_ortho)(
     const void* __restrict__ world, const void* __restrict__ harm, ProjectArgs P,
     GaussianRenderData* __restrict__ outRD, short4* __restrict__ outBounds,
     BlendRecord* __restrict__ outRec, uint32_t* __restrict__ counts,
@@ -135,11 +146,17 @@ __global__ __launch_bounds__(kProjectBlock) void k_project(
 #elif GSM_VIEWS == 2
     // the block's view (uniform: scalar loads) and its first gaussian; items are written at blk * 256 + thread
     uint32_t gblk;
+#ifdef GSM_ORTHO
+    uint32_t orthoView = 0;  // the view's kind (uniform per block)
+#endif
     {
         const BatchViewArgs& V = views[__builtin_amdgcn_readfirstlane((uint32_t)blockView[blk])];
         gblk = blk - V.blockBase;
         world = V.world;
         harm = V.harm;
+#ifdef GSM_ORTHO
+        orthoView = V.ortho;
+#endif
 #ifdef GSM_STYLED
         {
             const BatchExtras& E = extras[__builtin_amdgcn_readfirstlane((uint32_t)blockView[blk])];
@@ -221,8 +238,21 @@ __global__ __launch_bounds__(kProjectBlock) void k_project(
     o.bounds = make_short4(0, -1, 0, -1);
     uint32_t area = 0;
     int ty0 = 0;
-    if (gid < P.count) {
 #ifdef GSM_STYLED
+#define GSM_PROJ_MODE kProjStyled
+#define GSM_PROJ_STYLE style
+#else
+#define GSM_PROJ_MODE kProjPlain
+#define GSM_PROJ_STYLE make_uint2(0u, kStyleIdentityY)
+#endif
+    if (gid < P.count) {
+#if defined(GSM_ORTHO) && GSM_VIEWS == 2
+        o = project_gaussian<HALF, DEG, GSM_PROJ_MODE, kOrthoPerView>(world, harm, gid, P, sincos, lut,
+                                                                      HALF ? preW : nullptr, GSM_PROJ_STYLE, orthoView);
+#elif defined(GSM_ORTHO)
+        o = project_gaussian<HALF, DEG, GSM_PROJ_MODE, kOrthoOn>(world, harm, gid, P, sincos, lut, HALF ? preW : nullptr,
+                                                                 GSM_PROJ_STYLE);
+#elif defined(GSM_STYLED)
         o = project_gaussian<HALF, DEG, kProjStyled>(world, harm, gid, P, sincos, lut, HALF ? preW : nullptr, style);
 #else
         o = project_gaussian<HALF, DEG>(world, harm, gid, P, sincos, lut, HALF ? preW : nullptr);
@@ -305,3 +335,6 @@ __global__ __launch_bounds__(kProjectBlock) void k_project(
 #if !GSM_VIEWS
 #undef oid
 #endif
+#undef GSM_PROJ_MODE
+#undef GSM_PROJ_STYLE
+#undef GSM_PK

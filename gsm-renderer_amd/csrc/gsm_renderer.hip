@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -127,7 +128,7 @@ int GlobalRenderer::sortPassCount() const {
 }
 
 ProjectArgs GlobalRenderer::frameArgs(const gsm_camera_params& camp, uint32_t width, uint32_t height,
-                                      uint32_t count, uint32_t shComponents) const {
+                                      uint32_t count, uint32_t shComponents, bool orthographic) const {
     ProjectArgs a;
     std::memset(&a, 0, sizeof(a));
     // CameraUniforms(from: camera, ...) (KernelTypes.swift:107-123)
@@ -170,6 +171,24 @@ ProjectArgs GlobalRenderer::frameArgs(const gsm_camera_params& camp, uint32_t wi
     a.maxEig = u.maxEig;
     a.adjFar = u.adjFar;
     a.adjDen = u.adjDen;
+    if (orthographic) {
+        // The orthographic rule's uniforms, in the fields that carry the perspective terms, each formed
+        // once with the fp32 operations the checker repeats per gaussian: sigma, the two signed entries of the
+        // diagonal J, and the uniform SH direction -- minus the view's +z axis in world space, times sigma,
+        // normalised by normalize3's sequence (x x + y y, + z z, sqrt, three divisions).  camp.position is ignored.
+        const float sigma = a.cam.proj[10] >= 0.0f ? 1.0f : -1.0f;
+        a.limX = sigma;
+        a.limY = 0.0f;
+        a.focalX = a.cam.width * a.cam.proj[0] * 0.5f;
+        a.focalY = a.cam.height * a.cam.proj[5] * 0.5f;
+        const float d0 = -sigma * a.cam.view[2], d1 = -sigma * a.cam.view[6], d2 = -sigma * a.cam.view[10];
+        float dd = d0 * d0 + d1 * d1;
+        dd = dd + d2 * d2;
+        const float n = sqrtf(dd);
+        a.cam.cameraCenter[0] = d0 / n;
+        a.cam.cameraCenter[1] = d1 / n;
+        a.cam.cameraCenter[2] = d2 / n;
+    }
     return a;
 }
 
@@ -296,14 +315,19 @@ gsm_status GlobalRenderer::renderFrame(hipStream_t s, const gsm_gaussian_input& 
     if (st != GSM_OK) return st;
     if (style && !styleSourceOk(*style, 1)) return GSM_ERR_INVALID_ARGUMENT;
     // (set_tile_rows: a pick frame, an occluded frame and a styled frame are whole frames)
-    if ((extras.pick || extras.occluder || style) && tileRowsRestricted()) return GSM_ERR_UNSUPPORTED;
+    // (an orthographic frame too: the flag joins this row)
+    if ((extras.pick || extras.occluder || style || extras.orthographic) && tileRowsRestricted())
+        return GSM_ERR_UNSUPPORTED;
     // the projection's tile tests walk contiguous rows; interleaved row sets come from the records
     // path only (gsm_multigpu)
     if (rowStride_ != 1) return GSM_ERR_INVALID_ARGUMENT;
-    FrameRequest rq = request(FrameKind::Single, frameArgs(camp, width, height, in.gaussian_count, in.sh_components),
-                              width, height, t);
+    const bool ortho = extras.orthographic;
+    FrameRequest rq = request(FrameKind::Single,
+                              frameArgs(camp, width, height, in.gaussian_count, in.sh_components, ortho), width,
+                              height, t);
     rq.pick = extras.pick;
     rq.occluder = extras.occluder;
+    rq.orthographic = ortho;
     const uint32_t deg = sh_degree(in.sh_components);
     const bool half = config_.precision == GSM_PRECISION_FLOAT16;
     if (style) {
@@ -311,11 +335,11 @@ gsm_status GlobalRenderer::renderFrame(hipStream_t s, const gsm_gaussian_input& 
         const StyleArgs sa{arena_.styleTable, style->states[0].state, style->states[0].default_state};
         rq.styled = true;
         return runFrame(s, rq, [&](const ProjectArgs& pa) {
-            launch_project_styled(half, deg, in.gaussians, in.harmonics, pa, sa, arena_, s);
+            launch_project_styled(half, deg, in.gaussians, in.harmonics, pa, sa, arena_, s, ortho);
         });
     }
     return runFrame(s, rq, [&](const ProjectArgs& pa) {
-        launch_project(half, deg, in.gaussians, in.harmonics, pa, arena_, s);
+        launch_project(half, deg, in.gaussians, in.harmonics, pa, arena_, s, ortho);
     });
 }
 
@@ -349,7 +373,7 @@ gsm_status GlobalRenderer::fillStyleTable(hipStream_t s, const gsm_global_style*
 gsm_status GlobalRenderer::selectMask(hipStream_t s, const gsm_gaussian_input* in, const gsm_camera_params* camp,
                                       uint32_t width, uint32_t height, const void* mask, size_t maskPitch,
                                       uint8_t* state, const gsm_global_style* styles, uint32_t styleCount,
-                                      uint32_t andMask, uint32_t xorMask, uint32_t* matched) {
+                                      uint32_t andMask, uint32_t xorMask, uint32_t* matched, bool orthographic) {
     // (the count of a NULL input cannot be read: that is the missing buffer, before every other check)
     if (!in) return GSM_ERR_MISSING_REQUIRED_BUFFER;
     if (in->gaussian_count > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
@@ -363,9 +387,10 @@ gsm_status GlobalRenderer::selectMask(hipStream_t s, const gsm_gaussian_input* i
         const gsm_status st = fillStyleTable(s, styles, styleCount);
         if (st != GSM_OK) return st;
     }
-    const ProjectArgs a = frameArgs(*camp, width, height, in->gaussian_count, 0);
+    const ProjectArgs a = frameArgs(*camp, width, height, in->gaussian_count, 0, orthographic);
     launch_select_mask(config_.precision == GSM_PRECISION_FLOAT16, in->gaussians, a, (const uint8_t*)mask, maskPitch,
-                       width, height, state, styles ? arena_.styleTable : nullptr, andMask, xorMask, matched, arena_, s);
+                       width, height, state, styles ? arena_.styleTable : nullptr, andMask, xorMask, matched, arena_, s,
+                       orthographic);
     if (hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;
     return GSM_OK;
 }
@@ -484,7 +509,7 @@ gsm_status GlobalRenderer::renderFrames(hipStream_t s, const gsm_global_frame* f
     // row decides, within it the lowest frame.  (frame_count == 0 falls through to the batch's first row.)
     if (frameCount >= 1 && !frames) return GSM_ERR_MISSING_REQUIRED_BUFFER;
     for (uint32_t v = 0; v < frameCount; ++v)
-        if (frames[v].flags != 0) return GSM_ERR_INVALID_ARGUMENT;
+        if (frames[v].flags & ~GSM_FRAME_ORTHOGRAPHIC) return GSM_ERR_INVALID_ARGUMENT;
     for (uint32_t v = 0; v < frameCount; ++v)  // (composites inside a batch: out of scope)
         if (frames[v].object_count != 1) return GSM_ERR_UNSUPPORTED;
     for (uint32_t v = 0; v < frameCount; ++v)
@@ -529,9 +554,10 @@ gsm_status GlobalRenderer::renderFrames(hipStream_t s, const gsm_global_frame* f
         O.occluder = OccluderSource{F.occluder_r32f, F.occluder_pitch_bytes};
         O.styled = F.states || F.styles;  // (one without the other: the styled row refuses)
         O.style = StyleSource{F.states, F.styles, F.style_count};
-        any = any || F.pick_r32u || F.occluder_r32f || O.styled;
+        O.orthographic = (F.flags & GSM_FRAME_ORTHOGRAPHIC) != 0;
+        any = any || F.pick_r32u || F.occluder_r32f || O.styled || O.orthographic;
     }
-    // every option NULL in every frame: the plain batch, its path and its device code
+    // every option NULL and no flag in every frame: the plain batch, its path and its device code
     return enqueueBatch(s, framesViews_.data(), frameCount, any ? framesOptions_.data() : nullptr);
 }
 
@@ -573,10 +599,11 @@ gsm_status GlobalRenderer::enqueueBatch(hipStream_t s, const gsm_global_view* vi
         if (views[v].input.sh_components != views[0].input.sh_components) return GSM_ERR_INVALID_ARGUMENT;
     // the styled row, per view; the batch has one style table, so every styled view must give the same one (the
     // six meaningful bytes of every style; pad is ignored)
-    bool anyPick = false, anyOccluder = false;
+    bool anyPick = false, anyOccluder = false, anyOrtho = false;
     const StyleSource* table = nullptr;
     for (uint32_t v = 0; options && v < viewCount; ++v) {
         const BatchViewOptions& O = options[v];
+        anyOrtho = anyOrtho || O.orthographic;
         anyPick = anyPick || O.pick.pixels;
         anyOccluder = anyOccluder || O.occluder.pixels;
         if (!O.styled) continue;
@@ -605,8 +632,8 @@ gsm_status GlobalRenderer::enqueueBatch(hipStream_t s, const gsm_global_view* vi
         if (st == GSM_OK) st = allocs_.alloc((void**)&tv, (size_t)tileCount_ * sizeof(uint16_t));
         if (st != GSM_OK) return st;
         batchHost_.reserve(mv);
-        key_.reserve(ScheduleKey::kFixedWords + 3 * (size_t)mv);  // (the largest signature the handle can hold)
-        schedState_.reserve(ScheduleKey::kFixedWords + 3 * (size_t)mv);
+        key_.reserve(ScheduleKey::kFixedWords + 3 * (size_t)mv + 1);  // (the largest signature the handle can hold)
+        schedState_.reserve(ScheduleKey::kFixedWords + 3 * (size_t)mv + 1);
         arena_.batchArgs = args;
         arena_.batchBlockView = bv;
         arena_.batchTileView = tv;
@@ -627,10 +654,12 @@ gsm_status GlobalRenderer::enqueueBatch(hipStream_t s, const gsm_global_view* vi
     for (uint32_t v = 0; v < viewCount; ++v) {
         const gsm_global_view& V = views[v];
         const uint32_t n = V.input.gaussian_count;
-        const ProjectArgs pv = frameArgs(V.camera, V.width, V.height, n, sh);
+        const bool ortho = options && options[v].orthographic;  // (the kind is per view: a quad view mixes them)
+        const ProjectArgs pv = frameArgs(V.camera, V.width, V.height, n, sh, ortho);
         BatchViewArgs& d = batchHost_[v];
         std::memset(&d, 0, sizeof(d));
         set_view_terms(d, pv);
+        d.ortho = ortho ? 1u : 0u;
         d.count = n;
         d.bin = pv.bin;
         d.bin.tilesX = (V.width + kTileWidth - 1) / kTileWidth;
@@ -704,16 +733,18 @@ gsm_status GlobalRenderer::enqueueBatch(hipStream_t s, const gsm_global_view* vi
         bf.extras = arena_.batchExtras;
         rq.anyPick = anyPick;
         rq.anyOccluder = anyOccluder;
+        rq.orthographic = anyOrtho;
         if (table) {
             const gsm_status st = fillStyleTable(s, table->styles, table->styleCount);
             if (st != GSM_OK) return st;
             rq.styled = true;
             return runFrame(s, rq, [&](const ProjectArgs& pa) {
-                launch_project_batch_styled(half, deg, pa, bf, arena_.styleTable, arena_, s);
+                launch_project_batch_styled(half, deg, pa, bf, arena_.styleTable, arena_, s, anyOrtho);
             });
         }
     }
-    return runFrame(s, rq, [&](const ProjectArgs& pa) { launch_project_batch(half, deg, pa, bf, arena_, s); });
+    // (a batch without an orthographic view launches the kernels it launched before the flag existed)
+    return runFrame(s, rq, [&](const ProjectArgs& pa) { launch_project_batch(half, deg, pa, bf, arena_, s, anyOrtho); });
 }
 
 gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* objects, uint32_t objectCount,
@@ -722,6 +753,7 @@ gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* 
     const PickTarget* pick = extras.pick;
     const OccluderSource* occluder = extras.occluder;
     const StyleSource* style = extras.style;
+    const bool ortho = extras.orthographic;  // (the flag holds for every object; sigma, J and d0 are per object)
     void* const color = t.color;
     void* const depth = t.depth;
     const size_t colorPitch = t.colorPitch, depthPitch = t.depthPitch;
@@ -769,8 +801,8 @@ gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* 
         if (st != GSM_OK) return st;
         composeHost_.reserve(maxEntries);
         composeObject_.reserve(maxEntries);
-        key_.reserve(ScheduleKey::kFixedWords + 65535u);  // (the largest signature: a count per object)
-        schedState_.reserve(ScheduleKey::kFixedWords + 65535u);
+        key_.reserve(ScheduleKey::kFixedWords + 65535u + 1u);  // (the largest signature: a count per object)
+        schedState_.reserve(ScheduleKey::kFixedWords + 65535u + 1u);
         arena_.composeArgs = args;
         arena_.composeBlockObject = bo;
     }
@@ -785,7 +817,7 @@ gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* 
         const gsm_global_object& O = objects[o];
         const uint32_t n = O.input.gaussian_count;
         if (n == 0) continue;  // (no block, no entry)
-        const ProjectArgs po = frameArgs(O.camera, width, height, n, sh);
+        const ProjectArgs po = frameArgs(O.camera, width, height, n, sh, ortho);
         ComposeObjectArgs d;
         std::memset(&d, 0, sizeof(d));
         set_view_terms(d, po);
@@ -807,8 +839,9 @@ gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* 
     // the frame's arguments are the single frame's: the handle's tile grid and rows, the thresholds, the capacity
     // and the schedule; count = the composite's gaussians (counters).  (Not batchSharedArgs: that puts a batch on
     // view 0's own grid, and a composite stays on the handle's, as gsm_global_render does.)
-    const ProjectArgs a = frameArgs(objects[0].camera, width, height, countSum, sh);
+    const ProjectArgs a = frameArgs(objects[0].camera, width, height, countSum, sh, ortho);
     FrameRequest rq = request(FrameKind::Compose, a, width, height, t);
+    rq.orthographic = ortho;
     ComposeFrame& cf = rq.payload.composeFrame;
     cf.objects = objectCount;
     cf.entries = entries;
@@ -823,10 +856,10 @@ gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* 
         if ((st = fillStyleTable(s, style->styles, style->styleCount)) != GSM_OK) return st;
         rq.styled = true;
         return runFrame(s, rq, [&](const ProjectArgs& pa) {
-            launch_project_compose_styled(half, deg, pa, cf, arena_.styleTable, arena_, s);
+            launch_project_compose_styled(half, deg, pa, cf, arena_.styleTable, arena_, s, ortho);
         });
     }
-    return runFrame(s, rq, [&](const ProjectArgs& pa) { launch_project_compose(half, deg, pa, cf, arena_, s); });
+    return runFrame(s, rq, [&](const ProjectArgs& pa) { launch_project_compose(half, deg, pa, cf, arena_, s, ortho); });
 }
 
 gsm_status GlobalRenderer::renderRecords(hipStream_t s, const void* records, uint32_t count, uint32_t width,
@@ -1005,6 +1038,9 @@ const ScheduleKey& GlobalRenderer::requestKey(const FrameRequest& rq, uint32_t* 
     key_[ScheduleKey::kRowBegin] = rowBegin_;
     key_[ScheduleKey::kRowEnd] = rowEnd_;
     key_[ScheduleKey::kRowStride] = rowStride_;
+    // (an orthographic frame's footprints are another camera model's: its costs are its own, either way round; a
+    // batch: whether any view is orthographic)
+    if (rq.orthographic) key_.markOrthographic();
     return key_;
 }
 

@@ -24,10 +24,12 @@ struct StyleSource {
     const gsm_global_style* styles;
     uint32_t styleCount;
 };
+// orthographic: the frame's flag GSM_FRAME_ORTHOGRAPHIC -- the projection rule of every object.
 struct FrameExtras {
     const PickTarget* pick = nullptr;
     const OccluderSource* occluder = nullptr;
     const StyleSource* style = nullptr;
+    bool orthographic = false;
 };
 
 class GlobalRenderer {
@@ -58,11 +60,12 @@ class GlobalRenderer {
     // (gsm_global_render_frames)
     gsm_status renderFrames(hipStream_t stream, const gsm_global_frame* frames, uint32_t frameCount);
 
-    // state bytes of the gaussians whose projected centre lies on a nonzero mask byte (gsm_global_select_mask)
+    // state bytes of the gaussians whose projected centre lies on a nonzero mask byte (gsm_global_select_mask;
+    // orthographic: gsm_global_select_mask_ortho)
     gsm_status selectMask(hipStream_t stream, const gsm_gaussian_input* input, const gsm_camera_params* camera,
                           uint32_t width, uint32_t height, const void* mask, size_t maskPitch, uint8_t* state,
                           const gsm_global_style* styles, uint32_t styleCount, uint32_t andMask, uint32_t xorMask,
-                          uint32_t* matched);
+                          uint32_t* matched, bool orthographic = false);
     // state bytes of the gaussians of `object` that the last pick frame's image shows under the mask
     // (gsm_global_select_pick)
     gsm_status selectPick(hipStream_t stream, const void* pick, size_t pickPitch, uint32_t width, uint32_t height,
@@ -142,8 +145,9 @@ class GlobalRenderer {
     static bool styleSourceOk(const StyleSource& style, uint32_t stateCount);
     // the handle's style table: allocated by its first use, filled from the caller's styles (identity past them)
     gsm_status fillStyleTable(hipStream_t s, const gsm_global_style* styles, uint32_t styleCount);
+    // orthographic: the uniforms of the orthographic rule in place of the perspective terms (ProjectArgs)
     ProjectArgs frameArgs(const gsm_camera_params& camera, uint32_t width, uint32_t height, uint32_t count,
-                          uint32_t shComponents) const;
+                          uint32_t shComponents, bool orthographic = false) const;
     // One description of a frame: what runFrame enqueues after `front` filled the per-gaussian arrays.
     // (Views: args holds what the views share, the targets are view 0's.  Batch: args holds what the views share,
     // nothing per view.  Compose: args is the frame's, as a single frame's; only the items differ.)
@@ -155,6 +159,9 @@ class GlobalRenderer {
         const PickTarget* pick = nullptr;
         const OccluderSource* occluder = nullptr;
         bool styled = false;  // the projection applies styles: the walks are the frame's own (schedule key)
+        // the projection follows the orthographic rule (a Batch: some view's does): the footprints, and with them
+        // the walks, are the frame's own (schedule key)
+        bool orthographic = false;
         // a Batch with options (renderFrames): some view has a pick target / an occluder.  The targets themselves
         // are per view (BatchFrame::extras); these are the union the schedule key and the blend's kernel follow.
         bool anyPick = false, anyOccluder = false;
@@ -190,6 +197,7 @@ class GlobalRenderer {
         OccluderSource occluder{nullptr, 0};
         bool styled = false;
         StyleSource style{nullptr, nullptr, 0};
+        bool orthographic = false;  // the frame's flag: this view's projection rule
     };
     // renderBatch and renderFrames: every check, the per-view entries and tables, the request, the frame.
     // options (nullable, [viewCount]): null is the plain batch, device code and all.

@@ -24,8 +24,13 @@ struct ScheduleKey {
         kViewCount,  // views of a Views / Batch frame, objects of a Compose frame, else 0
         kFixedWords  // then a Batch's (width, height, count) per view, or a Compose's count per object
     };
+    // An orthographic frame (GSM_FRAME_ORTHOGRAPHIC; a Batch: any of its views) ends its key with one more word,
+    // kOrthographicWord, after the tail (markOrthographic); a perspective frame's key has none.  The two therefore
+    // differ in length whatever else they hold, so neither inherits the other's unit costs nor leaves it any -- the
+    // rule that added kStyled -- and the keys of perspective frames are the words they were.
+    static constexpr uint32_t kOrthographicWord = 1u;
     std::vector<uint32_t> words;
-    ScheduleKey() : words(kFixedWords, 0u) {}
+    ScheduleKey() : words(kFixedWords, 0u) { words.reserve(kFixedWords + 1); }
     void reserve(size_t n) { words.reserve(n); }
     // the fixed words zeroed but the kind, the tail dropped (no allocation)
     void reset(FrameKind kind) {
@@ -35,12 +40,14 @@ struct ScheduleKey {
     uint32_t& operator[](Word w) { return words[w]; }
     uint32_t operator[](Word w) const { return words[w]; }
     void push(uint32_t w) { words.push_back(w); }
+    // call last, after every tail word
+    void markOrthographic() { words.push_back(kOrthographicWord); }
 };
 
 // The key the unit costs belong to (none before the first frame: every key differs from it).
 class ScheduleState {
    public:
-    ScheduleState() { words_.reserve(ScheduleKey::kFixedWords); }
+    ScheduleState() { words_.reserve(ScheduleKey::kFixedWords + 1); }  // (+ 1: the orthographic word)
     // room for keys of up to n words: no update() of such a key allocates afterwards
     void reserve(size_t n) { words_.reserve(n); }
     // adopts `key`; true when it differs from the stored one, i.e. the costs must be cleared

@@ -179,7 +179,8 @@ class SceneObject:
 class Frame:
     """gsm_global_frame: one descriptor of GlobalRenderer.render_frames -- `render_frame`'s arguments as a value.
     objects: one (GaussianInput, CameraParams) pair (or a SceneObject list of one); pick / occluder / states /
-    styles None: that option is not given; pitches None: width * bytes per pixel."""
+    styles None: that option is not given; pitches None: width * bytes per pixel.  orthographic: the frame follows
+    the orthographic projection rule (FRAME_ORTHOGRAPHIC is or-ed into flags)."""
     objects: object
     width: int
     height: int
@@ -195,6 +196,7 @@ class Frame:
     occluder_pitch: Optional[int] = None
     style_count: Optional[int] = None
     flags: int = 0
+    orthographic: bool = False
 
 
 @dataclass
@@ -286,6 +288,7 @@ class _LocalCounters(C.Structure):
 
 
 PICK_NONE = 0xFFFFFFFF  # include/gsm_renderer.h GSM_PICK_NONE
+FRAME_ORTHOGRAPHIC = 2  # include/gsm_renderer.h GSM_FRAME_ORTHOGRAPHIC (gsm_global_frame.flags)
 
 _LIB = None
 
@@ -328,6 +331,9 @@ _SIGNATURES = {
     "gsm_global_select_mask": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera), C.c_uint32,
                                 C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(_Style), C.c_uint32,
                                 C.c_uint32, C.c_uint32, C.c_void_p], C.c_int),
+    "gsm_global_select_mask_ortho": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera), C.c_uint32,
+                                      C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(_Style), C.c_uint32,
+                                      C.c_uint32, C.c_uint32, C.c_void_p], C.c_int),
     "gsm_global_render_frame": ([C.c_void_p, C.c_void_p, C.POINTER(_GlobalFrame)], C.c_int),
     "gsm_global_select_pick": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
                                 C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p],
@@ -747,8 +753,9 @@ class GlobalRenderer(_Renderer):
 
     def select_mask(self, input: GaussianInput, camera: CameraParams, width: int, height: int, mask, state,
                     and_mask: int, xor_mask: int, styles=None, matched=None, stream=None,
-                    mask_pitch: Optional[int] = None, style_count: Optional[int] = None):
-        """gsm_global_select_mask: the state byte of every gaussian whose projected centre lies on a nonzero byte
+                    mask_pitch: Optional[int] = None, style_count: Optional[int] = None, orthographic: bool = False):
+        """gsm_global_select_mask (orthographic: gsm_global_select_mask_ortho, the same select under the
+        orthographic projection rule): the state byte of every gaussian whose projected centre lies on a nonzero byte
         of `mask` (uint8 CUDA tensor, height rows of mask_pitch bytes) becomes (old & and_mask) ^ xor_mask; with
         `styles`, gaussians whose current state is hidden are skipped.  matched: an int32 / uint32 CUDA tensor of
         one element that receives the count.  input.harmonics may be None."""
@@ -756,26 +763,29 @@ class GlobalRenderer(_Renderer):
         cam = _camera_struct(camera)
         mp = mask_pitch if mask_pitch is not None else int(width)
         sarr, sn = _style_array(styles)
-        st = _lib().gsm_global_select_mask(self._h, _stream_handle(stream), C.byref(inp), C.byref(cam), int(width),
-                                           int(height), _ptr(mask), mp, _ptr(state), sarr,
-                                           sn if style_count is None else int(style_count),
-                                           int(and_mask) & 0xFFFFFFFF, int(xor_mask) & 0xFFFFFFFF, _ptr(matched))
-        _check(st, "gsm_global_select_mask")
+        name = "gsm_global_select_mask_ortho" if orthographic else "gsm_global_select_mask"
+        st = getattr(_lib(), name)(self._h, _stream_handle(stream), C.byref(inp), C.byref(cam), int(width),
+                                   int(height), _ptr(mask), mp, _ptr(state), sarr,
+                                   sn if style_count is None else int(style_count),
+                                   int(and_mask) & 0xFFFFFFFF, int(xor_mask) & 0xFFFFFFFF, _ptr(matched))
+        _check(st, name)
 
     def render_frame(self, color_texture, depth_texture, objects, width: int, height: int, pick=None, occluder=None,
                      states=None, styles=None, stream=None, color_pitch: Optional[int] = None,
                      depth_pitch: Optional[int] = None, pick_pitch: Optional[int] = None,
                      occluder_pitch: Optional[int] = None, style_count: Optional[int] = None, flags: int = 0,
-                     null_frame: bool = False):
+                     null_frame: bool = False, orthographic: bool = False):
         """gsm_global_render_frame: one descriptor for every Single and Compose frame and every combination of a
         pick target, an occluder and styles.  objects: a SceneObject list, or one (GaussianInput, CameraParams)
         pair as a single object; None passes a NULL array with object_count 1.  pick / occluder: as for
         `render_pick` / `render_occluded`, None leaves the option out.  states: one entry per object (a uint8 CUDA
         tensor or an int), or a single such value for a single object; styles: a Style list.  null_frame passes a
-        NULL descriptor (the C entry's error path)."""
+        NULL descriptor (the C entry's error path).  orthographic: every object is projected by the orthographic
+        rule (scenes.ortho_camera builds such a camera); FRAME_ORTHOGRAPHIC is or-ed into flags."""
         f = _GlobalFrame()
         keep = self._fill_frame(f, color_texture, depth_texture, objects, width, height, pick, occluder, states, styles,
-                                color_pitch, depth_pitch, pick_pitch, occluder_pitch, style_count, flags)
+                                color_pitch, depth_pitch, pick_pitch, occluder_pitch, style_count,
+                                int(flags) | (FRAME_ORTHOGRAPHIC if orthographic else 0))
         st = _lib().gsm_global_render_frame(self._h, _stream_handle(stream), None if null_frame else C.byref(f))
         del keep
         _check(st, "gsm_global_render_frame")
@@ -821,7 +831,8 @@ class GlobalRenderer(_Renderer):
             for f, d in zip(arr, frames):
                 keep.append(self._fill_frame(f, d.color, d.depth, d.objects, d.width, d.height, d.pick, d.occluder,
                                              d.states, d.styles, d.color_pitch, d.depth_pitch, d.pick_pitch,
-                                             d.occluder_pitch, d.style_count, d.flags))
+                                             d.occluder_pitch, d.style_count,
+                                             int(d.flags) | (FRAME_ORTHOGRAPHIC if d.orthographic else 0)))
         st = _lib().gsm_global_render_frames(self._h, _stream_handle(stream), arr, n)
         del keep
         _check(st, "gsm_global_render_frames")

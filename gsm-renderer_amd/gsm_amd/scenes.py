@@ -45,6 +45,29 @@ def make_camera(width: int, height: int, eye_offset_x: float = 0.0) -> dict:
             "focal_x": width * f / (2 * aspect), "focal_y": height * f / 2, "near": 0.1, "far": 10.0}
 
 
+def ortho_camera(width: int, height: int, half_height: float, near: float = 0.1, far: float = 10.0,
+                 view=None) -> dict:
+    """An orthographic camera for a frame with the orthographic flag (GlobalRenderer.render_frame(...,
+    orthographic=True)), in make_camera's convention -- looking down +z, depth in [0, 1]: the view volume is
+    2 * half_height world units high and aspect times as wide, p00 = 1 / (half_height * aspect), p11 = 1 /
+    half_height, p10 = 1 / (far - near), p14 = -near / (far - near), p15 = 1 (column-major flat).  view: a
+    column-major flat 4x4 (None: the identity).  An orthographic camera has no position: the field is zero and
+    the frame ignores it; focal_x / focal_y are pixels per world unit."""
+    aspect = np.float32(width) / np.float32(height)
+    hh = np.float32(half_height)
+    P = np.zeros(16, np.float32)
+    P[0] = np.float32(1.0) / (hh * aspect)
+    P[5] = np.float32(1.0) / hh
+    P[10] = np.float32(1.0) / (np.float32(far) - np.float32(near))
+    P[14] = -np.float32(near) / (np.float32(far) - np.float32(near))
+    P[15] = 1.0
+    V = np.eye(4, dtype=np.float32).reshape(-1) if view is None else \
+        np.asarray(view, np.float32).reshape(-1).copy()
+    return {"view": V, "proj": P, "position": np.zeros(3, np.float32),
+            "focal_x": float(width * P[0] * np.float32(0.5)), "focal_y": float(height * P[5] * np.float32(0.5)),
+            "near": float(near), "far": float(far)}
+
+
 def orbit_camera(width: int, height: int, angle_deg: float, pivot_z: float = 5.5) -> dict:
     """make_camera's camera moved on a circle about the y axis through (0, 0, pivot_z), still looking
     at that point: angle 0 is make_camera itself.  Used for the moving-camera benchmark (bench.py

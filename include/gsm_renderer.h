@@ -471,7 +471,8 @@ gsm_status gsm_global_select_mask(gsm_renderer *renderer, void *stream, const gs
  * frame of this entry that had a pick target.
  *
  * Checked before anything is enqueued; the first failing check in this order decides:
- *   GSM_ERR_INVALID_ARGUMENT         frame NULL or flags != 0 (before everything else);
+ *   GSM_ERR_INVALID_ARGUMENT         frame NULL or a flags bit other than GSM_FRAME_ORTHOGRAPHIC set (before
+ *                                    everything else; bit 0 stays reserved: flags == 1 and flags == 3 are refused);
  *   then the checks of gsm_global_render (object_count == 1 with objects non-NULL) or gsm_global_render_composite
  *   (every other object_count, 0 included), in that entry's order, each optional buffer joining its rows --
  *   GSM_ERR_INVALID_GAUSSIAN_COUNT   as that entry;
@@ -484,7 +485,8 @@ gsm_status gsm_global_select_mask(gsm_renderer *renderer, void *stream, const gs
  *                                    states, states without styles, style_count 0 or above 256, or a default_state
  *                                    above 255 (both NULL: no styles, style_count ignored);
  *   GSM_ERR_UNSUPPORTED              last: the handle is restricted to tile rows (gsm_global_set_tile_rows) and
- *                                    the frame has a pick target, an occluder or styles, or more than one object.
+ *                                    the frame has a pick target, an occluder, styles or the orthographic flag, or
+ *                                    more than one object.
  * Enqueue-only and capturable; nothing is allocated per frame beyond what the entries above allocate once.
  * Several descriptors in one batch -- a quad view, a stereo pair -- are gsm_global_render_frames (below).  Out of
  * scope: gsm_global_render_views, gsm_global_render_records, the DepthFirst and Local renderers and the multi-GPU
@@ -498,7 +500,7 @@ typedef struct {
     const void *occluder_r32f;  size_t occluder_pitch_bytes;    /* nullable */
     const gsm_global_state *states;                             /* [object_count], nullable with styles */
     const gsm_global_style *styles;  uint32_t style_count;      /* nullable */
-    uint32_t flags;                                             /* must be 0 */
+    uint32_t flags;                                             /* 0 or GSM_FRAME_ORTHOGRAPHIC */
 } gsm_global_frame;
 #ifdef __cplusplus
 static_assert(sizeof(gsm_global_frame) == 112, "gsm_global_frame is 112 bytes");
@@ -506,6 +508,39 @@ static_assert(sizeof(gsm_global_frame) == 112, "gsm_global_frame is 112 bytes");
 _Static_assert(sizeof(gsm_global_frame) == 112, "gsm_global_frame is 112 bytes");
 #endif
 gsm_status gsm_global_render_frame(gsm_renderer *renderer, void *stream, const gsm_global_frame *frame);
+
+/* Orthographic cameras (no reference analogue): the top, front and side viewports of an editor.  A
+ * frame is orthographic when gsm_global_frame.flags has GSM_FRAME_ORTHOGRAPHIC; the kind is requested, never detected
+ * from the matrix.  Bit 0 of flags stays reserved and refused.  The flag holds for every object of the frame; in
+ * gsm_global_render_frames it is per frame, so one batch may mix perspective and orthographic views.
+ *
+ * The rule, for a gaussian under an object's camera (everything not named is the perspective rule unchanged: the
+ * scale cull, the alpha threshold, the 3-D covariance, the stabilisation, theta and the sigmas, the radius cull, the
+ * extents, the screen-bounds cull, the tile bounds, the record, the tile count, the scatter, the sort, the blend):
+ *   vp = view * (pos, 1), clip = proj * vp; row 3 of proj is not used;
+ *   depth   d = sigma * vp.z with sigma = +1 when proj[10] >= 0 and -1 otherwise (the project's convention is
+ *           proj[10] > 0, looking down +z).  The near cull is !(d > near_plane); d replaces clip.w wherever the
+ *           perspective rule uses it: the fp16 depth of GaussianRenderData, the sort key, the depth target and the
+ *           total-ink cull's depth;
+ *   screen  ndc = (clip.x, clip.y) without a division, then the same pixel-centred mapping;
+ *   cov     J = diag(width * proj[0] * 0.5f, height * proj[5] * 0.5f), the signed entries, every other entry 0:
+ *           no 1/z, no tan clamp, no third column; then T = J W, T C T^T and + 0.3f on the diagonal as before;
+ *   colour  all rays are parallel: the SH direction is the uniform normalize(-sigma * (view[2], view[6], view[10])),
+ *           from the scene toward the camera; camera.position is ignored.  Degree 0 is unchanged.
+ * A perspective frame's bytes, kernels and schedule are what they were; an orthographic frame keeps blend-unit costs
+ * of its own.  Out of scope: reversed-Z or otherwise unconventional proj[10]; skewed or oblique projections
+ * (proj[1], proj[4], proj[8], proj[9] act on the mean through clip, but not on J); gsm_global_render, _views, _batch
+ * and the older single-purpose entries, which get no flag; the DepthFirst, Local and multi-GPU renderers. */
+#define GSM_FRAME_ORTHOGRAPHIC 2u
+
+/* gsm_global_select_mask in an orthographic viewport: the same signature, checks (in the same order), match rule
+ * and state update, with the gaussians projected by the orthographic rule above -- the means are those of an
+ * orthographic frame of the same camera, width and height. */
+gsm_status gsm_global_select_mask_ortho(gsm_renderer *renderer, void *stream, const gsm_gaussian_input *input,
+                                        const gsm_camera_params *camera, uint32_t width, uint32_t height,
+                                        const void *mask_u8, size_t mask_pitch_bytes, uint8_t *state,
+                                        const gsm_global_style *styles, uint32_t style_count,
+                                        uint32_t and_mask, uint32_t xor_mask, uint32_t *matched);
 
 /* Select what is visible: the state bytes of the gaussians of one object that a pick image shows
  * under a mask.  The handle's last enqueued frame must be a pick frame (any entry with a pick target) of
@@ -569,7 +604,7 @@ gsm_status gsm_global_select_pick(gsm_renderer *renderer, void *stream,
  *
  * Checked before anything is enqueued; the first failing row decides, within a row the lowest frame index:
  *   GSM_ERR_MISSING_REQUIRED_BUFFER  frames NULL with frame_count >= 1;
- *   GSM_ERR_INVALID_ARGUMENT         a frame with flags != 0;
+ *   GSM_ERR_INVALID_ARGUMENT         a frame with a flags bit other than GSM_FRAME_ORTHOGRAPHIC set;
  *   GSM_ERR_UNSUPPORTED              a frame with object_count != 1 (composites inside a batch are out of scope);
  *   GSM_ERR_MISSING_REQUIRED_BUFFER  a frame's objects NULL;
  *   then the rows of gsm_global_render_batch, in its order, applied to (objects[0].input, objects[0].camera, width,
