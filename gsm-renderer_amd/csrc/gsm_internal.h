@@ -432,53 +432,39 @@ constexpr uint32_t kWideMaxBits = 11, kWideBins = 1u << kWideMaxBits;
 constexpr size_t kSortTotalsWords = kWideBins;
 inline SortSpace sort_space(const DeviceArena& A) { return SortSpace{A.radixHist, A.radixHistBytes, A.radixBinTotals, kSortTotalsWords}; }
 
-// project + cull + SH + tile count + per-block count sums (GlobalShaders.metal:19-123, 563-616)
-// ortho / anyOrtho (every projection launcher below but the views'): the orthographic instances --
-// k_project_ortho and its styled / compose forms for a frame whose flag is set (args and the compose entries then
-// carry the orthographic uniforms, see ProjectArgs), k_project_batch_ortho(_styled) for a batch in which some view's
-// `ortho` word is set.  false launches the kernels the frame launched before the flag existed.
-void launch_project(bool halfInput, uint32_t shDegree, const void* world, const void* harmonics,
-                    const ProjectArgs& args, const DeviceArena& A, hipStream_t stream, bool ortho = false);
-// the same for a batch of views (k_project_views): args.count gaussians per view, vb.views views; entries
-// [first, first + n) of the device array filled from `chunk` by launch_fill_views (n <= kViewChunk)
-void launch_project_views(bool halfInput, uint32_t shDegree, const void* world, const void* harmonics,
-                          const ProjectArgs& args, const ViewBatch& vb, const DeviceArena& A, hipStream_t stream);
+// project + cull + SH + tile count + per-block count sums (GlobalShaders.metal:19-123, 563-616): the projection
+// launch of a Global frame of any kind.  The payload's kind picks the kernel and supplies the per-view or per-object
+// entries; world / harmonics are the scene of a Single or Views frame (a Batch's and a Compose's travel in their
+// entries); `args` holds the frame's own arguments, or what a batch shares (the thresholds, the capacity, the
+// schedule).
+//   Single  -> k_project: args.count gaussians, an item is its gaussian id
+//   Views   -> k_project_views: args.count gaussians per view, vb.views views
+//   Batch   -> k_project_batch: every block's scene, count, camera terms and tile grid come from its
+//              view's entry
+//   Compose -> k_project_compose: every block's scene, count and camera terms come from its object's
+//              entry, on the frame's own tile grid
+// style (nullable; Single, Batch, Compose): the _styled kernel of the kind -- the style of every
+// gaussian's state byte, from style->table, applied where its four u8 bytes are formed.  A Single frame's state bytes
+// are style->state / defaultState; a Compose's travel in its entries, a Batch's in bf.extras (required then).
+// ortho (Single, Batch, Compose): the _ortho kernel of the kind -- for a Single or Compose frame whose
+// flag is set (args and the compose entries then carry the orthographic uniforms, see ProjectArgs), for a Batch in
+// which some view's `ortho` word is set.  false launches the kernels the frame launched before the flag existed.
+// An empty frame launches nothing unless args.schedUnits asks for the blend units to be ordered.
+void launch_project(bool halfInput, uint32_t shDegree, const FramePayload& payload, const void* world,
+                    const void* harmonics, const ProjectArgs& args, const StyleArgs* style, bool ortho,
+                    const DeviceArena& A, hipStream_t stream);
+// The device arrays behind the payloads and the style table are filled from kernel arguments, a chunk per launch:
+// entries [first, first + n) of the array from `chunk` (n <= kViewChunk / kBatchChunk / kExtrasChunk /
+// kComposeChunk).  launch_fill_batch also writes those views' ranges of the block and tile tables, and
+// launch_fill_compose those objects' ranges of the block table (at most maxBlocks / maxTiles entries of a table are
+// written, whatever the entries say); launch_fill_styles writes the 256-entry table.
 void launch_fill_views(const ViewChunk& chunk, uint32_t first, uint32_t n, ViewArgs* dst, hipStream_t stream);
-// a batch of views of different scenes and sizes (k_project_batch): every block's scene, count,
-// camera terms and tile grid come from its view's entry; `args` holds what the batch shares (the thresholds,
-// the capacity, the schedule).  launch_fill_batch writes entries [first, first + n) of the device array from
-// `chunk` (n <= kBatchChunk) and those views' ranges of the block and tile tables (at most maxBlocks / maxTiles
-// entries of either table are written, whatever the entries say).
-void launch_project_batch(bool halfInput, uint32_t shDegree, const ProjectArgs& args, const BatchFrame& bf,
-                          const DeviceArena& A, hipStream_t stream, bool anyOrtho = false);
 void launch_fill_batch(const BatchChunk& chunk, uint32_t first, uint32_t n, BatchViewArgs* dst, uint16_t* blockView,
                        uint32_t maxBlocks, uint16_t* tileView, uint32_t maxTiles, hipStream_t stream);
-// a batch with options (gsm_global_render_frames): launch_fill_batch_extras writes entries [first,
-// first + n) of the per-view options array from `chunk` (n <= kExtrasChunk); launch_project_batch_styled is
-// k_project_batch with the style step of the views whose line says so (bf.extras, styleTable: both required)
 void launch_fill_batch_extras(const ExtrasChunk& chunk, uint32_t first, uint32_t n, BatchExtras* dst,
                               hipStream_t stream);
-void launch_project_batch_styled(bool halfInput, uint32_t shDegree, const ProjectArgs& args, const BatchFrame& bf,
-                                 const uint2* styleTable, const DeviceArena& A, hipStream_t stream,
-                                 bool anyOrtho = false);
-// several posed objects on the frame's own tile grid (k_project_compose): every block's scene,
-// count and camera terms come from its object's entry; `args` holds the frame's (the grid, the rows, the
-// thresholds, the capacity, the schedule).  launch_fill_compose writes entries [first, first + n) of the device
-// array from `chunk` (n <= kComposeChunk) and those objects' ranges of the block table (at most maxBlocks
-// entries of it are written, whatever the entries say).
-void launch_project_compose(bool halfInput, uint32_t shDegree, const ProjectArgs& args, const ComposeFrame& cf,
-                            const DeviceArena& A, hipStream_t stream, bool ortho = false);
 void launch_fill_compose(const ComposeChunk& chunk, uint32_t first, uint32_t n, ComposeObjectArgs* dst,
                          uint16_t* blockObject, uint32_t maxBlocks, hipStream_t stream);
-// the styled frames (k_project_styled, k_project_compose_styled): the projections above with the
-// style of every gaussian's state byte applied where its four u8 bytes are formed; a composite's state pointers
-// travel in its entries.  launch_fill_styles writes the 256-entry table from `chunk`.
-void launch_project_styled(bool halfInput, uint32_t shDegree, const void* world, const void* harmonics,
-                           const ProjectArgs& args, const StyleArgs& style, const DeviceArena& A, hipStream_t stream,
-                           bool ortho = false);
-void launch_project_compose_styled(bool halfInput, uint32_t shDegree, const ProjectArgs& args, const ComposeFrame& cf,
-                                   const uint2* styleTable, const DeviceArena& A, hipStream_t stream,
-                                   bool ortho = false);
 void launch_fill_styles(const StyleChunk& chunk, uint2* dst, hipStream_t stream);
 // gsm_global_select_mask (k_select_mask): the state bytes of the gaussians whose fp16 mean lies on
 // a nonzero mask byte become (old & andMask) ^ xorMask; *matched (nullable, zeroed by the caller) counts them.

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <tuple>
 #include <type_traits>
 
 #include "gsm_device.h"
@@ -1310,46 +1311,56 @@ static void dispatch_sh(bool halfInput, uint32_t deg, F&& f) {
 // the projection grids: the items' blocks, plus one workgroup that orders the blend units (a.schedUnits)
 static dim3 project_grid(uint32_t blocks, const ProjectArgs& a) { return dim3(blocks + (a.schedUnits ? 1u : 0u)); }
 
-void launch_project(bool halfInput, uint32_t deg, const void* world, const void* harm,
-                    const ProjectArgs& a, const DeviceArena& A, hipStream_t s, bool ortho) {
-    const uint32_t blocks = (a.count + kProjectBlock - 1) / kProjectBlock;
+// The projection launch of a Global frame: the kernel of the payload's kind, styled when `style` is given,
+// orthographic when `ortho` is set (a Batch: when some view is).  Views frames are neither.
+void launch_project(bool halfInput, uint32_t deg, const FramePayload& payload, const void* world, const void* harm,
+                    const ProjectArgs& a, const StyleArgs* style, bool ortho, const DeviceArena& A, hipStream_t s) {
+    const ViewBatch* vb = payload.views();
+    const BatchFrame* bf = payload.batch();
+    const ComposeFrame* cf = payload.compose();
+    const uint32_t blocks = cf ? cf->blocks : bf ? bf->blocks : vb ? vb->views * vb->blocksPerView
+                                                                  : (a.count + kProjectBlock - 1) / kProjectBlock;
     if (blocks == 0 && a.schedUnits == 0) return;  // (an empty frame still orders its blend units)
+    // the arguments every projection kernel takes between its own first and last ones
+    const auto out = std::make_tuple(A.renderData, A.bounds, A.rec, A.tileCounts, A.tileMasks, A.blockSums,
+                                     A.sincosTable, A.unitCost, A.unitOrder, A.costMax);
     dispatch_sh(halfInput, deg, [&](auto H, auto D) {
-        const auto k = ortho ? k_project_ortho<decltype(H)::value, decltype(D)::value>
-                             : k_project<decltype(H)::value, decltype(D)::value>;
-        hipLaunchKernelGGL(k, project_grid(blocks, a),
-                           dim3(kProjectBlock), 0, s, world, harm, a, A.renderData, A.bounds, A.rec, A.tileCounts,
-                           A.tileMasks, A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax);
-    });
-}
-
-void launch_project_views(bool halfInput, uint32_t deg, const void* world, const void* harm, const ProjectArgs& a,
-                          const ViewBatch& vb, const DeviceArena& A, hipStream_t s) {
-    const uint32_t blocks = vb.views * vb.blocksPerView;
-    if (blocks == 0 && a.schedUnits == 0) return;  // (an empty batch still orders its blend units)
-    dispatch_sh(halfInput, deg, [&](auto H, auto D) {
-        hipLaunchKernelGGL((k_project_views<decltype(H)::value, decltype(D)::value>), project_grid(blocks, a),
-                           dim3(kProjectBlock), 0, s, world, harm, a, vb.args,
-                           vb.blocksPerView ? vb.blocksPerView : 1u, A.renderData, A.bounds, A.rec, A.tileCounts,
-                           A.tileMasks, A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax);
+        constexpr bool h = decltype(H)::value;
+        constexpr int d = decltype(D)::value;
+        const auto launch = [&](auto kernel, const auto& first, const auto& last) {
+            std::apply(
+                [&](const auto&... args) {
+                    hipLaunchKernelGGL(kernel, project_grid(blocks, a), dim3(kProjectBlock), 0, s, args...);
+                },
+                std::tuple_cat(first, out, last));
+        };
+        const auto none = std::make_tuple();
+        if (cf && style)
+            launch(ortho ? k_project_compose_ortho_styled<h, d> : k_project_compose_styled<h, d>,
+                   std::make_tuple(a, cf->args, cf->blockObject), std::make_tuple(style->table));
+        else if (cf)
+            launch(ortho ? k_project_compose_ortho<h, d> : k_project_compose<h, d>,
+                   std::make_tuple(a, cf->args, cf->blockObject), none);
+        else if (bf && style)  // (the views' state bytes travel in bf->extras)
+            launch(ortho ? k_project_batch_ortho_styled<h, d> : k_project_batch_styled<h, d>,
+                   std::make_tuple(a, bf->args, bf->blockView, bf->extras), std::make_tuple(style->table));
+        else if (bf)
+            launch(ortho ? k_project_batch_ortho<h, d> : k_project_batch<h, d>,
+                   std::make_tuple(a, bf->args, bf->blockView), none);
+        else if (vb)
+            launch(k_project_views<h, d>,
+                   std::make_tuple(world, harm, a, vb->args, vb->blocksPerView ? vb->blocksPerView : 1u), none);
+        else if (style)
+            launch(ortho ? k_project_ortho_styled<h, d> : k_project_styled<h, d>, std::make_tuple(world, harm, a),
+                   std::make_tuple(style->table, style->state, style->defaultState));
+        else
+            launch(ortho ? k_project_ortho<h, d> : k_project<h, d>, std::make_tuple(world, harm, a), none);
     });
 }
 
 void launch_fill_views(const ViewChunk& chunk, uint32_t first, uint32_t n, ViewArgs* dst, hipStream_t s) {
     if (n == 0) return;
     hipLaunchKernelGGL(k_fill_views, dim3(1), dim3(256), 0, s, chunk, n > kViewChunk ? kViewChunk : n, dst + first);
-}
-
-void launch_project_batch(bool halfInput, uint32_t deg, const ProjectArgs& a, const BatchFrame& bf,
-                          const DeviceArena& A, hipStream_t s, bool anyOrtho) {
-    if (bf.blocks == 0 && a.schedUnits == 0) return;  // (an empty batch still orders its blend units)
-    dispatch_sh(halfInput, deg, [&](auto H, auto D) {
-        const auto k = anyOrtho ? k_project_batch_ortho<decltype(H)::value, decltype(D)::value>
-                                : k_project_batch<decltype(H)::value, decltype(D)::value>;
-        hipLaunchKernelGGL(k, project_grid(bf.blocks, a),
-                           dim3(kProjectBlock), 0, s, a, bf.args, bf.blockView, A.renderData, A.bounds, A.rec,
-                           A.tileCounts, A.tileMasks, A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax);
-    });
 }
 
 void launch_fill_batch(const BatchChunk& chunk, uint32_t first, uint32_t n, BatchViewArgs* dst, uint16_t* blockView,
@@ -1365,63 +1376,11 @@ void launch_fill_batch_extras(const ExtrasChunk& chunk, uint32_t first, uint32_t
                        dst);
 }
 
-void launch_project_batch_styled(bool halfInput, uint32_t deg, const ProjectArgs& a, const BatchFrame& bf,
-                                 const uint2* styleTable, const DeviceArena& A, hipStream_t s, bool anyOrtho) {
-    if (bf.blocks == 0 && a.schedUnits == 0) return;  // (an empty batch still orders its blend units)
-    dispatch_sh(halfInput, deg, [&](auto H, auto D) {
-        const auto k = anyOrtho ? k_project_batch_ortho_styled<decltype(H)::value, decltype(D)::value>
-                                : k_project_batch_styled<decltype(H)::value, decltype(D)::value>;
-        hipLaunchKernelGGL(k,
-                           project_grid(bf.blocks, a), dim3(kProjectBlock), 0, s, a, bf.args, bf.blockView, bf.extras,
-                           A.renderData, A.bounds, A.rec, A.tileCounts, A.tileMasks, A.blockSums, A.sincosTable,
-                           A.unitCost, A.unitOrder, A.costMax, styleTable);
-    });
-}
-
-void launch_project_compose(bool halfInput, uint32_t deg, const ProjectArgs& a, const ComposeFrame& cf,
-                            const DeviceArena& A, hipStream_t s, bool ortho) {
-    if (cf.blocks == 0 && a.schedUnits == 0) return;  // (an empty composite still orders its blend units)
-    dispatch_sh(halfInput, deg, [&](auto H, auto D) {
-        const auto k = ortho ? k_project_compose_ortho<decltype(H)::value, decltype(D)::value>
-                             : k_project_compose<decltype(H)::value, decltype(D)::value>;
-        hipLaunchKernelGGL(k, project_grid(cf.blocks, a),
-                           dim3(kProjectBlock), 0, s, a, cf.args, cf.blockObject, A.renderData, A.bounds, A.rec,
-                           A.tileCounts, A.tileMasks, A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax);
-    });
-}
-
 void launch_fill_compose(const ComposeChunk& chunk, uint32_t first, uint32_t n, ComposeObjectArgs* dst,
                          uint16_t* blockObject, uint32_t maxBlocks, hipStream_t s) {
     if (n == 0) return;
     hipLaunchKernelGGL(k_fill_compose, dim3(1), dim3(256), 0, s, chunk, first, n > kComposeChunk ? kComposeChunk : n,
                        dst, blockObject, maxBlocks);
-}
-
-void launch_project_styled(bool halfInput, uint32_t deg, const void* world, const void* harm, const ProjectArgs& a,
-                           const StyleArgs& st, const DeviceArena& A, hipStream_t s, bool ortho) {
-    const uint32_t blocks = (a.count + kProjectBlock - 1) / kProjectBlock;
-    if (blocks == 0 && a.schedUnits == 0) return;  // (an empty frame still orders its blend units)
-    dispatch_sh(halfInput, deg, [&](auto H, auto D) {
-        const auto k = ortho ? k_project_ortho_styled<decltype(H)::value, decltype(D)::value>
-                             : k_project_styled<decltype(H)::value, decltype(D)::value>;
-        hipLaunchKernelGGL(k, project_grid(blocks, a),
-                           dim3(kProjectBlock), 0, s, world, harm, a, A.renderData, A.bounds, A.rec, A.tileCounts,
-                           A.tileMasks, A.blockSums, A.sincosTable, A.unitCost, A.unitOrder, A.costMax, st.table,
-                           st.state, st.defaultState);
-    });
-}
-
-void launch_project_compose_styled(bool halfInput, uint32_t deg, const ProjectArgs& a, const ComposeFrame& cf,
-                                   const uint2* styleTable, const DeviceArena& A, hipStream_t s, bool ortho) {
-    if (cf.blocks == 0 && a.schedUnits == 0) return;  // (an empty composite still orders its blend units)
-    dispatch_sh(halfInput, deg, [&](auto H, auto D) {
-        const auto k = ortho ? k_project_compose_ortho_styled<decltype(H)::value, decltype(D)::value>
-                             : k_project_compose_styled<decltype(H)::value, decltype(D)::value>;
-        hipLaunchKernelGGL(k,
-                           project_grid(cf.blocks, a), dim3(kProjectBlock), 0, s, a, cf.args, cf.blockObject,
-                           A.renderData, A.bounds, A.rec, A.tileCounts, A.tileMasks, A.blockSums, A.sincosTable,
-                           A.unitCost, A.unitOrder, A.costMax, styleTable);
-    });
 }
 
 void launch_fill_styles(const StyleChunk& chunk, uint2* dst, hipStream_t s) {

@@ -328,19 +328,14 @@ gsm_status GlobalRenderer::renderFrame(hipStream_t s, const gsm_gaussian_input& 
     rq.pick = extras.pick;
     rq.occluder = extras.occluder;
     rq.orthographic = ortho;
-    const uint32_t deg = sh_degree(in.sh_components);
-    const bool half = config_.precision == GSM_PRECISION_FLOAT16;
+    rq.world = in.gaussians;
+    rq.harm = in.harmonics;
+    rq.shDegree = sh_degree(in.sh_components);
     if (style) {
         if ((st = fillStyleTable(s, style->styles, style->styleCount)) != GSM_OK) return st;
-        const StyleArgs sa{arena_.styleTable, style->states[0].state, style->states[0].default_state};
-        rq.styled = true;
-        return runFrame(s, rq, [&](const ProjectArgs& pa) {
-            launch_project_styled(half, deg, in.gaussians, in.harmonics, pa, sa, arena_, s, ortho);
-        });
+        rq.style = StyleArgs{arena_.styleTable, style->states[0].state, style->states[0].default_state};
     }
-    return runFrame(s, rq, [&](const ProjectArgs& pa) {
-        launch_project(half, deg, in.gaussians, in.harmonics, pa, arena_, s, ortho);
-    });
+    return runFrame(s, rq);
 }
 
 bool GlobalRenderer::styleSourceOk(const StyleSource& style, uint32_t stateCount) {
@@ -493,11 +488,10 @@ gsm_status GlobalRenderer::renderViews(hipStream_t s, const gsm_gaussian_input& 
     vb.args = arena_.viewArgs;
     rq.payload.colorViewStride = colorStride;
     rq.payload.depthViewStride = depthStride;
-    const uint32_t deg = sh_degree(in.sh_components);
-    const bool half = config_.precision == GSM_PRECISION_FLOAT16;
-    return runFrame(s, rq, [&](const ProjectArgs& pa) {
-        launch_project_views(half, deg, in.gaussians, in.harmonics, pa, vb, arena_, s);
-    });
+    rq.world = in.gaussians;
+    rq.harm = in.harmonics;
+    rq.shDegree = sh_degree(in.sh_components);
+    return runFrame(s, rq);
 }
 
 gsm_status GlobalRenderer::renderBatch(hipStream_t s, const gsm_global_view* views, uint32_t viewCount) {
@@ -702,8 +696,7 @@ gsm_status GlobalRenderer::enqueueBatch(hipStream_t s, const gsm_global_view* vi
     bf.args = arena_.batchArgs;
     bf.blockView = arena_.batchBlockView;
     bf.tileView = arena_.batchTileView;
-    const uint32_t deg = sh_degree(sh);
-    const bool half = config_.precision == GSM_PRECISION_FLOAT16;
+    rq.shDegree = sh_degree(sh);
     if (options) {
         // the host copy of the per-view options, to the device array in kernel-argument chunks as the entries
         // above; the alignment bits follow each view's own pointer and pitch, as launch_blend's for a single frame
@@ -737,14 +730,11 @@ gsm_status GlobalRenderer::enqueueBatch(hipStream_t s, const gsm_global_view* vi
         if (table) {
             const gsm_status st = fillStyleTable(s, table->styles, table->styleCount);
             if (st != GSM_OK) return st;
-            rq.styled = true;
-            return runFrame(s, rq, [&](const ProjectArgs& pa) {
-                launch_project_batch_styled(half, deg, pa, bf, arena_.styleTable, arena_, s, anyOrtho);
-            });
+            rq.style.table = arena_.styleTable;  // (the views' state bytes travel in their options lines)
         }
     }
     // (a batch without an orthographic view launches the kernels it launched before the flag existed)
-    return runFrame(s, rq, [&](const ProjectArgs& pa) { launch_project_batch(half, deg, pa, bf, arena_, s, anyOrtho); });
+    return runFrame(s, rq);
 }
 
 gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* objects, uint32_t objectCount,
@@ -850,16 +840,12 @@ gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* 
     cf.blockObject = arena_.composeBlockObject;
     rq.pick = pick;
     rq.occluder = occluder;
-    const uint32_t deg = sh_degree(sh);
-    const bool half = config_.precision == GSM_PRECISION_FLOAT16;
+    rq.shDegree = sh_degree(sh);
     if (style) {
         if ((st = fillStyleTable(s, style->styles, style->styleCount)) != GSM_OK) return st;
-        rq.styled = true;
-        return runFrame(s, rq, [&](const ProjectArgs& pa) {
-            launch_project_compose_styled(half, deg, pa, cf, arena_.styleTable, arena_, s, ortho);
-        });
+        rq.style.table = arena_.styleTable;  // (the objects' state bytes travel in their entries)
     }
-    return runFrame(s, rq, [&](const ProjectArgs& pa) { launch_project_compose(half, deg, pa, cf, arena_, s, ortho); });
+    return runFrame(s, rq);
 }
 
 gsm_status GlobalRenderer::renderRecords(hipStream_t s, const void* records, uint32_t count, uint32_t width,
@@ -874,10 +860,11 @@ gsm_status GlobalRenderer::renderRecords(hipStream_t s, const void* records, uin
     std::memset(&cam, 0, sizeof(cam));
     FrameRequest rq = request(FrameKind::Records, frameArgs(cam, width, height, count, 1), width, height,
                               FrameTargets{color, colorPitch, depth, depthPitch});
+    rq.records = records;
     rq.devCount = devCount;
     rq.preOrdered = preOrdered;
     rq.blendArrive = blendArrive;
-    return runFrame(s, rq, [&](const ProjectArgs& pa) { launch_records_in(records, pa, arena_, s, devCount); });
+    return runFrame(s, rq);
 }
 
 gsm_status GlobalRenderer::preparePartition(const gsm_gaussian_input& in, const gsm_camera_params& camp,
@@ -1031,7 +1018,7 @@ const ScheduleKey& GlobalRenderer::requestKey(const FrameRequest& rq, uint32_t* 
     // (a batch with options: the union over its views, so such batches keep unit costs of their own)
     key_[ScheduleKey::kPick] = (rq.pick || rq.anyPick) ? 1u : 0u;
     key_[ScheduleKey::kOccluded] = (rq.occluder || rq.anyOccluder) ? 1u : 0u;
-    key_[ScheduleKey::kStyled] = rq.styled ? 1u : 0u;
+    key_[ScheduleKey::kStyled] = rq.style.table ? 1u : 0u;
     key_[ScheduleKey::kUnitsPerTile] = blend_units_per_tile(*tiles, dev_.numCUs);
     key_[ScheduleKey::kWidth] = rq.width;
     key_[ScheduleKey::kHeight] = rq.height;
@@ -1056,8 +1043,7 @@ uint32_t GlobalRenderer::scheduleUnits(hipStream_t s, const ScheduleKey& key, ui
     return tuning_.costOrder ? units : 0u;
 }
 
-template <class Front>
-gsm_status GlobalRenderer::runFrame(hipStream_t s, const FrameRequest& rq, Front&& front) {
+gsm_status GlobalRenderer::runFrame(hipStream_t s, const FrameRequest& rq) {
     (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's: the launches below are checked)
     const ProjectArgs& a = rq.args;
     const FrameTargets& tg = rq.targets;
@@ -1102,7 +1088,12 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const FrameRequest& rq, Front
 
     timer_.beginFrame();  // every stage bracketed by events, only the blend, or none
     timer_.record(0, s);
-    front(fa);  // the projection (or records) launch; its block 0 orders the blend units (fa.schedUnits)
+    // the projection (or records) launch; its block 0 orders the blend units (fa.schedUnits)
+    if (rq.payload.kind == FrameKind::Records)
+        launch_records_in(rq.records, fa, arena_, s, rq.devCount);
+    else
+        launch_project(config_.precision == GSM_PRECISION_FLOAT16, rq.shDegree, rq.payload, rq.world, rq.harm, fa,
+                       rq.style.table ? &rq.style : nullptr, rq.orthographic, arena_, s);
     timer_.record(1, s);
     // (a frame of few blocks: the scatter's workgroups add up the block counts themselves).  The records path
     // (devCount: a multi-GPU slab) sizes its grids for the receive capacity but adds up only the blocks of

@@ -148,7 +148,7 @@ class GlobalRenderer {
     // orthographic: the uniforms of the orthographic rule in place of the perspective terms (ProjectArgs)
     ProjectArgs frameArgs(const gsm_camera_params& camera, uint32_t width, uint32_t height, uint32_t count,
                           uint32_t shComponents, bool orthographic = false) const;
-    // One description of a frame: what runFrame enqueues after `front` filled the per-gaussian arrays.
+    // One description of a frame: everything runFrame enqueues, the projection (or records) launch in front.
     // (Views: args holds what the views share, the targets are view 0's.  Batch: args holds what the views share,
     // nothing per view.  Compose: args is the frame's, as a single frame's; only the items differ.)
     struct FrameRequest {
@@ -156,9 +156,17 @@ class GlobalRenderer {
         uint32_t width = 0, height = 0;
         FrameTargets targets;
         FramePayload payload;  // the kind and its payload
+        // what the front launch reads: a Single or Views frame's scene (a Batch's and a Compose's travel in their
+        // entries), the SH degree of the frame's scenes, a Records frame's received records
+        const void* world = nullptr;
+        const void* harm = nullptr;
+        uint32_t shDegree = 0;
+        const void* records = nullptr;
         const PickTarget* pick = nullptr;
         const OccluderSource* occluder = nullptr;
-        bool styled = false;  // the projection applies styles: the walks are the frame's own (schedule key)
+        // table non-null: the projection applies styles (state / defaultState: a Single frame's), and the walks are
+        // the frame's own (schedule key)
+        StyleArgs style;
         // the projection follows the orthographic rule (a Batch: some view's does): the footprints, and with them
         // the walks, are the frame's own (schedule key)
         bool orthographic = false;
@@ -173,9 +181,8 @@ class GlobalRenderer {
     };
     FrameRequest request(FrameKind kind, const ProjectArgs& args, uint32_t width, uint32_t height,
                          const FrameTargets& targets) const;
-    // scan, scatter, sort, headers and blend around front(args): the projection (or records) launch
-    template <class Front>
-    gsm_status runFrame(hipStream_t s, const FrameRequest& rq, Front&& front);
+    // the projection (or records) launch, then scan, scatter, sort, headers and blend
+    gsm_status runFrame(hipStream_t s, const FrameRequest& rq);
     // the request's schedule key in key_ (reserved: no allocation) and the tiles its blend units cover
     const ScheduleKey& requestKey(const FrameRequest& rq, uint32_t* tiles);
     // the blend schedule's unit count for a frame of that key over `tiles` tiles (0 when cost order is off), the
