@@ -242,6 +242,27 @@ gsm_status gsm_global_select_pick_ids(gsm_renderer* r, void* stream, const void*
                                   gaussian_count, and_mask, xor_mask, matched);
 }
 
+void gsm_global_keep_visible(const gsm_global_style* styles, uint32_t style_count, uint32_t keep[8]) {
+    gsm::keep_visible(styles, style_count, keep);
+}
+
+void gsm_global_keep_masked(uint32_t test_mask, uint32_t test_value, uint32_t keep[8]) {
+    gsm::keep_masked(test_mask, test_value, keep);
+}
+
+gsm_status gsm_global_extract(gsm_renderer* r, void* stream, const gsm_gaussian_input* input,
+                              const gsm_global_state* state, const uint32_t keep[8], const gsm_global_extract_out* out,
+                              uint32_t* kept) {
+    if (!r || !r->impl) return GSM_ERR_INVALID_ARGUMENT;
+    return r->impl->extract((hipStream_t)stream, input, state, keep, out, kept);
+}
+
+gsm_status gsm_global_state_histogram(gsm_renderer* r, void* stream, const uint8_t* state, uint32_t gaussian_count,
+                                      uint32_t* histogram) {
+    if (!r || !r->impl) return GSM_ERR_INVALID_ARGUMENT;
+    return r->impl->stateHistogram((hipStream_t)stream, state, gaussian_count, histogram);
+}
+
 gsm_status gsm_global_pick_owner(gsm_renderer* r, const uint32_t* items, uint32_t n, uint32_t* object,
                                  uint32_t* gaussian) {
     if (!r || !r->impl || (n > 0 && (!items || !object || !gaussian))) return GSM_ERR_INVALID_ARGUMENT;

@@ -376,6 +376,7 @@ struct DeviceArena {
     uint16_t* composeBlockObject = nullptr;    // [ceil(maxG / 256)] the entry of every projection block of a composite
     uint2* styleTable = nullptr;               // [kStyleEntries] packed styles (styled frames, select_mask; lazily)
     uint32_t* selectBitmap = nullptr;          // [ceil(maxG / 32)] one bit per gaussian id (select_pick; lazily)
+    uint32_t* extractBlocks = nullptr;         // [ceil(maxG / 256)] kept gaussians per block, then their scan (extract; lazily)
     uint16_t* expTable = nullptr;              // [65536]
     float2* sincosTable = nullptr;             // [kSincosEntries + 256]: sin/cos, then the byte table (det_byte_lut_entry)
 };
@@ -480,6 +481,33 @@ void launch_select_mask(bool halfInput, const void* world, const ProjectArgs& ar
 void launch_select_pick(const uint8_t* pick, size_t pickPitch, uint32_t width, uint32_t height, const uint8_t* mask,
                         size_t maskPitch, uint32_t base, uint32_t n, uint32_t* bitmap, uint8_t* state,
                         uint32_t andMask, uint32_t xorMask, uint32_t* matched, hipStream_t stream);
+// gsm_global_extract (gsm_edit.hip: k_extract_count, k_extract_scan, k_extract_move): the rows of the
+// gaussians whose state byte (state[g], or defaultState when state is null) has its bit in `keep`, in ascending id
+// order, into the outputs' first min(K, capacity) rows; *kept = K.  blockBase holds ceil(count / 256) words.  Three
+// launches in stream order; a count of 0 launches the scan alone, which writes *kept = 0.
+struct KeepSet {
+    uint32_t w[8];
+};
+struct ExtractArgs {
+    const uint8_t* records;    // count rows of recordBytes
+    const uint8_t* harmonics;  // count rows of harmonicsBytes (0: no harmonics)
+    const uint8_t* state;      // nullable
+    uint32_t defaultState;
+    uint32_t count;
+    KeepSet keep;
+    uint32_t* blockBase;
+    uint8_t* outRecords;
+    uint8_t* outHarmonics;
+    uint8_t* outState;  // nullable
+    uint32_t* outIds;   // nullable
+    uint32_t capacity;
+    uint32_t recordBytes;
+    uint64_t harmonicsBytes;
+};
+void launch_extract(const ExtractArgs& args, uint32_t* kept, hipStream_t stream);
+// gsm_global_state_histogram (k_state_histogram): histogram[s] = the number of g < count with state[g] == s; the 256
+// words are cleared here on the stream.
+void launch_state_histogram(const uint8_t* state, uint32_t count, uint32_t* histogram, hipStream_t stream);
 // exclusive scan of the per-block sums, total + clamp into the header (GlobalShaders.metal:685-712)
 // project gaussians [0, a.count) of world/harm (already offset to the rank's range) and pack
 // the records of each slab's gaussians into `send` (slab-major, ascending id), counts to sendCounts

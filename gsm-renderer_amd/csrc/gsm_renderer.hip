@@ -295,6 +295,49 @@ gsm_status GlobalRenderer::enqueueSelectPick(hipStream_t s, const void* pick, si
     return GSM_OK;
 }
 
+gsm_status GlobalRenderer::extract(hipStream_t s, const gsm_gaussian_input* in, const gsm_global_state* state,
+                                   const uint32_t* keep, const gsm_global_extract_out* out, uint32_t* kept) {
+    const bool half = config_.precision == GSM_PRECISION_FLOAT16;
+    gsm_status st = extract_check(maxGaussians_, half, in, state, keep, out, kept);
+    if (st != GSM_OK) return st;
+    if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
+    if (!arena_.extractBlocks) {  // (the handle's first extract: one word per block of 256 gaussians it can hold)
+        st = allocs_.alloc((void**)&arena_.extractBlocks,
+                           (((size_t)maxGaussians_ + kProjectBlock - 1) / kProjectBlock) * sizeof(uint32_t));
+        if (st != GSM_OK) return st;
+    }
+    ExtractArgs a{};
+    a.records = (const uint8_t*)in->gaussians;
+    a.harmonics = (const uint8_t*)in->harmonics;
+    a.state = state->state;
+    a.defaultState = state->default_state;
+    a.count = in->gaussian_count;
+    for (int k = 0; k < 8; ++k) a.keep.w[k] = keep[k];
+    a.blockBase = arena_.extractBlocks;
+    a.outRecords = (uint8_t*)out->gaussians;
+    a.outHarmonics = (uint8_t*)out->harmonics;
+    a.outState = out->state;
+    a.outIds = out->ids;
+    a.capacity = out->capacity;
+    a.recordBytes = extract_record_bytes(half);
+    a.harmonicsBytes = extract_harmonics_row_bytes(half, in->sh_components);
+    (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's)
+    launch_extract(a, kept, s);
+    if (hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;
+    return GSM_OK;
+}
+
+gsm_status GlobalRenderer::stateHistogram(hipStream_t s, const uint8_t* state, uint32_t gaussianCount,
+                                          uint32_t* histogram) {
+    const gsm_status st = state_histogram_check(maxGaussians_, state, gaussianCount, histogram);
+    if (st != GSM_OK) return st;
+    if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
+    (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's)
+    launch_state_histogram(state, gaussianCount, histogram, s);
+    if (hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;
+    return GSM_OK;
+}
+
 GlobalRenderer::FrameRequest GlobalRenderer::request(FrameKind kind, const ProjectArgs& args, uint32_t width,
                                                      uint32_t height, const FrameTargets& targets) const {
     FrameRequest rq;

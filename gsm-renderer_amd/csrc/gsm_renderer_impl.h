@@ -7,6 +7,7 @@
 
 #include "../../include/gsm_debug.h"
 #include "../../include/gsm_renderer.h"
+#include "gsm_extract_check.h"
 #include "gsm_host.h"
 #include "gsm_internal.h"
 #include "gsm_schedule_key.h"
@@ -75,6 +76,12 @@ class GlobalRenderer {
     gsm_status selectPickIds(hipStream_t stream, const void* pick, size_t pickPitch, uint32_t width, uint32_t height,
                              const void* mask, size_t maskPitch, uint8_t* state, uint32_t gaussianCount,
                              uint32_t andMask, uint32_t xorMask, uint32_t* matched);
+    // the rows of the gaussians whose state byte is in the keep set, in ascending id order (gsm_global_extract,
+    // DESIGN.md 28); the handle's last-frame state is neither read nor changed
+    gsm_status extract(hipStream_t stream, const gsm_gaussian_input* input, const gsm_global_state* state,
+                       const uint32_t* keep, const gsm_global_extract_out* out, uint32_t* kept);
+    // the number of gaussians of every state value (gsm_global_state_histogram)
+    gsm_status stateHistogram(hipStream_t stream, const uint8_t* state, uint32_t gaussianCount, uint32_t* histogram);
     // items of the last enqueued pick frame -> (object of the call, gaussian id within it); host only, no sync
     gsm_status pickOwner(const uint32_t* items, uint32_t n, uint32_t* object, uint32_t* gaussian) const;
 

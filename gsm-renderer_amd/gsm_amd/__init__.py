@@ -263,6 +263,15 @@ GLOBAL_FRAME_BYTES = 112  # include/gsm_renderer.h: sizeof(gsm_global_frame), as
 assert C.sizeof(_GlobalFrame) == GLOBAL_FRAME_BYTES
 
 
+class _ExtractOut(C.Structure):  # gsm_global_extract_out
+    _fields_ = [("gaussians", C.c_void_p), ("harmonics", C.c_void_p), ("state", C.c_void_p), ("ids", C.c_void_p),
+                ("capacity", C.c_uint32), ("pad", C.c_uint32)]
+
+
+EXTRACT_OUT_BYTES = 40  # include/gsm_renderer.h: sizeof(gsm_global_extract_out), asserted there
+assert C.sizeof(_ExtractOut) == EXTRACT_OUT_BYTES
+
+
 class _Counters(C.Structure):
     _fields_ = [("total_assignments", C.c_uint32), ("max_capacity", C.c_uint32),
                 ("padded_count", C.c_uint32), ("overflow", C.c_uint32), ("tiles_x", C.c_uint32),
@@ -342,6 +351,11 @@ _SIGNATURES = {
     "gsm_global_select_pick_ids": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                     C.c_void_p], C.c_int),
+    "gsm_global_keep_visible": ([C.POINTER(_Style), C.c_uint32, C.POINTER(C.c_uint32)], None),
+    "gsm_global_keep_masked": ([C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)], None),
+    "gsm_global_extract": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_State), C.POINTER(C.c_uint32),
+                            C.POINTER(_ExtractOut), C.c_void_p], C.c_int),
+    "gsm_global_state_histogram": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p], C.c_int),
     "gsm_global_render_stereo": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera),
                                   C.POINTER(_Camera), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                   C.c_void_p, C.c_size_t], C.c_int),
@@ -863,6 +877,36 @@ class GlobalRenderer(_Renderer):
                                            _ptr(mask), mp, int(object), _ptr(state), int(gaussian_count),
                                            int(and_mask) & 0xFFFFFFFF, int(xor_mask) & 0xFFFFFFFF, _ptr(matched))
         _check(st, "gsm_global_select_pick")
+
+    def extract(self, input: GaussianInput, state, keep, out_gaussians, out_harmonics, out_state=None, out_ids=None,
+                capacity: Optional[int] = None, kept=None, stream=None):
+        """gsm_global_extract: the rows of the gaussians whose state byte has its bit in `keep`, in ascending id
+        order, into the first min(K, capacity) rows of the outputs; `kept` (an int32 / uint32 CUDA tensor of one
+        element; None: one is allocated) receives K and is returned.  state: as the styled entries take it (a uint8
+        CUDA tensor, an int for every gaussian's state, None for a NULL struct).  keep: a sequence of 8 words
+        (keep_visible, keep_masked; None: NULL).  out_state (uint8) and out_ids (int32 / uint32) may be None.
+        capacity defaults to the rows out_gaussians holds."""
+        inp = _Input(_ptr(input.gaussians), _ptr(input.harmonics), int(input.gaussian_count),
+                     int(input.sh_components))
+        if capacity is None:
+            record = 32 if int(self.config.precision) == RenderPrecision.FLOAT16 else 48
+            capacity = 0 if out_gaussians is None else out_gaussians.numel() * out_gaussians.element_size() // record
+        if kept is None:
+            kept = torch.zeros(1, dtype=torch.int32, device=getattr(out_gaussians, "device", "cuda"))
+        out = _ExtractOut(_ptr(out_gaussians), _ptr(out_harmonics), _ptr(out_state), _ptr(out_ids), int(capacity), 0)
+        words = None if keep is None else (C.c_uint32 * 8)(*[int(w) & 0xFFFFFFFF for w in keep])
+        st = _lib().gsm_global_extract(self._h, _stream_handle(stream), C.byref(inp),
+                                       None if state is None else C.byref(_state_struct(state)), words, C.byref(out),
+                                       _ptr(kept))
+        _check(st, "gsm_global_extract")
+        return kept
+
+    def state_histogram(self, state, count: int, histogram, stream=None):
+        """gsm_global_state_histogram: histogram[s] (an int32 / uint32 CUDA tensor of 256 elements) becomes the
+        number of the first `count` bytes of `state` (a uint8 CUDA tensor) that equal s."""
+        st = _lib().gsm_global_state_histogram(self._h, _stream_handle(stream), _ptr(state), int(count),
+                                               _ptr(histogram))
+        _check(st, "gsm_global_state_histogram")
 
     def pick_owner(self, items):
         """gsm_global_pick_owner: items of the last enqueued pick frame (any integer array, host) ->
@@ -1437,6 +1481,22 @@ def sort_rank_probe(device: int = 0) -> bool:
     out = C.c_int(0)
     _check(_lib().gsm_debug_sort_rank_probe(int(device), C.byref(out)), "gsm_debug_sort_rank_probe")
     return bool(out.value)
+
+
+def keep_visible(styles, style_count: Optional[int] = None) -> list:
+    """gsm_global_keep_visible: the keep set (8 words) of the states a styled frame with the Style list `styles`
+    does not cull; None: every state.  style_count overrides the list's length."""
+    arr, n = _style_array(styles)
+    keep = (C.c_uint32 * 8)()
+    _lib().gsm_global_keep_visible(arr, n if style_count is None else int(style_count), keep)
+    return [int(w) for w in keep]
+
+
+def keep_masked(test_mask: int, test_value: int) -> list:
+    """gsm_global_keep_masked: the keep set (8 words) of the states s with (s & test_mask) == test_value."""
+    keep = (C.c_uint32 * 8)()
+    _lib().gsm_global_keep_masked(int(test_mask) & 0xFFFFFFFF, int(test_value) & 0xFFFFFFFF, keep)
+    return [int(w) for w in keep]
 
 
 def abi_version() -> int:

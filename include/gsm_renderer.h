@@ -361,7 +361,8 @@ gsm_status gsm_global_render_composite_occluded(gsm_renderer *renderer, void *st
 
 /* Per-gaussian styles (no reference analogue): gsm_global_render and gsm_global_render_composite
  * with one state byte per gaussian and a table of at most 256 styles, so an application shows a selection --
- * hides, highlights or fades splats -- without rewriting its scene.
+ * hides, highlights or fades splats -- without rewriting its scene while the user is selecting.  The step that
+ * does rewrite it (delete, crop, separate, export) is gsm_global_extract, below.
  *
  * Rule.  A gaussian's state s is its byte of the state array, or default_state when the array is NULL.  Its style
  * is S = styles[s] when s < style_count, otherwise the identity {tint_amount 0, opacity_scale 255, hidden 0}.  For
@@ -643,6 +644,87 @@ gsm_status gsm_global_select_pick_ids(gsm_renderer *renderer, void *stream,
                                       const void *mask_u8, size_t mask_pitch_bytes,
                                       uint8_t *state, uint32_t gaussian_count,
                                       uint32_t and_mask, uint32_t xor_mask, uint32_t *matched);
+
+/* Rewriting the scene by its state bytes (no reference analogue): the step after the selection --
+ * delete it, crop to it, separate it into an object of its own (which gsm_global_render_composite then poses),
+ * export what is visible -- on the device, from the state bytes the selects write and the styled frames read.
+ *
+ * A keep set is 256 bits, one per state value: bit (s & 31) of keep[s >> 5] says that a gaussian whose state byte
+ * is s is kept.  Two host-only helpers fill one:
+ *   gsm_global_keep_visible  bit s is set unless s < style_count and styles[s].hidden != 0 -- exactly the states the
+ *                            styled frames do not cull; styles NULL or style_count 0 sets all 256 bits, a
+ *                            style_count above 256 is read as 256;
+ *   gsm_global_keep_masked   bit s is set when (s & test_mask & 0xFF) == (test_value & 0xFF): "selection bit set"
+ *                            (b, b), "selection bit clear" (b, 0), "state equals v" (0xFF, v).
+ *
+ * gsm_global_extract.  Gaussian g < gaussian_count has the state s_g = state->state[g], or state->default_state
+ * when that pointer is NULL, and is kept when bit s_g of `keep` is set.  With g_0 < g_1 < ... < g_{K-1} the kept ids
+ * in ascending order, for every j < min(K, capacity): row j of out->gaussians is the byte copy of input record g_j
+ * (48 B, or 32 B for a half-precision handle), row j of out->harmonics the byte copy of input row g_j (3 *
+ * sh_components floats or halfs), out->state[j] = s_g_j and out->ids[j] = g_j.  *kept = K, the full count, not the
+ * clamped one: K > capacity says that the output is a prefix and how much room a second call needs.  No byte of any
+ * output at or past row min(K, capacity) is written; every byte before it is.  The ascending order is part of the
+ * contract: the Global sort breaks equal (tile, depth) keys by ascending id, so only an order-preserving removal
+ * keeps the styled entries' identity above byte for byte -- gsm_global_render of the scene extracted with
+ * gsm_global_keep_visible equals gsm_global_render_styled of the full scene when the hidden styles' other fields
+ * are the identity.  Rows are copied, never re-encoded: no arithmetic is added to the numeric contract.
+ *
+ * The structs and `keep` are host memory, consumed before the call returns; everything they point to, and `kept`,
+ * is device memory.  Enqueue-only on `stream` and capturable: a captured call replays the pointers, the keep set and
+ * default_state it was captured with, and reads the state bytes of the replay.  Nothing is allocated per call (the
+ * handle's first extract allocates ceil(max_gaussians / 256) words).  It neither reads nor changes the handle's
+ * last-frame state, and gsm_global_set_tile_rows does not concern it.  Extraction in place is not offered.
+ *
+ * Checks, all before anything is enqueued; the first failing row in this order decides:
+ *   GSM_ERR_INVALID_ARGUMENT         renderer NULL;
+ *   GSM_ERR_INVALID_GAUSSIAN_COUNT   gaussian_count > max_gaussians (the count of a NULL input cannot be read: that
+ *                                    call falls to the next row);
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  input, state, keep, out or kept NULL;
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  with a count > 0: input->gaussians NULL, or input->harmonics NULL while
+ *                                    sh_components > 0;
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  with a count > 0 and a capacity > 0: out->gaussians NULL, or out->harmonics
+ *                                    NULL while sh_components > 0;
+ *   GSM_ERR_INVALID_BUFFER_SIZE      kept or out->ids not 4-byte aligned;
+ *   GSM_ERR_INVALID_BUFFER_SIZE      out->gaussians not 16-byte aligned;
+ *   GSM_ERR_INVALID_BUFFER_SIZE      out->harmonics not aligned to its element (2 or 4 bytes);
+ *   GSM_ERR_INVALID_ARGUMENT         default_state > 255;
+ *   GSM_ERR_INVALID_ARGUMENT         an output's byte range meets one of the byte ranges the call reads or another
+ *                                    output's range: the outputs are `capacity` rows each and `kept` is 4 bytes; the
+ *                                    ranges read are gaussian_count rows each of the records, the harmonics and the
+ *                                    state array.
+ * A count of 0 writes *kept = 0 and nothing else.
+ *
+ * gsm_global_state_histogram.  histogram[s] (device, 256 words) becomes the number of g < gaussian_count with
+ * state[g] == s: overwritten, not added to; a count of 0 writes 256 zeros.  An editor's "n selected" readout, and,
+ * summed over a keep set, the exact capacity for an extract.  Enqueue-only and capturable.  Checks, in this order:
+ *   GSM_ERR_INVALID_ARGUMENT         renderer NULL;
+ *   GSM_ERR_INVALID_GAUSSIAN_COUNT   gaussian_count > max_gaussians;
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  histogram NULL, or state NULL with a count > 0;
+ *   GSM_ERR_INVALID_BUFFER_SIZE      histogram not 4-byte aligned.
+ *
+ * Out of scope: transforming the kept gaussians (baking a pose rotates the SH rows: arithmetic), merging scenes (a
+ * plain copy concatenates their rows), extraction in place, and the DepthFirst, Local and multi-GPU renderers,
+ * which have no state bytes. */
+typedef struct {
+    void *gaussians;   /* capacity records of the handle's precision (48 B or 32 B) */
+    void *harmonics;   /* capacity rows of 3 * sh_components floats or halfs; ignored when sh_components == 0 */
+    uint8_t *state;    /* nullable: capacity bytes, the kept gaussians' state bytes */
+    uint32_t *ids;     /* nullable: capacity words, the kept gaussians' ids in the input */
+    uint32_t capacity; /* rows the outputs can hold */
+    uint32_t pad;      /* ignored */
+} gsm_global_extract_out;
+#ifdef __cplusplus
+static_assert(sizeof(gsm_global_extract_out) == 40, "gsm_global_extract_out is 40 bytes");
+#else
+_Static_assert(sizeof(gsm_global_extract_out) == 40, "gsm_global_extract_out is 40 bytes");
+#endif
+void gsm_global_keep_visible(const gsm_global_style *styles, uint32_t style_count, uint32_t keep[8]);
+void gsm_global_keep_masked(uint32_t test_mask, uint32_t test_value, uint32_t keep[8]);
+gsm_status gsm_global_extract(gsm_renderer *renderer, void *stream, const gsm_gaussian_input *input,
+                              const gsm_global_state *state, const uint32_t keep[8],
+                              const gsm_global_extract_out *out, uint32_t *kept /* device */);
+gsm_status gsm_global_state_histogram(gsm_renderer *renderer, void *stream, const uint8_t *state,
+                                      uint32_t gaussian_count, uint32_t *histogram /* device, 256 words */);
 
 /* GlobalRenderer.renderStereo (GlobalRenderer.swift:240-255) calls fatalError for
  * every target; this entry returns GSM_ERR_UNSUPPORTED instead. */

@@ -11,7 +11,8 @@ Each of the two directories holds one `.s` file per `.hip` source, made with the
 
 after removing comments and the numbers of compiler-generated labels (`.LBB12_3` -> `.LBB_3`), which change when
 a function is added in front of another.  It prints one JSON document: per file the counts of identical, changed,
-missing and new symbols, and for every changed function both instruction counts.
+missing and new symbols, and for every changed function both instruction counts; `common_files_identical` says that
+every file of the parent is unchanged, `identical` that the tree also adds no file of its own.
 
     python3 tools/asm_compare.py PARENT_DIR TREE_DIR [--group NAME=REGEX ...] [-o OUT.json]
 
@@ -176,6 +177,9 @@ def main():
         result["files"][x] = r
         same = same and not r["all"]["differs"] and not r["all"]["missing"] and not r["new"]
     result["tree_only_files"] = sorted(x for x in os.listdir(a.tree_dir) if x.endswith(".s") and x not in names)
+    # common_files_identical: every file of the parent exists in the tree with every symbol identical and none new;
+    # identical: that, and the tree has no file of its own (a new translation unit alone makes it false)
+    result["common_files_identical"] = same
     result["identical"] = same and not result["tree_only_files"]
     text = json.dumps(result, indent=1) + "\n"
     if a.output:
