@@ -8,7 +8,118 @@
 #include "../../include/gsm_multigpu.h"
 #include "../../include/gsm_renderer.h"
 #include "gsm_internal.h"
+#include "gsm_frame_sort_check.h"
 #include "gsm_renderer_impl.h"
+
+namespace gsm {
+
+// gsm_debug_frame_sort (include/gsm_debug.h): what a renderer owns for its frame sort, and the calls
+// runFrame and the DepthFirst frame make on it.  No kernel of its own.
+class FrameSorter {
+   public:
+    static gsm_status create(uint32_t capacity, uint32_t maxTiles, int device, FrameSorter** out) {
+        FrameSorter* f = new (std::nothrow) FrameSorter;
+        if (!f) return GSM_ERR_FAILED_TO_ALLOCATE_BUFFER;
+        gsm_status st = pick_device(device, &f->dev_);
+        if (st == GSM_OK) {
+            f->allocs_.setDevice(f->dev_.id);
+            f->tuning_ = tuning_from_env(f->dev_.id);  // GSM_SORT_RANK / _WIDE / _SCAN, as a renderer's create
+            f->capacity_ = capacity;
+            f->maxTiles_ = maxTiles;
+            DeviceAllocations& M = f->allocs_;
+            for (int i = 0; i < 2; ++i) {
+                M.alloc(st, f->keys_[i], (size_t)capacity * 4);
+                M.alloc(st, f->vals_[i], (size_t)capacity * 4);
+                M.alloc(st, f->half_[i], (size_t)capacity * 4);
+            }
+            M.alloc(st, f->count_, 4);
+            f->histBytes_ = radix_workspace_bytes(capacity);
+            M.alloc(st, f->hist_, f->histBytes_);
+            M.alloc(st, f->binTotals_, kSortTotalsWords * sizeof(uint32_t));
+            M.alloc(st, f->buckets_, ((size_t)kWideBins + 1) * sizeof(uint32_t));
+            M.alloc(st, f->tileStart_, ((size_t)maxTiles + 1) * sizeof(uint32_t));
+            M.alloc(st, f->halfCount_, (size_t)maxTiles * 2 * sizeof(uint32_t));
+            // the workspace is zeroed here and never again (the scanless row sets: every sort leaves them zero)
+            if (st == GSM_OK && (hipMemset(f->hist_, 0, f->histBytes_) != hipSuccess ||
+                                 hipMemset(f->tileStart_, 0, ((size_t)maxTiles + 1) * sizeof(uint32_t)) != hipSuccess))
+                st = GSM_ERR_FAILED_TO_ALLOCATE_BUFFER;
+        }
+        if (st != GSM_OK) {
+            delete f;
+            return st;
+        }
+        *out = f;
+        return GSM_OK;
+    }
+
+    gsm_status run(hipStream_t s, const gsm_debug_frame_sort_desc* desc, const void* keys, const void* values,
+                   uint32_t n, gsm_debug_frame_sort_out* out) {
+        gsm_status st = frame_sort_run_check(capacity_, maxTiles_, desc, keys, values, n, out);
+        if (st != GSM_OK) return st;
+        if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
+        (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's)
+        const gsm_debug_frame_sort_desc d = *desc;
+        out->plan = 0u;
+        hostCount_ = n;
+        if (n > 0u) {
+            hipMemcpyAsync(keys_[0], keys, (size_t)n * 4, hipMemcpyDeviceToDevice, s);
+            hipMemcpyAsync(vals_[0], values, (size_t)n * 4, hipMemcpyDeviceToDevice, s);
+        }
+        hipMemcpyAsync(count_, &hostCount_, 4, hipMemcpyHostToDevice, s);
+        const SortSpace ws{hist_, histBytes_, binTotals_, kSortTotalsWords};
+        const bool ballot = tuning_.ballotRank;
+        // GlobalRenderer::runFrame (shift 16) and DepthFirstRenderer::sortTiles (shift 0)
+        const int res = d.all_tiles > kFrameSortMaxTiles16
+                            ? radix_sort_tiles_wide(keys_, vals_, count_, capacity_, ws, tileStart_, buckets_, d.all_tiles, s,
+                                                    ballot)
+                            : radix_sort_tiles(keys_, vals_, count_, capacity_, d.shift, ws, tileStart_, 0u, d.num_tiles,
+                                               d.all_tiles, s, ballot, tuning_.wideSort, tuning_.sortScanless);
+        if (res == kSortNoSpace) return GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;  // (nothing of the sort launched)
+        out->plan = frame_sort_plan(d.all_tiles, res);
+        int sorted = res;
+        if (d.depth_sort) {
+            // k_tile_sort indexes the runs by the starts: they are checked here first (a renderer does not look)
+            starts_.resize((size_t)d.num_tiles + 1);
+            if (hipMemcpyAsync(starts_.data(), tileStart_, starts_.size() * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                hipStreamSynchronize(s) != hipSuccess || !frame_sort_starts_in_range(starts_.data(), d.num_tiles, n)) {
+                st = GSM_ERR_RENDER_FAILED;
+            } else {
+                tile_depth_sort(keys_[res], vals_[res], keys_[res ^ 1], vals_[res ^ 1], tileStart_, 0u, d.num_tiles, s,
+                                ballot, half_[0], half_[1], halfCount_, d.all_tiles, d.full != 0u, dev_.numCUs);
+                sorted = res ^ 1;
+            }
+        }
+        auto copy_out = [&](uint32_t* dst, const uint32_t* src, size_t words) {
+            if (dst && words) hipMemcpyAsync(dst, src, words * 4, hipMemcpyDeviceToHost, s);
+        };
+        copy_out(out->sorted_keys, keys_[sorted], n);
+        copy_out(out->sorted_values, vals_[sorted], n);
+        copy_out(out->tile_start, tileStart_, (size_t)d.all_tiles + 1);
+        if (d.depth_sort && st == GSM_OK) {
+            copy_out(out->half0, half_[0], n);
+            copy_out(out->half1, half_[1], n);
+            copy_out(out->half_count, halfCount_, (size_t)d.all_tiles * 2);
+        }
+        if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;
+        return st;
+    }
+
+   private:
+    FrameSorter() = default;
+    Device dev_;
+    DeviceAllocations allocs_;
+    Tuning tuning_;
+    uint32_t capacity_ = 0, maxTiles_ = 0, hostCount_ = 0;
+    uint32_t *keys_[2] = {nullptr, nullptr}, *vals_[2] = {nullptr, nullptr}, *half_[2] = {nullptr, nullptr};
+    uint32_t *count_ = nullptr, *hist_ = nullptr, *binTotals_ = nullptr, *buckets_ = nullptr, *tileStart_ = nullptr,
+             *halfCount_ = nullptr;
+    size_t histBytes_ = 0;
+    std::vector<uint32_t> starts_;
+};
+
+}  // namespace gsm
+
+struct gsm_debug_frame_sort : gsm::Handle<gsm::FrameSorter> {};
 
 extern "C" {
 
@@ -397,6 +508,21 @@ gsm_status gsm_sort_pairs_u32(void* keys, void* values, uint32_t n, uint32_t key
     hipFree(bins);
     hipFree(np);
     return st;
+}
+
+gsm_status gsm_debug_frame_sort_create(uint32_t capacity, uint32_t max_tiles, int hip_device,
+                                       gsm_debug_frame_sort** out) {
+    const gsm_status st = gsm::frame_sort_create_check(capacity, max_tiles, out);
+    if (st != GSM_OK) return st;
+    return gsm_debug_frame_sort::create(out, capacity, max_tiles, hip_device);
+}
+
+void gsm_debug_frame_sort_destroy(gsm_debug_frame_sort* f) { gsm_debug_frame_sort::destroy(f); }
+
+gsm_status gsm_debug_frame_sort_run(gsm_debug_frame_sort* f, void* stream, const gsm_debug_frame_sort_desc* desc,
+                                    const void* keys, const void* values, uint32_t n, gsm_debug_frame_sort_out* out) {
+    if (!f || !f->impl) return GSM_ERR_INVALID_ARGUMENT;
+    return f->impl->run((hipStream_t)stream, desc, keys, values, n, out);
 }
 
 gsm_status gsm_debug_sort_rank_probe(int hip_device, int* lane_ordered) {

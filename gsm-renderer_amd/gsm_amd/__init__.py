@@ -272,6 +272,17 @@ EXTRACT_OUT_BYTES = 40  # include/gsm_renderer.h: sizeof(gsm_global_extract_out)
 assert C.sizeof(_ExtractOut) == EXTRACT_OUT_BYTES
 
 
+class _FrameSortDesc(C.Structure):  # gsm_debug_frame_sort_desc (include/gsm_debug.h)
+    _fields_ = [("shift", C.c_uint32), ("num_tiles", C.c_uint32), ("all_tiles", C.c_uint32),
+                ("depth_sort", C.c_uint32), ("full", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class _FrameSortOut(C.Structure):  # gsm_debug_frame_sort_out
+    _fields_ = [("sorted_keys", C.c_void_p), ("sorted_values", C.c_void_p), ("tile_start", C.c_void_p),
+                ("half0", C.c_void_p), ("half1", C.c_void_p), ("half_count", C.c_void_p),
+                ("plan", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class _Counters(C.Structure):
     _fields_ = [("total_assignments", C.c_uint32), ("max_capacity", C.c_uint32),
                 ("padded_count", C.c_uint32), ("overflow", C.c_uint32), ("tiles_x", C.c_uint32),
@@ -374,6 +385,10 @@ _SIGNATURES = {
     "gsm_global_stage_times": ([C.c_void_p, C.POINTER(C.c_float), C.c_int], C.c_int),
     "gsm_global_set_tile_rows": ([C.c_void_p, C.c_uint32, C.c_uint32], C.c_int),
     "gsm_sort_pairs_u32": ([C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p], C.c_int),
+    "gsm_debug_frame_sort_create": ([C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)], C.c_int),
+    "gsm_debug_frame_sort_destroy": ([C.c_void_p], None),
+    "gsm_debug_frame_sort_run": ([C.c_void_p, C.c_void_p, C.POINTER(_FrameSortDesc), C.c_void_p, C.c_void_p,
+                                  C.c_uint32, C.POINTER(_FrameSortOut)], C.c_int),
     # include/gsm_multigpu.h
     "gsm_global_project_partition": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera),
                                       C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -1218,6 +1233,76 @@ def sort_pairs_u32(keys, values, key_bits: int = 32, stream=None):
     n = int(keys.numel())
     _check(_lib().gsm_sort_pairs_u32(_ptr(keys), _ptr(values), n, int(key_bits), _stream_handle(stream)),
            "gsm_sort_pairs_u32")
+
+
+class FrameSortPlan(enum.IntEnum):  # include/gsm_debug.h gsm_frame_sort_plan
+    ONE_NARROW = 1
+    TWO_NARROW = 2
+    ONE_WIDE = 3
+    WIDE_THEN_NARROW = 4
+
+
+@dataclass
+class FrameSortResult:
+    """What one FrameSort.run copied out (numpy uint32).  half0 / half1 / half_count: None without a depth sort;
+    sorted_keys / sorted_values after a depth sort with full = False hold nothing specified."""
+    plan: FrameSortPlan
+    sorted_keys: np.ndarray
+    sorted_values: np.ndarray
+    tile_start: np.ndarray
+    half0: Optional[np.ndarray] = None
+    half1: Optional[np.ndarray] = None
+    half_count: Optional[np.ndarray] = None
+
+
+class FrameSort:
+    """gsm_debug_frame_sort (include/gsm_debug.h; debug only): the production frame sort -- the tile passes that
+    write the tile starts, then the per-tile depth sort with its half-tile lists -- on caller keys.  One handle
+    keeps its workspace between runs, as a renderer does; GSM_SORT_RANK / GSM_SORT_WIDE / GSM_SORT_SCAN are read
+    when it is created.  A context manager; close() frees the device buffers."""
+
+    def __init__(self, capacity: int, max_tiles: int, device: Optional[int] = None):
+        h = C.c_void_p()
+        self.capacity, self.max_tiles = int(capacity), int(max_tiles)
+        _check(_lib().gsm_debug_frame_sort_create(self.capacity, self.max_tiles, -1 if device is None else int(device),
+                                                  C.byref(h)), "gsm_debug_frame_sort_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            _lib().gsm_debug_frame_sort_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    def run(self, keys, values, n: Optional[int] = None, *, shift: int, num_tiles: int,
+            all_tiles: Optional[int] = None, depth_sort: bool = False, full: bool = False,
+            stream=None) -> FrameSortResult:
+        """Sort the first n (default: all) pairs of the device tensors keys / values (torch int32, the words read
+        as uint32); shift 16: keys tile << 16 | depth16, shift 0: the tile alone.  Every key's tile is below
+        num_tiles <= all_tiles (default num_tiles); bits 30 and 31 of a value are the half-tile skip flags."""
+        n = int(keys.numel()) if n is None else int(n)
+        all_tiles = int(num_tiles) if all_tiles is None else int(all_tiles)
+        desc = _FrameSortDesc(int(shift), int(num_tiles), all_tiles, int(bool(depth_sort)), int(bool(full)), 0)
+        sk, sv = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        ts = np.zeros(max(all_tiles, 0) + 1, np.uint32)
+        h0 = h1 = hc = None
+        if depth_sort:
+            h0, h1 = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+            hc = np.zeros(2 * max(all_tiles, 0), np.uint32)
+        host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        out = _FrameSortOut(host(sk), host(sv), host(ts), host(h0), host(h1), host(hc), 0, 0)
+        _check(_lib().gsm_debug_frame_sort_run(self._h, _stream_handle(stream), C.byref(desc),
+                                               _ptr(keys) if n else None, _ptr(values) if n else None, n,
+                                               C.byref(out)), "gsm_debug_frame_sort_run")
+        return FrameSortResult(FrameSortPlan(out.plan), sk, sv, ts, h0, h1, hc)
 
 
 class _MgOptions(C.Structure):

@@ -110,6 +110,62 @@ gsm_status gsm_debug_sort_rank_probe(int hip_device, int *lane_ordered);
 size_t gsm_debug_sort_workspace_bytes(uint32_t capacity);
 gsm_status gsm_debug_sort_plan_fits(uint32_t capacity, uint32_t key_bits, int wide, size_t hist_bytes);
 
+/* The production frame sort on caller keys (debug only): the tile passes whose last pass writes
+ * the tile starts -- what a Global or DepthFirst frame runs after its scatter -- and, when asked, the per-tile
+ * depth sort with its half-tile lists.  A handle owns what a renderer owns for the sort: two key and two value
+ * buffers of `capacity` words, the device count word, the digit-count workspace (zeroed once, at create; it
+ * persists between runs like a renderer's), the digit totals, the low-digit buckets, tileStart[max_tiles + 1],
+ * the two half lists and halfCount[2 * max_tiles].  GSM_SORT_RANK, GSM_SORT_WIDE and GSM_SORT_SCAN are read
+ * from the environment at create, as by a renderer.  hip_device < 0: the current device.
+ * create: GSM_ERR_INVALID_ASSIGNMENT_CAPACITY for capacity 0, GSM_ERR_INVALID_TILE_COUNT for max_tiles 0 or above
+ * 524,288 (19 bits: one wide pass + one 8-bit pass). */
+typedef struct gsm_debug_frame_sort gsm_debug_frame_sort;
+
+typedef struct {
+    uint32_t shift;      /* the tile field's first bit: 16 (Global keys, tile << 16 | depth16) or 0 (DepthFirst
+                            instance keys: the tile alone) */
+    uint32_t num_tiles;  /* the frame's tiles: every key's tile field is below it (1 .. all_tiles) */
+    uint32_t all_tiles;  /* the configuration's tiles (<= max_tiles; <= 65,536 with shift 16) */
+    uint32_t depth_sort; /* 1: the depth sort of tiles [0, num_tiles) after the tile passes (shift 16 only) */
+    uint32_t full;       /* 1: the depth sort also writes the sorted keys and values (captured frames) */
+    uint32_t reserved;   /* 0 */
+} gsm_debug_frame_sort_desc;
+
+/* The passes a run took (chosen by all_tiles, num_tiles and GSM_SORT_WIDE). */
+typedef enum {
+    GSM_FRAME_SORT_ONE_NARROW = 1,      /* <= 256 tiles: one pass of 4..8 bits */
+    GSM_FRAME_SORT_TWO_NARROW = 2,      /* <= 65,536 tiles: two passes of 4..8 bits each */
+    GSM_FRAME_SORT_ONE_WIDE = 3,        /* > 256 tiles, num_tiles <= 2048: one pass of 9..11 bits */
+    GSM_FRAME_SORT_WIDE_THEN_NARROW = 4 /* > 65,536 tiles: 9..11 bits, then 8 bits over up to 2048 buckets */
+} gsm_frame_sort_plan;
+
+/* Host destinations, each optional (NULL: not copied). */
+typedef struct {
+    uint32_t *sorted_keys;   /* [n]; after a depth sort with full = 0 their content is not specified */
+    uint32_t *sorted_values; /* [n]; as sorted_keys */
+    uint32_t *tile_start;    /* [all_tiles + 1] */
+    uint32_t *half0, *half1; /* [n]: tile t's kept ids from tile_start[t]; written by a depth sort only */
+    uint32_t *half_count;    /* [2 * all_tiles]: half h of tile t at h * all_tiles + t, for t < num_tiles;
+                                written by a depth sort only */
+    uint32_t plan;           /* out: gsm_frame_sort_plan */
+    uint32_t reserved;       /* 0 */
+} gsm_debug_frame_sort_out;
+
+gsm_status gsm_debug_frame_sort_create(uint32_t capacity, uint32_t max_tiles, int hip_device,
+                                       gsm_debug_frame_sort **out);
+void gsm_debug_frame_sort_destroy(gsm_debug_frame_sort *sorter);
+/* Copies the n <= capacity device pairs (keys, values: device memory, read only) into the handle, writes n to
+ * the device count word, runs the tile passes (and the depth sort), copies the results out and synchronises
+ * `stream`.  The value word's bits 30 and 31 are the half-tile skip flags, the bits below the id the half lists
+ * hold.  Before the depth sort the tile starts are read back and checked (non-decreasing, at most n): starts that
+ * are not end the run with GSM_ERR_RENDER_FAILED, the depth sort not launched -- its workgroups index the runs by
+ * them.  GSM_ERR_INVALID_ARGUMENT: n > capacity, a shift other than 0 or 16, depth_sort without shift 16,
+ * num_tiles = 0 or > all_tiles, all_tiles > max_tiles (> 65,536 with shift 16);
+ * GSM_ERR_INVALID_ASSIGNMENT_CAPACITY: the plan does not fit the workspace (nothing launched). */
+gsm_status gsm_debug_frame_sort_run(gsm_debug_frame_sort *sorter, void *stream,
+                                    const gsm_debug_frame_sort_desc *desc, const void *keys, const void *values,
+                                    uint32_t n, gsm_debug_frame_sort_out *out);
+
 /* The device steps of gsm_multigpu_render (gsm_multigpu.h) without RCCL, so W virtual ranks can run
  * the native exchange in one process on one GPU (tests): the caller plays the collectives --
  * gathers every rank's per-slab counts into the W x W matrix (row r = rank r) on the device and
