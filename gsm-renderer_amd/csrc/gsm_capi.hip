@@ -374,6 +374,23 @@ gsm_status gsm_global_state_histogram(gsm_renderer* r, void* stream, const uint8
     return r->impl->stateHistogram((hipStream_t)stream, state, gaussian_count, histogram);
 }
 
+void gsm_global_select_query_default(gsm_global_select_query* q) { gsm::select_query_default(q); }
+
+gsm_status gsm_global_select_where(gsm_renderer* r, void* stream, const gsm_gaussian_input* input,
+                                   const gsm_global_select_query* query, uint8_t* state,
+                                   const gsm_global_style* styles, uint32_t style_count, uint32_t and_mask,
+                                   uint32_t xor_mask, uint32_t* matched) {
+    if (!r || !r->impl) return GSM_ERR_INVALID_ARGUMENT;
+    return r->impl->selectWhere((hipStream_t)stream, input, query, state, styles, style_count, and_mask, xor_mask,
+                                matched);
+}
+
+gsm_status gsm_global_state_bounds(gsm_renderer* r, void* stream, const gsm_gaussian_input* input,
+                                   const gsm_global_state* state, const uint32_t keep[8], gsm_global_bounds* bounds) {
+    if (!r || !r->impl) return GSM_ERR_INVALID_ARGUMENT;
+    return r->impl->stateBounds((hipStream_t)stream, input, state, keep, bounds);
+}
+
 gsm_status gsm_global_pick_owner(gsm_renderer* r, const uint32_t* items, uint32_t n, uint32_t* object,
                                  uint32_t* gaussian) {
     if (!r || !r->impl || (n > 0 && (!items || !object || !gaussian))) return GSM_ERR_INVALID_ARGUMENT;

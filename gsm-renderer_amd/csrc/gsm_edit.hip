@@ -1,6 +1,8 @@
-// gsm_edit.hip -- gfx950 kernels of the Global renderer's scene-editing entries (DESIGN.md 28):
-// gsm_global_extract, a stable compaction of a scene's rows by its state bytes, and gsm_global_state_histogram.
-// No reference analogue.  Nothing here computes: rows are copied byte for byte.
+// gsm_edit.hip -- gfx950 kernels of the Global renderer's scene-editing entries (DESIGN.md 28, 30):
+// gsm_global_extract, a stable compaction of a scene's rows by its state bytes, gsm_global_state_histogram,
+// gsm_global_select_where, a select by a world-space and attribute predicate, and gsm_global_state_bounds, the box
+// of a keep set.  No reference analogue.  The extract copies rows byte for byte; the select's only arithmetic is
+// the nine products and nine sums of its shape test, unfused (-ffp-contract=off), and the bounds only compare.
 //
 // The extract is three launches in stream order and the launch boundary is the only barrier between workgroups:
 // no kernel here waits for another workgroup (no look-back, no flag, no ticket).
@@ -189,6 +191,193 @@ __global__ __launch_bounds__(kEditBlock) void k_state_histogram(const uint8_t* _
     if (v) atomicAdd(&histogram[threadIdx.x], v);
 }
 
+// gsm_global_select_where: *matched starts from 0 (a kernel, not a memset node, as k_state_histogram_clear)
+__global__ __launch_bounds__(64) void k_select_where_clear(uint32_t* __restrict__ matched) {
+    if (threadIdx.x == 0) *matched = 0u;
+}
+
+// gsm_global_select_where: one thread per gaussian.  The record's first 32 bytes (fp32: two 16-byte
+// loads; the quaternion is not read) or first 20 (fp16: one 16-byte and one 4-byte load) give the position, the
+// opacity and the scales; the state byte is loaded and stored by its own thread alone.  The query is a kernel
+// argument, so the shape and the two range switches are scalar branches.  One ballot count per wave, one integer
+// add per workgroup with a match.
+template <bool HALF>
+__global__ __launch_bounds__(kEditBlock) void k_select_where(const void* __restrict__ world, SelectWhereArgs q,
+                                                             uint8_t* __restrict__ state,
+                                                             const uint2* __restrict__ styleTable,
+                                                             uint32_t* __restrict__ matched) {
+    __shared__ uint32_t waveCount[kEditBlock / 64];
+    const uint32_t g = blockIdx.x * kEditBlock + threadIdx.x;
+    bool match = false;
+    if (g < q.count) {
+        float px, py, pz, o, sx, sy, sz;
+        if constexpr (HALF) {
+            const uint8_t* rec = (const uint8_t*)world + (size_t)g * sizeof(PackedWorldGaussianHalf);
+            const uint4 w0 = *(const uint4*)rec;
+            const uint32_t w1 = *(const uint32_t*)(rec + 16);
+            px = __builtin_bit_cast(float, w0.x);
+            py = __builtin_bit_cast(float, w0.y);
+            pz = __builtin_bit_cast(float, w0.z);
+            o = hbits_to_f((uint16_t)(w0.w & 0xFFFFu));
+            sx = hbits_to_f((uint16_t)(w0.w >> 16));
+            sy = hbits_to_f((uint16_t)(w1 & 0xFFFFu));
+            sz = hbits_to_f((uint16_t)(w1 >> 16));
+        } else {
+            const float4* wp = (const float4*)((const PackedWorldGaussian*)world + g);
+            const float4 w0 = wp[0], w1 = wp[1];
+            px = w0.x; py = w0.y; pz = w0.z; o = w0.w;
+            sx = w1.x; sy = w1.y; sz = w1.z;
+        }
+        const uint32_t old = state[g];
+        match = (old & q.testMask) == q.testValue;
+        if (styleTable && ((styleTable[old].y >> 8) & 0xFFu)) match = false;  // hidden: not selectable
+        if (q.shape != GSM_SELECT_ALL) {  // (uniform)
+            float v[3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) v[r] = ((q.A[4 * r] * px + q.A[4 * r + 1] * py) + q.A[4 * r + 2] * pz) + q.A[4 * r + 3];
+            bool inside;
+            if (q.shape == GSM_SELECT_BOX)  // (uniform)
+                inside = __builtin_fabsf(v[0]) <= 1.0f && __builtin_fabsf(v[1]) <= 1.0f && __builtin_fabsf(v[2]) <= 1.0f;
+            else
+                inside = ((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) <= 1.0f;
+            const bool nan = v[0] != v[0] || v[1] != v[1] || v[2] != v[2];
+            if (nan || inside == (q.outside != 0)) match = false;
+        }
+        if (q.opacityOn && !(q.opacityMin <= o && o <= q.opacityMax)) match = false;  // (uniform switch)
+        if (q.scaleOn) {                                                               // (uniform)
+            const float m = __builtin_fmaxf(__builtin_fmaxf(sx, sy), sz);  // maxNum: NaN only when all three are
+            if (!(q.scaleMin <= m && m <= q.scaleMax)) match = false;
+        }
+        if (match) state[g] = (uint8_t)(((old & q.andMask) ^ q.xorMask) & 0xFFu);
+    }
+    if (matched) {  // (uniform)
+        const unsigned long long b = __ballot(match);
+        if ((threadIdx.x & 63u) == 0) waveCount[threadIdx.x >> 6] = (uint32_t)__popcll(b);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const uint32_t n = waveCount[0] + waveCount[1] + waveCount[2] + waveCount[3];
+            if (n) atomicAdd(matched, n);
+        }
+    }
+}
+
+// gsm_global_state_bounds: the extrema and counts a thread, a wave, a block or the grid has seen.  min / max of
+// finite values with -0 stored as +0: exact and the same bits in any order.
+struct BoundsAcc {
+    float mn[3], mx[3];
+    uint32_t n, skipped;
+};
+
+__device__ __forceinline__ void bounds_empty(BoundsAcc& a) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        a.mn[k] = __builtin_inff();
+        a.mx[k] = -__builtin_inff();
+    }
+    a.n = a.skipped = 0u;
+}
+
+__device__ __forceinline__ void bounds_merge(BoundsAcc& a, const BoundsAcc& b) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        a.mn[k] = __builtin_fminf(a.mn[k], b.mn[k]);
+        a.mx[k] = __builtin_fmaxf(a.mx[k], b.mx[k]);
+    }
+    a.n += b.n;
+    a.skipped += b.skipped;
+}
+
+// the block's accumulators into one, valid in thread 0: a butterfly inside each wave, then the four waves through LDS
+__device__ __forceinline__ void bounds_block_reduce(BoundsAcc& a, BoundsAcc* lds) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        BoundsAcc b;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            b.mn[k] = __shfl_xor(a.mn[k], off);
+            b.mx[k] = __shfl_xor(a.mx[k], off);
+        }
+        b.n = __shfl_xor(a.n, off);
+        b.skipped = __shfl_xor(a.skipped, off);
+        bounds_merge(a, b);
+    }
+    if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (uint32_t w = 1; w < kEditBlock / 64; ++w) bounds_merge(a, lds[w]);
+}
+
+// launch 1: per block of 256 gaussians.  A gaussian in the keep set loads its record's first 16 bytes (the position
+// is three fp32 values in both formats); one with a NaN or infinite coordinate is counted apart and not in the box.
+template <bool HALF>
+__global__ __launch_bounds__(kEditBlock) void k_bounds_partial(const void* __restrict__ world,
+                                                               const uint8_t* __restrict__ state,
+                                                               uint32_t defaultState, uint32_t count, KeepSet keep,
+                                                               uint4* __restrict__ partials) {
+    __shared__ BoundsAcc lds[kEditBlock / 64];
+    uint32_t s;
+    BoundsAcc a;
+    bounds_empty(a);
+    if (thread_kept(state, defaultState, count, keep, &s)) {
+        const size_t g = (size_t)blockIdx.x * kEditBlock + threadIdx.x;
+        const uint4 w = *(const uint4*)((const uint8_t*)world + g * (HALF ? sizeof(PackedWorldGaussianHalf)
+                                                                          : sizeof(PackedWorldGaussian)));
+        uint32_t bits[3] = {w.x, w.y, w.z};
+        bool finite = true;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if ((bits[k] & 0x7F800000u) == 0x7F800000u) finite = false;
+            if (bits[k] == 0x80000000u) bits[k] = 0u;  // -0 counts as +0
+        }
+        if (finite) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) a.mn[k] = a.mx[k] = __builtin_bit_cast(float, bits[k]);
+            a.n = 1u;
+        } else {
+            a.skipped = 1u;
+        }
+    }
+    bounds_block_reduce(a, lds);
+    if (threadIdx.x == 0) {
+        partials[2 * (size_t)blockIdx.x] = make_uint4(__builtin_bit_cast(uint32_t, a.mn[0]), __builtin_bit_cast(uint32_t, a.mn[1]),
+                                                      __builtin_bit_cast(uint32_t, a.mn[2]), __builtin_bit_cast(uint32_t, a.mx[0]));
+        partials[2 * (size_t)blockIdx.x + 1] = make_uint4(__builtin_bit_cast(uint32_t, a.mx[1]), __builtin_bit_cast(uint32_t, a.mx[2]),
+                                                          a.n, a.skipped);
+    }
+}
+
+// launch 2: one workgroup walks the partials 256 a round and writes the eight words of *bounds (blocks == 0: the
+// empty result)
+__global__ __launch_bounds__(kEditBlock) void k_bounds_final(const uint4* __restrict__ partials, uint32_t blocks,
+                                                             uint32_t* __restrict__ bounds) {
+    __shared__ BoundsAcc lds[kEditBlock / 64];
+    BoundsAcc a;
+    bounds_empty(a);
+    for (uint32_t i = threadIdx.x; i < blocks; i += kEditBlock) {
+        const uint4 lo = partials[2 * (size_t)i], hi = partials[2 * (size_t)i + 1];
+        BoundsAcc b;
+        b.mn[0] = __builtin_bit_cast(float, lo.x);
+        b.mn[1] = __builtin_bit_cast(float, lo.y);
+        b.mn[2] = __builtin_bit_cast(float, lo.z);
+        b.mx[0] = __builtin_bit_cast(float, lo.w);
+        b.mx[1] = __builtin_bit_cast(float, hi.x);
+        b.mx[2] = __builtin_bit_cast(float, hi.y);
+        b.n = hi.z;
+        b.skipped = hi.w;
+        bounds_merge(a, b);
+    }
+    bounds_block_reduce(a, lds);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            bounds[k] = __builtin_bit_cast(uint32_t, a.mn[k]);
+            bounds[3 + k] = __builtin_bit_cast(uint32_t, a.mx[k]);
+        }
+        bounds[6] = a.n;
+        bounds[7] = a.skipped;
+    }
+}
+
 // the widest chunk (a power of two, at most 16 bytes) that both addresses and the row width are multiples of
 static uint32_t chunk_width(const void* src, const void* dst, uint64_t rowBytes) {
     const uint64_t x = (uint64_t)(uintptr_t)src | (uint64_t)(uintptr_t)dst | rowBytes | 16u;
@@ -213,6 +402,26 @@ void launch_state_histogram(const uint8_t* state, uint32_t count, uint32_t* hist
     if (count == 0) return;
     const uint32_t grid = std::min(std::max((count / 4u + 2047u) / 2048u, 1u), 1024u);
     hipLaunchKernelGGL(k_state_histogram, dim3(grid), dim3(kEditBlock), 0, s, state, count, histogram);
+}
+
+void launch_select_where(bool halfInput, const void* world, const SelectWhereArgs& a, uint8_t* state,
+                         const uint2* styleTable, uint32_t* matched, hipStream_t s) {
+    // overwritten, not added to (a kernel, not a memset node: launch_state_histogram's note)
+    if (matched) hipLaunchKernelGGL(k_select_where_clear, dim3(1), dim3(64), 0, s, matched);
+    const uint32_t blocks = (a.count + kEditBlock - 1u) / kEditBlock;
+    if (blocks == 0) return;
+    const auto k = halfInput ? k_select_where<true> : k_select_where<false>;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(kEditBlock), 0, s, world, a, state, styleTable, matched);
+}
+
+void launch_state_bounds(bool halfInput, const void* world, const uint8_t* state, uint32_t defaultState,
+                         uint32_t count, const KeepSet& keep, uint4* partials, uint32_t* bounds, hipStream_t s) {
+    const uint32_t blocks = (count + kEditBlock - 1u) / kEditBlock;
+    if (blocks) {
+        const auto k = halfInput ? k_bounds_partial<true> : k_bounds_partial<false>;
+        hipLaunchKernelGGL(k, dim3(blocks), dim3(kEditBlock), 0, s, world, state, defaultState, count, keep, partials);
+    }
+    hipLaunchKernelGGL(k_bounds_final, dim3(1), dim3(kEditBlock), 0, s, (const uint4*)partials, blocks, bounds);
 }
 
 }  // namespace gsm

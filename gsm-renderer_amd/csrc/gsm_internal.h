@@ -377,6 +377,7 @@ struct DeviceArena {
     uint2* styleTable = nullptr;               // [kStyleEntries] packed styles (styled frames, select_mask; lazily)
     uint32_t* selectBitmap = nullptr;          // [ceil(maxG / 32)] one bit per gaussian id (select_pick; lazily)
     uint32_t* extractBlocks = nullptr;         // [ceil(maxG / 256)] kept gaussians per block, then their scan (extract; lazily)
+    uint4* boundsPartials = nullptr;           // [2 * ceil(maxG / 256)] 32 B per block: extrema and counts (state_bounds; lazily)
     uint16_t* expTable = nullptr;              // [65536]
     float2* sincosTable = nullptr;             // [kSincosEntries + 256]: sin/cos, then the byte table (det_byte_lut_entry)
 };
@@ -508,6 +509,27 @@ void launch_extract(const ExtractArgs& args, uint32_t* kept, hipStream_t stream)
 // gsm_global_state_histogram (k_state_histogram): histogram[s] = the number of g < count with state[g] == s; the 256
 // words are cleared here on the stream.
 void launch_state_histogram(const uint8_t* state, uint32_t count, uint32_t* histogram, hipStream_t stream);
+// gsm_global_select_where (gsm_edit.hip: k_select_where): one thread per gaussian tests its record
+// against the query and a matching gaussian's state byte becomes (old & andMask) ^ xorMask.  The query travels as a
+// kernel argument; opacityOn / scaleOn say that the range is not (-inf, +inf).  *matched (nullable) is zeroed by a
+// kernel here on the stream; a count of 0 launches that alone.
+struct SelectWhereArgs {
+    float A[12];  // row-major 3x4 (not read when shape is 0)
+    float opacityMin, opacityMax, scaleMin, scaleMax;
+    uint32_t shape, outside, opacityOn, scaleOn;
+    uint32_t testMask, testValue;  // (both already & 0xFF)
+    uint32_t andMask, xorMask;
+    uint32_t count;
+};
+void launch_select_where(bool halfInput, const void* world, const SelectWhereArgs& args, uint8_t* state,
+                         const uint2* styleTable, uint32_t* matched, hipStream_t stream);
+// gsm_global_state_bounds (k_bounds_partial, k_bounds_final): per block of 256 gaussians the six extrema and the two
+// counts of the gaussians in the keep set into partials[block] (kBoundsPartialBytes each), then one workgroup
+// reduces the partials into *bounds (8 words: min[3], max[3], count, skipped); with no block it writes the empty
+// result.
+constexpr size_t kBoundsPartialBytes = 32;
+void launch_state_bounds(bool halfInput, const void* world, const uint8_t* state, uint32_t defaultState,
+                         uint32_t count, const KeepSet& keep, uint4* partials, uint32_t* bounds, hipStream_t stream);
 // exclusive scan of the per-block sums, total + clamp into the header (GlobalShaders.metal:685-712)
 // project gaussians [0, a.count) of world/harm (already offset to the rank's range) and pack
 // the records of each slab's gaussians into `send` (slab-major, ascending id), counts to sendCounts

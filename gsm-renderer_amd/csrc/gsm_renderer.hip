@@ -338,6 +338,59 @@ gsm_status GlobalRenderer::stateHistogram(hipStream_t s, const uint8_t* state, u
     return GSM_OK;
 }
 
+gsm_status GlobalRenderer::selectWhere(hipStream_t s, const gsm_gaussian_input* in, const gsm_global_select_query* q,
+                                       uint8_t* state, const gsm_global_style* styles, uint32_t styleCount,
+                                       uint32_t andMask, uint32_t xorMask, uint32_t* matched) {
+    const gsm_status st = select_where_check(maxGaussians_, in, q, state, styles, styleCount, matched);
+    if (st != GSM_OK) return st;
+    if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
+    (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's)
+    if (styles && in->gaussian_count > 0) {
+        const gsm_status fs = fillStyleTable(s, styles, styleCount);
+        if (fs != GSM_OK) return fs;
+    }
+    SelectWhereArgs a{};
+    a.shape = q->shape;
+    if (q->shape != GSM_SELECT_ALL)  // (GSM_SELECT_ALL never reads to_shape)
+        for (int i = 0; i < 12; ++i) a.A[i] = q->to_shape[i];
+    a.outside = q->flags & GSM_SELECT_OUTSIDE;
+    a.opacityMin = q->opacity_min;
+    a.opacityMax = q->opacity_max;
+    a.scaleMin = q->scale_min;
+    a.scaleMax = q->scale_max;
+    a.opacityOn = select_range_applied(q->opacity_min, q->opacity_max) ? 1u : 0u;
+    a.scaleOn = select_range_applied(q->scale_min, q->scale_max) ? 1u : 0u;
+    a.testMask = q->test_mask & 0xFFu;
+    a.testValue = q->test_value & 0xFFu;
+    a.andMask = andMask;
+    a.xorMask = xorMask;
+    a.count = in->gaussian_count;
+    launch_select_where(config_.precision == GSM_PRECISION_FLOAT16, in->gaussians, a, state,
+                        styles ? arena_.styleTable : nullptr, matched, s);
+    if (hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;
+    return GSM_OK;
+}
+
+gsm_status GlobalRenderer::stateBounds(hipStream_t s, const gsm_gaussian_input* in, const gsm_global_state* state,
+                                       const uint32_t* keep, gsm_global_bounds* bounds) {
+    gsm_status st = state_bounds_check(maxGaussians_, in, state, keep, bounds);
+    if (st != GSM_OK) return st;
+    if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
+    if (!arena_.boundsPartials) {  // (the handle's first state_bounds: 32 bytes per block of 256 gaussians it can hold)
+        st = allocs_.alloc((void**)&arena_.boundsPartials,
+                           std::max<size_t>(((size_t)maxGaussians_ + kProjectBlock - 1) / kProjectBlock, 1) *
+                               kBoundsPartialBytes);
+        if (st != GSM_OK) return st;
+    }
+    KeepSet k;
+    for (int i = 0; i < 8; ++i) k.w[i] = keep[i];
+    (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's)
+    launch_state_bounds(config_.precision == GSM_PRECISION_FLOAT16, in->gaussians, state->state, state->default_state,
+                        in->gaussian_count, k, arena_.boundsPartials, (uint32_t*)bounds, s);
+    if (hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;
+    return GSM_OK;
+}
+
 GlobalRenderer::FrameRequest GlobalRenderer::request(FrameKind kind, const ProjectArgs& args, uint32_t width,
                                                      uint32_t height, const FrameTargets& targets) const {
     FrameRequest rq;

@@ -11,6 +11,7 @@
 #include "gsm_host.h"
 #include "gsm_internal.h"
 #include "gsm_schedule_key.h"
+#include "gsm_select_check.h"
 
 namespace gsm {
 
@@ -82,6 +83,14 @@ class GlobalRenderer {
                        const uint32_t* keep, const gsm_global_extract_out* out, uint32_t* kept);
     // the number of gaussians of every state value (gsm_global_state_histogram)
     gsm_status stateHistogram(hipStream_t stream, const uint8_t* state, uint32_t gaussianCount, uint32_t* histogram);
+    // the state bytes of the gaussians whose records match the query become (old & andMask) ^ xorMask
+    // (gsm_global_select_where): no camera, no frame state
+    gsm_status selectWhere(hipStream_t stream, const gsm_gaussian_input* input, const gsm_global_select_query* query,
+                           uint8_t* state, const gsm_global_style* styles, uint32_t styleCount, uint32_t andMask,
+                           uint32_t xorMask, uint32_t* matched);
+    // the axis-aligned box and the count of the gaussians whose state byte is in the keep set (gsm_global_state_bounds)
+    gsm_status stateBounds(hipStream_t stream, const gsm_gaussian_input* input, const gsm_global_state* state,
+                           const uint32_t* keep, gsm_global_bounds* bounds);
     // items of the last enqueued pick frame -> (object of the call, gaussian id within it); host only, no sync
     gsm_status pickOwner(const uint32_t* items, uint32_t n, uint32_t* object, uint32_t* gaussian) const;
 

@@ -210,6 +210,27 @@ class Style:
     hidden: bool = False
 
 
+SELECT_ALL, SELECT_BOX, SELECT_ELLIPSOID = 0, 1, 2  # include/gsm_renderer.h GSM_SELECT_*
+SELECT_OUTSIDE = 1
+
+
+@dataclass
+class SelectQuery:
+    """gsm_global_select_query: the predicate of GlobalRenderer.select_where.  The defaults are
+    gsm_global_select_query_default's: no shape, identity rows, both ranges (-inf, +inf), every state.  to_shape:
+    twelve floats, a row-major 3x4 from scene space to the shape's unit space (scenes.box_to_shape,
+    scenes.sphere_to_shape)."""
+    shape: int = SELECT_ALL
+    flags: int = 0
+    to_shape: tuple = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+    opacity_min: float = float("-inf")
+    opacity_max: float = float("inf")
+    scale_min: float = float("-inf")
+    scale_max: float = float("inf")
+    test_mask: int = 0
+    test_value: int = 0
+
+
 # ---------------------------------------------------------------------------
 # ctypes layer
 # ---------------------------------------------------------------------------
@@ -270,6 +291,20 @@ class _ExtractOut(C.Structure):  # gsm_global_extract_out
 
 EXTRACT_OUT_BYTES = 40  # include/gsm_renderer.h: sizeof(gsm_global_extract_out), asserted there
 assert C.sizeof(_ExtractOut) == EXTRACT_OUT_BYTES
+
+
+class _SelectQuery(C.Structure):  # gsm_global_select_query
+    _fields_ = [("shape", C.c_uint32), ("flags", C.c_uint32), ("to_shape", C.c_float * 12),
+                ("opacity_min", C.c_float), ("opacity_max", C.c_float), ("scale_min", C.c_float),
+                ("scale_max", C.c_float), ("test_mask", C.c_uint32), ("test_value", C.c_uint32)]
+
+
+class _Bounds(C.Structure):  # gsm_global_bounds
+    _fields_ = [("min", C.c_float * 3), ("max", C.c_float * 3), ("count", C.c_uint32), ("skipped", C.c_uint32)]
+
+
+SELECT_QUERY_BYTES, BOUNDS_BYTES = 80, 32  # include/gsm_renderer.h: asserted there
+assert C.sizeof(_SelectQuery) == SELECT_QUERY_BYTES and C.sizeof(_Bounds) == BOUNDS_BYTES
 
 
 class _FrameSortDesc(C.Structure):  # gsm_debug_frame_sort_desc (include/gsm_debug.h)
@@ -367,6 +402,11 @@ _SIGNATURES = {
     "gsm_global_extract": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_State), C.POINTER(C.c_uint32),
                             C.POINTER(_ExtractOut), C.c_void_p], C.c_int),
     "gsm_global_state_histogram": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p], C.c_int),
+    "gsm_global_select_query_default": ([C.POINTER(_SelectQuery)], None),
+    "gsm_global_select_where": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_SelectQuery), C.c_void_p,
+                                 C.POINTER(_Style), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p], C.c_int),
+    "gsm_global_state_bounds": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_State),
+                                 C.POINTER(C.c_uint32), C.c_void_p], C.c_int),
     "gsm_global_render_stereo": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera),
                                   C.POINTER(_Camera), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                   C.c_void_p, C.c_size_t], C.c_int),
@@ -618,6 +658,16 @@ def _state_struct(state) -> _State:
     if isinstance(state, int):
         return _State(None, int(state), 0)
     return _State(_ptr(state), 0, 0)
+
+
+def _select_query_struct(q: SelectQuery) -> _SelectQuery:
+    s = _SelectQuery()
+    s.shape, s.flags = int(q.shape) & 0xFFFFFFFF, int(q.flags) & 0xFFFFFFFF
+    s.to_shape[:] = [float(v) for v in np.asarray(q.to_shape, np.float32).reshape(12)]
+    s.opacity_min, s.opacity_max = float(q.opacity_min), float(q.opacity_max)
+    s.scale_min, s.scale_max = float(q.scale_min), float(q.scale_max)
+    s.test_mask, s.test_value = int(q.test_mask) & 0xFFFFFFFF, int(q.test_value) & 0xFFFFFFFF
+    return s
 
 
 class GlobalRenderer(_Renderer):
@@ -922,6 +972,32 @@ class GlobalRenderer(_Renderer):
         st = _lib().gsm_global_state_histogram(self._h, _stream_handle(stream), _ptr(state), int(count),
                                                _ptr(histogram))
         _check(st, "gsm_global_state_histogram")
+
+    def select_where(self, input: GaussianInput, query, state, and_mask: int, xor_mask: int, styles=None,
+                     matched=None, stream=None, style_count: Optional[int] = None):
+        """gsm_global_select_where: the state byte of every gaussian whose record matches `query` (a SelectQuery;
+        None: NULL) becomes (old & and_mask) ^ xor_mask -- inside or outside a box or an ellipsoid in scene space,
+        opacity and largest scale in a range, a test on the current state; with `styles`, gaussians whose current
+        state is hidden are skipped.  No camera.  matched: an int32 / uint32 CUDA tensor of one element that
+        receives the count.  input.harmonics may be None."""
+        inp = _Input(_ptr(input.gaussians), _ptr(input.harmonics), int(input.gaussian_count), 0)
+        sarr, sn = _style_array(styles)
+        st = _lib().gsm_global_select_where(self._h, _stream_handle(stream), C.byref(inp),
+                                            None if query is None else C.byref(_select_query_struct(query)),
+                                            _ptr(state), sarr, sn if style_count is None else int(style_count),
+                                            int(and_mask) & 0xFFFFFFFF, int(xor_mask) & 0xFFFFFFFF, _ptr(matched))
+        _check(st, "gsm_global_select_where")
+
+    def state_bounds(self, input: GaussianInput, state, keep, bounds, stream=None):
+        """gsm_global_state_bounds: `bounds` (a CUDA tensor of 32 bytes: min[3] and max[3] as float32, then count
+        and skipped as uint32) receives the axis-aligned box and the count of the gaussians whose state byte has
+        its bit in `keep`.  state and keep: as GlobalRenderer.extract takes them."""
+        inp = _Input(_ptr(input.gaussians), _ptr(input.harmonics), int(input.gaussian_count), 0)
+        words = None if keep is None else (C.c_uint32 * 8)(*[int(w) & 0xFFFFFFFF for w in keep])
+        st = _lib().gsm_global_state_bounds(self._h, _stream_handle(stream), C.byref(inp),
+                                            None if state is None else C.byref(_state_struct(state)), words,
+                                            _ptr(bounds))
+        _check(st, "gsm_global_state_bounds")
 
     def pick_owner(self, items):
         """gsm_global_pick_owner: items of the last enqueued pick frame (any integer array, host) ->
@@ -1582,6 +1658,16 @@ def keep_masked(test_mask: int, test_value: int) -> list:
     keep = (C.c_uint32 * 8)()
     _lib().gsm_global_keep_masked(int(test_mask) & 0xFFFFFFFF, int(test_value) & 0xFFFFFFFF, keep)
     return [int(w) for w in keep]
+
+
+def select_query_default() -> SelectQuery:
+    """gsm_global_select_query_default, read back into a SelectQuery."""
+    s = _SelectQuery()
+    C.memset(C.byref(s), 0xA5, C.sizeof(s))
+    _lib().gsm_global_select_query_default(C.byref(s))
+    return SelectQuery(int(s.shape), int(s.flags), tuple(float(v) for v in s.to_shape), float(s.opacity_min),
+                       float(s.opacity_max), float(s.scale_min), float(s.scale_max), int(s.test_mask),
+                       int(s.test_value))
 
 
 def abi_version() -> int:

@@ -107,6 +107,26 @@ def object_camera(cam: dict, model) -> dict:
     return out
 
 
+def box_to_shape(center, half_extents, rotation=None) -> np.ndarray:
+    """SelectQuery.to_shape of an oriented box (GlobalRenderer.select_where, SELECT_BOX; with SELECT_ELLIPSOID the
+    ellipsoid inscribed in it): twelve float32, the row-major 3x4 that takes scene space to the box's unit cube.
+    rotation: a 3x3 whose rows are the box axes (unit vectors; None: the scene's axes).  Row r is rotation[r] /
+    half_extents[r], with -dot(rotation[r], center) / half_extents[r] in its fourth column; computed in float64
+    and rounded once to float32."""
+    c = np.asarray(center, np.float64).reshape(3)
+    h = np.asarray(half_extents, np.float64).reshape(3)
+    R = np.eye(3) if rotation is None else np.asarray(rotation, np.float64).reshape(3, 3)
+    A = np.empty((3, 4), np.float64)
+    A[:, :3] = R / h[:, None]
+    A[:, 3] = -(R @ c) / h
+    return A.astype(np.float32).reshape(12)
+
+
+def sphere_to_shape(center, radius: float) -> np.ndarray:
+    """SelectQuery.to_shape of a sphere (SELECT_ELLIPSOID): box_to_shape of its bounding cube."""
+    return box_to_shape(center, (radius, radius, radius))
+
+
 def _f16_bits(x: np.ndarray) -> np.ndarray:
     return np.asarray(x, np.float32).astype(np.float16).view(np.uint16)
 

@@ -726,6 +726,108 @@ gsm_status gsm_global_extract(gsm_renderer *renderer, void *stream, const gsm_ga
 gsm_status gsm_global_state_histogram(gsm_renderer *renderer, void *stream, const uint8_t *state,
                                       uint32_t gaussian_count, uint32_t *histogram /* device, 256 words */);
 
+/* Selecting in the scene's own space, and the extent of a selection (no reference analogue).  Every
+ * select above is a screen-space select: it needs a camera and cannot reach what is hidden or off screen.
+ * gsm_global_select_where updates state bytes by a predicate on the records themselves -- inside or outside a box
+ * or an ellipsoid, opacity in a range, largest scale in a range, the current state -- and gsm_global_state_bounds
+ * gives the axis-aligned box and the count of the gaussians in a keep set: "frame the selection", a gizmo's pivot,
+ * the pose of an object separated by gsm_global_extract.
+ *
+ * gsm_global_select_where, the match rule.  Gaussian g < gaussian_count has the old state byte `old` and its record
+ * in the handle's precision: the position is three fp32 values, the opacity and the three scales are fp32, or fp16
+ * widened exactly.  It matches when all of these hold:
+ *   1. (old & test_mask & 0xFF) == (test_value & 0xFF);
+ *   2. styles is NULL, or the style of `old` is not hidden (gsm_global_select_mask's rule, the identity for
+ *      old >= style_count);
+ *   3. the shape test.  With A = to_shape (row-major 3x4) and p the position, for every row r
+ *        q_r = ((A[r][0]*px + A[r][1]*py) + A[r][2]*pz) + A[r][3],
+ *      each multiplication and addition one IEEE fp32 operation in exactly this order, none fused;
+ *        GSM_SELECT_BOX        inside = |q_0| <= 1 && |q_1| <= 1 && |q_2| <= 1,
+ *        GSM_SELECT_ELLIPSOID  inside = ((q_0*q_0 + q_1*q_1) + q_2*q_2) <= 1.
+ *      A gaussian with a NaN in q never matches, with or without GSM_SELECT_OUTSIDE; otherwise the test is
+ *      inside != (flags & GSM_SELECT_OUTSIDE).  GSM_SELECT_ALL skips this step and never reads to_shape;
+ *   4. unless the opacity range is exactly (-inf, +inf): opacity_min <= o && o <= opacity_max (false for a NaN o);
+ *   5. unless the scale range is exactly (-inf, +inf): the same test on m = maxNum(maxNum(sx, sy), sz), which is
+ *      NaN, and fails, only when all three scales are NaN.
+ * No camera is involved and none of the projection's culls applies: a record the frame never draws (behind the
+ * near plane, a scale below 0.0005) is selectable, so that it can be deleted.
+ * A matching gaussian's state becomes ((old & and_mask) ^ xor_mask) & 0xFF.  Every other byte of `state`, and every
+ * byte at or past gaussian_count, keeps its value.  `matched` (device, nullable) receives the number of matching
+ * gaussians: overwritten, not added to.  input->harmonics is not read and may be NULL; sh_components is ignored.
+ * `query` and `styles` are host memory, consumed before the call returns.  Enqueue-only and capturable: a captured
+ * call replays the query, the style table and the pointers it was captured with and reads the state bytes of the
+ * replay.  It neither reads nor changes the handle's last-frame or last-pick state, and gsm_global_set_tile_rows
+ * does not concern it.
+ *
+ * Checks, all before anything is enqueued; the first failing row in this order decides:
+ *   GSM_ERR_INVALID_ARGUMENT         renderer NULL;
+ *   GSM_ERR_INVALID_GAUSSIAN_COUNT   gaussian_count > max_gaussians (the count of a NULL input cannot be read: that
+ *                                    call falls to the next row);
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  input or query NULL; input->gaussians or state NULL with a count > 0;
+ *   GSM_ERR_INVALID_BUFFER_SIZE      matched not 4-byte aligned;
+ *   GSM_ERR_INVALID_ARGUMENT         shape > 2; a flags bit other than bit 0; GSM_SELECT_ALL with GSM_SELECT_OUTSIDE;
+ *                                    a NaN among the four range bounds; with a shape, a non-finite entry of to_shape;
+ *   GSM_ERR_INVALID_ARGUMENT         styles NULL with style_count != 0, or styles non-NULL with style_count 0 or
+ *                                    above 256.
+ * A count of 0 is a no-op that writes *matched = 0.
+ *
+ * gsm_global_state_bounds.  The state and the keep set are gsm_global_extract's: s_g is state->state[g], or
+ * state->default_state when that pointer is NULL, and gaussian g takes part when bit s_g of `keep` is set; {NULL, s}
+ * with a full keep set gives the bounds of the whole scene.  min and max are the exact componentwise minimum and
+ * maximum of the positions taking part whose three coordinates are finite; a coordinate of -0 counts as +0, so the
+ * result has one bit pattern whatever the reduction order.  count is the number of those gaussians, skipped the
+ * number taking part with a NaN or infinite coordinate (they are not in the box): count + skipped is the number
+ * taking part.  The result is overwritten, not accumulated.  The centre and the radius are the caller's arithmetic
+ * on the six numbers; no centroid is formed (a sum's rounding depends on its order).  `state` and `keep` are host
+ * memory, `bounds` is device memory.  Enqueue-only and capturable; the handle's first call allocates 32 bytes per
+ * 256 gaussians of max_gaussians, nothing is allocated after it.
+ *
+ * Checks, in this order:
+ *   GSM_ERR_INVALID_ARGUMENT         renderer NULL;
+ *   GSM_ERR_INVALID_GAUSSIAN_COUNT   gaussian_count > max_gaussians;
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  input, state, keep or bounds NULL;
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  input->gaussians NULL with a count > 0;
+ *   GSM_ERR_INVALID_BUFFER_SIZE      bounds not 4-byte aligned;
+ *   GSM_ERR_INVALID_ARGUMENT         default_state > 255.
+ *
+ * Out of scope: transforming or re-encoding records, colour or SH predicates, a centroid or covariance, shapes
+ * beyond an affine image of the unit cube and the unit ball, selection growth, and the DepthFirst, Local and
+ * multi-GPU renderers, which have no state bytes. */
+#define GSM_SELECT_ALL        0u   /* no shape: to_shape is not read */
+#define GSM_SELECT_BOX        1u
+#define GSM_SELECT_ELLIPSOID  2u
+#define GSM_SELECT_OUTSIDE    1u   /* flags bit 0: the complement of the shape */
+typedef struct {
+    uint32_t shape;            /* GSM_SELECT_ALL, _BOX or _ELLIPSOID */
+    uint32_t flags;            /* 0 or GSM_SELECT_OUTSIDE */
+    float    to_shape[12];     /* row-major 3x4: scene space -> the shape's unit space */
+    float    opacity_min, opacity_max;  /* inclusive; (-inf, +inf): not applied */
+    float    scale_min, scale_max;      /* on the largest of the three scales; inclusive; (-inf, +inf): not applied */
+    uint32_t test_mask, test_value;     /* on the current state byte; (0, 0): every state */
+} gsm_global_select_query;
+typedef struct {
+    float    min[3];   /* +inf when count == 0 */
+    float    max[3];   /* -inf when count == 0 */
+    uint32_t count;    /* gaussians in the keep set with three finite coordinates */
+    uint32_t skipped;  /* gaussians in the keep set with a NaN or infinite coordinate: not in the box */
+} gsm_global_bounds;
+#ifdef __cplusplus
+static_assert(sizeof(gsm_global_select_query) == 80, "gsm_global_select_query is 80 bytes");
+static_assert(sizeof(gsm_global_bounds) == 32, "gsm_global_bounds is 32 bytes");
+#else
+_Static_assert(sizeof(gsm_global_select_query) == 80, "gsm_global_select_query is 80 bytes");
+_Static_assert(sizeof(gsm_global_bounds) == 32, "gsm_global_bounds is 32 bytes");
+#endif
+/* ALL, flags 0, identity rows, both ranges (-inf, +inf), test (0, 0) */
+void gsm_global_select_query_default(gsm_global_select_query *q);
+gsm_status gsm_global_select_where(gsm_renderer *renderer, void *stream, const gsm_gaussian_input *input,
+                                   const gsm_global_select_query *query, uint8_t *state,
+                                   const gsm_global_style *styles, uint32_t style_count,
+                                   uint32_t and_mask, uint32_t xor_mask, uint32_t *matched /* device, nullable */);
+gsm_status gsm_global_state_bounds(gsm_renderer *renderer, void *stream, const gsm_gaussian_input *input,
+                                   const gsm_global_state *state, const uint32_t keep[8],
+                                   gsm_global_bounds *bounds /* device */);
+
 /* GlobalRenderer.renderStereo (GlobalRenderer.swift:240-255) calls fatalError for
  * every target; this entry returns GSM_ERR_UNSUPPORTED instead. */
 gsm_status gsm_global_render_stereo(gsm_renderer *renderer, void *stream,
