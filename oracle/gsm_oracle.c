@@ -851,9 +851,7 @@ void og_radix_sort_pairs(uint32_t *keys, int32_t *values, uint32_t n) {
 }
 
 /* globalRender (GlobalShaders.metal:1030-1187) for one active tile. */
-typedef struct {
-    uint16_t mx, my, cxx, cyy, cxy2, op, cr, cg, cb, dep;
-} blend_rec;
+typedef og_blend_rec blend_rec; /* gsm_oracle.h */
 typedef struct {
     og_frame *f;
     blend_rec *rec; /* per gaussian */
@@ -948,6 +946,62 @@ static void rec_range(void *vctx, uint32_t lo, uint32_t hi) {
         r->cb = og_f2h(H(og_f2h((float)g->colorB)) / 255.0f);
         r->dep = g->depth;
     }
+}
+
+/* The two steps above on a caller's arrays (gsm_oracle.h): the frame's own rec_range and blend_tiles, run on a
+ * frame header that only borrows the caller's pointers. */
+void og_blend_records(const og_render_data *render_data, const uint8_t *mask, uint32_t count, int nthreads,
+                      og_blend_rec *out) {
+    ensure_init();
+    if (!render_data || !mask || !out || count == 0) return;
+    if (nthreads < 1) nthreads = 1;
+    og_frame f;
+    memset(&f, 0, sizeof(f));
+    f.count = count;
+    f.render_data = (og_render_data *)render_data;
+    f.mask = (uint8_t *)mask;
+    rec_ctx RC = {&f, out};
+    parallel_for(nthreads, count, rec_range, &RC);
+}
+
+int og_blend_tiles(const og_blend_rec *rec, const uint32_t *headers, const int32_t *sorted_values,
+                   uint32_t tiles_x, uint32_t tiles_y, uint32_t width, uint32_t height, int nthreads,
+                   uint16_t *color, uint16_t *depth, uint32_t *group_iters) {
+    ensure_init();
+    if (!headers || !color || !depth || !group_iters || tiles_x == 0 || tiles_y == 0 || width == 0 || height == 0 ||
+        width > tiles_x * 32u || height > tiles_y * 16u)
+        return OG_ERR_INVALID_ARGUMENT;
+    if (nthreads < 1) nthreads = 1;
+    og_frame f;
+    memset(&f, 0, sizeof(f));
+    f.width = width;
+    f.height = height;
+    f.tiles_x = tiles_x;
+    f.tiles_y = tiles_y;
+    f.tile_count = tiles_x * tiles_y;
+    f.headers = (uint32_t *)headers;
+    f.sorted_values = (int32_t *)sorted_values;
+    f.color = color;
+    f.depth = depth;
+    f.group_iters = group_iters;
+    uint32_t *active = (uint32_t *)calloc(f.tile_count, sizeof(uint32_t));
+    if (!active) return OG_ERR_OUT_OF_MEMORY;
+    uint32_t nact = 0;
+    for (uint32_t tile = 0; tile < f.tile_count; ++tile) {
+        if (headers[2 * tile + 1] > 0 && (!rec || !sorted_values)) { free(active); return OG_ERR_INVALID_ARGUMENT; }
+        if (headers[2 * tile + 1] > 0) active[nact++] = tile;
+    }
+    memset(group_iters, 0, sizeof(uint32_t) * (size_t)f.tile_count * 64);
+    /* clearRenderTexturesKernel, as og_render: color (0,0,0,1), depth 0 */
+    for (size_t i = 0; i < (size_t)width * height; ++i) {
+        color[4 * i + 0] = 0; color[4 * i + 1] = 0; color[4 * i + 2] = 0;
+        color[4 * i + 3] = 0x3C00u;
+        depth[i] = 0;
+    }
+    blend_ctx B = {&f, (blend_rec *)rec, active};
+    parallel_for_interleaved(nthreads, nact, blend_tiles, &B);
+    free(active);
+    return OG_OK;
 }
 
 void og_frame_free(og_frame *f) {

@@ -119,6 +119,23 @@ uint32_t og_sort_key(uint32_t tile, uint16_t depth_h);
 /* Stable LSD radix sort of (key,value) pairs, 8-bit digits (RadixSortEncoder.swift:41-101). */
 void og_radix_sort_pairs(uint32_t *keys, int32_t *values, uint32_t n);
 
+/* The per-gaussian values the blend reads (globalRender's per-entry values, GlobalShaders.metal:1094-1105), all
+ * fp16 bits: mean, conic (cxx, cyy, 2 cxy), opacity, colour, depth. */
+typedef struct {
+    uint16_t mx, my, cxx, cyy, cxy2, op, cr, cg, cb, dep;
+} og_blend_rec;
+/* Two steps of og_render on the caller's arrays (the same functions the frame calls).
+ * og_blend_records: out[i] from render_data[i] for every i with mask[i] != 0 (others untouched).
+ * og_blend_tiles: the tile blend of a width x height frame (tiles_x x tiles_y tiles of 32 x 16 pixels covering
+ * it) from blend records, headers {offset, count}[tiles_x * tiles_y] and the sorted values they index; writes
+ * color[height * width * 4] (rgba16f bits, cleared to (0, 0, 0, 1) first), depth[height * width] (cleared to 0)
+ * and group_iters[tiles_x * tiles_y * 64] (0 for tiles without entries).  Returns OG_OK or an OG_ERR_*. */
+void og_blend_records(const og_render_data *render_data, const uint8_t *mask, uint32_t count, int nthreads,
+                      og_blend_rec *out);
+int og_blend_tiles(const og_blend_rec *rec, const uint32_t *headers, const int32_t *sorted_values,
+                   uint32_t tiles_x, uint32_t tiles_y, uint32_t width, uint32_t height, int nthreads,
+                   uint16_t *color, uint16_t *depth, uint32_t *group_iters);
+
 /* The colour target's pixel format (include/gsm_renderer.h gsm_color_format): converts n
  * rgba16f pixels (the frame's colour) into dst -- 0 rgba16f copy, 1 rgba32f, 2 rgba8 unorm,
  * 3 rgba8 unorm sRGB, 4 bgra8 unorm, 5 bgra8 unorm sRGB.  Returns bytes per pixel or 0. */

@@ -28,6 +28,8 @@ STEREO_RENDER_DATA = np.dtype([(f, "<u2") for f in (
     "rightMeanX", "rightMeanY", "rightCxx", "rightCyy", "rightCxy2", "rightDepth")] +
     [("colorR", "u1"), ("colorG", "u1"), ("colorB", "u1"), ("opacity", "u1"),
      ("centerDepth", "<u2"), ("pad0", "<u2")])
+BLEND_REC = np.dtype([(f, "<u2") for f in ("mx", "my", "cxx", "cyy", "cxy2", "op", "cr", "cg", "cb", "dep")])
+assert BLEND_REC.itemsize == 20
 assert WORLD32.itemsize == 48 and WORLD16.itemsize == 32 and RENDER_DATA.itemsize == 16
 assert STEREO_RENDER_DATA.itemsize == 32
 
@@ -95,6 +97,11 @@ def lib():
                                 C.POINTER(C.POINTER(OgFrame))]
         L.og_render.restype = C.c_int
         L.og_frame_free.argtypes = [C.POINTER(OgFrame)]
+        L.og_blend_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
+        L.og_blend_records.restype = None
+        L.og_blend_tiles.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                     C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.og_blend_tiles.restype = C.c_int
         L.og_sort_key.argtypes = [C.c_uint32, C.c_uint16]
         L.og_sort_key.restype = C.c_uint32
         L.og_radix_sort_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
@@ -260,6 +267,41 @@ def _nthreads(nthreads: int) -> int:
     if nthreads > 0:
         return nthreads
     return int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or min(16, os.cpu_count() or 1)
+
+
+def blend_records(render_data: np.ndarray, mask: np.ndarray, nthreads: int = 0) -> np.ndarray:
+    """og_blend_records: the frame's per-gaussian blend record (BLEND_REC) of every render_data[i] with mask[i];
+    the others stay zero."""
+    rd = np.ascontiguousarray(render_data, RENDER_DATA)
+    m = np.ascontiguousarray(mask, np.uint8)
+    assert rd.shape == m.shape
+    out = np.zeros(rd.size, BLEND_REC)
+    if rd.size:
+        lib().og_blend_records(rd.ctypes.data, m.ctypes.data, rd.size, _nthreads(nthreads), out.ctypes.data)
+    return out
+
+
+def blend_tiles(rec: np.ndarray, headers: np.ndarray, sorted_values: np.ndarray, tiles_x: int, tiles_y: int,
+                width: int, height: int, nthreads: int = 0) -> dict:
+    """og_blend_tiles: the frame's tile blend on the caller's blend records (BLEND_REC), headers
+    ({offset, count} per tile) and sorted values; colour, depth and group_iters as render() returns them."""
+    rec = np.ascontiguousarray(rec, BLEND_REC)
+    hdr = np.ascontiguousarray(headers, np.uint32).reshape(-1)
+    vals = np.ascontiguousarray(sorted_values, np.int32)
+    assert hdr.size == 2 * tiles_x * tiles_y
+    cnt = hdr[1::2]
+    live = cnt > 0
+    assert not live.any() or int((hdr[0::2][live].astype(np.int64) + cnt[live]).max()) <= vals.size
+    assert vals.size == 0 or (vals.max() < rec.size)
+    color = np.zeros((height, width, 4), np.uint16)
+    depth = np.zeros((height, width), np.uint16)
+    iters = np.zeros((tiles_x * tiles_y, 8, 8), np.uint32)
+    rc = lib().og_blend_tiles(rec.ctypes.data if rec.size else None, hdr.ctypes.data,
+                              vals.ctypes.data if vals.size else None, tiles_x, tiles_y, width, height,
+                              _nthreads(nthreads), color.ctypes.data, depth.ctypes.data, iters.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"og_blend_tiles: status {rc}")
+    return {"color": color, "depth": depth, "group_iters": iters}
 
 
 def sincos_theta(theta: float):
