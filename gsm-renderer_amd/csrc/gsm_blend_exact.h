@@ -14,18 +14,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "gsm_blend_common.h"
 #include "gsm_types.h"
 
 namespace gsm {
 namespace blend_exact {
 
-typedef _Float16 xh1;
-typedef _Float16 xh2 __attribute__((ext_vector_type(2)));
-typedef unsigned short xu16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ xh2 x_h2(uint32_t u) { return __builtin_bit_cast(xh2, u); }
-__device__ __forceinline__ uint32_t x_u32(xh2 v) { return __builtin_bit_cast(uint32_t, v); }
-__device__ __forceinline__ xh2 x_lo(xh2 v) { return xh2{v.x, v.x}; }
-__device__ __forceinline__ xh2 x_hi(xh2 v) { return xh2{v.y, v.y}; }
 template <int CTRL>
 __device__ __forceinline__ uint32_t x_dpp_or(uint32_t v) {
     return v | (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
@@ -70,25 +64,25 @@ __device__ __forceinline__ void walk_unit_exact(const uint32_t* __restrict__ lst
         offY0 = (grp >> 2) * 2u;
         offY1 = offY0 + 1u;
     }
-    const xh2 ONE = {(xh1)1.0f, (xh1)1.0f}, ZERO = {(xh1)0.0f, (xh1)0.0f};
-    const xh1 c099 = (xh1)0.99;
-    const xh2 C099 = {c099, c099};
-    const xh2 X = {(xh1)(float)(ux + offX), (xh1)(float)(ux + offX + 1u)};
-    const xh2 Yv = {(xh1)(float)(uy + offY0), (xh1)(float)(uy + offY1)};
-    xh2 T[P], R[P], G[P], B[P], D[P];
+    const h2 ONE = {(h1)1.0f, (h1)1.0f}, ZERO = {(h1)0.0f, (h1)0.0f};
+    const h1 c099 = (h1)0.99;
+    const h2 C099 = {c099, c099};
+    const h2 X = {(h1)(float)(ux + offX), (h1)(float)(ux + offX + 1u)};
+    const h2 Yv = {(h1)(float)(uy + offY0), (h1)(float)(uy + offY1)};
+    h2 T[P], R[P], G[P], B[P], D[P];
 #pragma unroll
     for (int q = 0; q < P; ++q) {
         T[q] = ONE;
         R[q] = G[q] = B[q] = D[q] = ZERO;
     }
-    xh2 best[P];
+    h2 best[P];
     uint32_t pk[P][2];
 #pragma unroll
     for (int q = 0; q < P; ++q) {
         best[q] = ZERO;
         pk[q][0] = pk[q][1] = 0xFFFFFFFFu;  // GSM_PICK_NONE
     }
-    xh2 Z[P];
+    h2 Z[P];
     uint32_t open[P];  // 0xFFFF in the half of every pixel that is not closed
 #pragma unroll
     for (int q = 0; q < P; ++q) {
@@ -96,12 +90,12 @@ __device__ __forceinline__ void walk_unit_exact(const uint32_t* __restrict__ lst
         open[q] = 0xFFFFFFFFu;
     }
     if constexpr (OCC) {
-        Z[0] = x_h2(limits(ux + offX, uy + offY0));
-        if (P == 2) Z[P - 1] = x_h2(limits(ux + offX, uy + offY1));
+        Z[0] = as_h2(limits(ux + offX, uy + offY0));
+        if (P == 2) Z[P - 1] = as_h2(limits(ux + offX, uy + offY1));
     }
     bool alive = true;
     const uint32_t last = count - 1u;
-    const uint4 pad = make_uint4(x_u32(xh2{(xh1)(float)ux, (xh1)(float)uy}), 0u, 0u, 0u);
+    const uint4 pad = make_uint4(as_u32(h2{(h1)(float)ux, (h1)(float)uy}), 0u, 0u, 0u);
     for (uint32_t b0 = 0; b0 < count; b0 += 64u) {
         uint32_t gi = lst[min(b0 + lane, last)];
         if constexpr (OCC) gi &= idMask;
@@ -123,10 +117,10 @@ __device__ __forceinline__ void walk_unit_exact(const uint32_t* __restrict__ lst
         const uint32_t n = min(64u, count - b0);
         for (uint32_t j = 0; j < n; ++j) {
             // group break before the entry (GlobalShaders.metal:1086-1088): max T of the 4x2 group
-            xu16x2 tm = __builtin_bit_cast(xu16x2, OCC ? (x_u32(T[0]) & open[0]) : x_u32(T[0]));
+            u16x2 tm = __builtin_bit_cast(u16x2, OCC ? (as_u32(T[0]) & open[0]) : as_u32(T[0]));
 #pragma unroll
             for (int q = 1; q < P; ++q)
-                tm = __builtin_elementwise_max(tm, __builtin_bit_cast(xu16x2, OCC ? (x_u32(T[q]) & open[q]) : x_u32(T[q])));
+                tm = __builtin_elementwise_max(tm, __builtin_bit_cast(u16x2, OCC ? (as_u32(T[q]) & open[q]) : as_u32(T[q])));
             const uint32_t tb = __builtin_bit_cast(uint32_t, tm);
             uint32_t gm = max(tb & 0xFFFFu, tb >> 16);
             gm = x_dpp_max<0xB1>(gm);
@@ -136,42 +130,42 @@ __device__ __forceinline__ void walk_unit_exact(const uint32_t* __restrict__ lst
             const uint4 ra = stA[j];
             const uint32_t bd = stB[j];
             // p = ((dx*dx)*cxx + (dy*dy)*cyy) + (dx*dy)*cxy2 (GlobalShaders.metal:1115-1122)
-            const xh2 mean = x_h2(ra.x), cc = x_h2(ra.y), oc = x_h2(ra.z);
-            const xh2 dyv = Yv - x_hi(mean);
-            const xh2 dyy = (dyv * dyv) * x_hi(cc);
-            const xh2 dx = X - x_lo(mean);
-            xh2 pq[P];
+            const h2 mean = as_h2(ra.x), cc = as_h2(ra.y), oc = as_h2(ra.z);
+            const h2 dyv = Yv - splat_hi(mean);
+            const h2 dyy = (dyv * dyv) * splat_hi(cc);
+            const h2 dx = X - splat_lo(mean);
+            h2 pq[P];
             if constexpr (P == 2) {
-                const xh2 dxx = (dx * dx) * x_lo(cc);
-                pq[0] = (dxx + x_lo(dyy)) + (dx * x_lo(dyv)) * x_lo(oc);
-                pq[1] = (dxx + x_hi(dyy)) + (dx * x_hi(dyv)) * x_lo(oc);
+                const h2 dxx = (dx * dx) * splat_lo(cc);
+                pq[0] = (dxx + splat_lo(dyy)) + (dx * splat_lo(dyv)) * splat_lo(oc);
+                pq[1] = (dxx + splat_hi(dyy)) + (dx * splat_hi(dyv)) * splat_lo(oc);
             } else {
-                pq[0] = ((dx * dx) * x_lo(cc) + x_lo(dyy)) + (dx * x_lo(dyv)) * x_lo(oc);
+                pq[0] = ((dx * dx) * splat_lo(cc) + splat_lo(dyy)) + (dx * splat_lo(dyv)) * splat_lo(oc);
             }
-            xh2 ac[P], om[P];
+            h2 ac[P], om[P];
             uint32_t nz = 0;
 #pragma unroll
             for (int q = 0; q < P; ++q) {
-                const uint32_t pb = x_u32(pq[q]);
-                const xh2 ek = x_h2((uint32_t)tbl[pb & 0xFFFFu] | ((uint32_t)tbl[pb >> 16] << 16));
+                const uint32_t pb = as_u32(pq[q]);
+                const h2 ek = as_h2((uint32_t)tbl[pb & 0xFFFFu] | ((uint32_t)tbl[pb >> 16] << 16));
                 // a = min(opacity * exp(-0.5h * p), 0.99h) (GlobalShaders.metal:1124-1131)
-                ac[q] = __builtin_elementwise_min(x_hi(oc) * ek, C099);
+                ac[q] = __builtin_elementwise_min(splat_hi(oc) * ek, C099);
                 if constexpr (OCC) {
-                    const xh1 dep = x_h2(bd).y;
+                    const h1 dep = as_h2(bd).y;
                     if (Z[q].x < dep) open[q] &= 0xFFFF0000u;
                     if (Z[q].y < dep) open[q] &= 0x0000FFFFu;
-                    ac[q] = x_h2(x_u32(ac[q]) & open[q]);
+                    ac[q] = as_h2(as_u32(ac[q]) & open[q]);
                 }
                 om[q] = ONE - ac[q];
-                nz |= x_u32(ac[q]) & 0x7FFF7FFFu;
+                nz |= as_u32(ac[q]) & 0x7FFF7FFFu;
             }
             nz = x_dpp_or<0xB1>(nz);
             if (P == 1) nz = x_dpp_or<0x4E>(nz);
             if (alive && nz != 0u) {  // the group's alphas are not all zero (GlobalShaders.metal:1133)
-                const xh2 rgv = x_h2(ra.w), bdv = x_h2(bd);
+                const h2 rgv = as_h2(ra.w), bdv = as_h2(bd);
 #pragma unroll
                 for (int q = 0; q < P; ++q) {
-                    const xh2 w = ac[q] * T[q];  // (GlobalShaders.metal:1137-1149)
+                    const h2 w = ac[q] * T[q];  // (GlobalShaders.metal:1137-1149)
                     if constexpr (PICK) {
                         const uint32_t item = stI[j];
                         if (w.x > best[q].x) {
@@ -184,10 +178,10 @@ __device__ __forceinline__ void walk_unit_exact(const uint32_t* __restrict__ lst
                         }
                     }
                     T[q] = T[q] * om[q];
-                    R[q] = __builtin_elementwise_fma(x_lo(rgv), w, R[q]);
-                    G[q] = __builtin_elementwise_fma(x_hi(rgv), w, G[q]);
-                    B[q] = __builtin_elementwise_fma(x_lo(bdv), w, B[q]);
-                    D[q] = __builtin_elementwise_fma(x_hi(bdv), w, D[q]);
+                    R[q] = __builtin_elementwise_fma(splat_lo(rgv), w, R[q]);
+                    G[q] = __builtin_elementwise_fma(splat_hi(rgv), w, G[q]);
+                    B[q] = __builtin_elementwise_fma(splat_lo(bdv), w, B[q]);
+                    D[q] = __builtin_elementwise_fma(splat_hi(bdv), w, D[q]);
                 }
             }
         }

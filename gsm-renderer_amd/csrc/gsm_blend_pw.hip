@@ -18,47 +18,22 @@
 // longest job is no longer than before.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
+#include <tuple>
 #include <type_traits>
 
 #include "../../include/gsm_renderer.h"
+#include "gsm_blend_common.h"
 #include "gsm_blend_exact.h"
-#include "gsm_detmath.h"
+#include "gsm_blend_plan.h"
 #include "gsm_internal.h"
-#include "gsm_types.h"
 
 namespace gsm {
 namespace {
 
-typedef _Float16 h1;
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ h2 as_h2(uint32_t u) { return __builtin_bit_cast(h2, u); }
-__device__ __forceinline__ uint32_t as_u32(h2 v) { return __builtin_bit_cast(uint32_t, v); }
-__device__ __forceinline__ h2 splat_lo(h2 v) { return h2{v.x, v.x}; }
-__device__ __forceinline__ h2 splat_hi(h2 v) { return h2{v.y, v.y}; }
-// `color += gColor * w`: one fused multiply-add per channel
-__device__ __forceinline__ h2 acc_fma(h2 acc, h2 c, h2 w) { return __builtin_elementwise_fma(c, w, acc); }
-__device__ __forceinline__ float hbits2f(uint16_t b) { return (float)__builtin_bit_cast(h1, b); }
-__device__ __forceinline__ float srgb_enc(float c) {
-    return c <= 0.0031308f ? c * 12.92f : 1.055f * det_powrf(c, 1.0f / 2.4f) - 0.055f;
-}
-__device__ __forceinline__ void pw_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ uint32_t pw_bperm(uint32_t srcLane, uint32_t v) {
     return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(srcLane * 4u), (int)v);
 }
 __device__ __forceinline__ h2 pw_bperm(uint32_t srcLane, h2 v) { return as_h2(pw_bperm(srcLane, as_u32(v))); }
-
-// the table index of a packed pair of quadratic forms: its fp16 bits (the far-field clamp / dead-column
-// variants: tools/exp/rejected_variants.patch)
-__device__ __forceinline__ uint32_t pw_tbl_bits(h2 p) {
-    return as_u32(p);
-}
 
 struct PwTarget {
     uint8_t* color;
@@ -66,7 +41,7 @@ struct PwTarget {
     uint8_t* depth;
     size_t depthPitch;
     uint32_t W, H;
-    int flags;  // bit 0: 16-B colour / 4-B depth stores allowed; bits 4-7: gsm_color_format
+    int flags;  // kBlendWide: 16-B colour / 4-B depth stores allowed; the format field: gsm_color_format
 };
 
 // one pixel pair (px, py), (px + 1, py) in the target's format (GlobalShaders.metal:1152-1186;
@@ -76,13 +51,13 @@ __device__ __forceinline__ void pw_write_pair(const PwTarget& t, uint32_t px, ui
     if (py >= t.H) return;
     uint8_t* crow = t.color + (size_t)py * t.colorPitch;
     const uint32_t ur = as_u32(Rq), ug = as_u32(Gq), ub = as_u32(Bq), ua = as_u32(Av), ud = as_u32(Dq);
-    const int fmt = (t.flags >> 4) & 15;
+    const int fmt = (t.flags >> kBlendFormatShift) & kBlendFormatMask;
     if (fmt == GSM_COLOR_FORMAT_RGBA16F) {
         const uint32_t p0a = (ur & 0xFFFFu) | (ug << 16);
         const uint32_t p0b = (ub & 0xFFFFu) | (ua << 16);
         const uint32_t p1a = (ur >> 16) | (ug & 0xFFFF0000u);
         const uint32_t p1b = (ub >> 16) | (ua & 0xFFFF0000u);
-        if ((t.flags & 1) && px + 1 < t.W) {
+        if ((t.flags & kBlendWide) && px + 1 < t.W) {
             *(uint4*)(crow + (size_t)px * 8) = make_uint4(p0a, p0b, p1a, p1b);
         } else {
             if (px < t.W) {
@@ -99,11 +74,11 @@ __device__ __forceinline__ void pw_write_pair(const PwTarget& t, uint32_t px, ui
         for (uint32_t i = 0; i < 2; ++i) {
             if (px + i >= t.W) break;
             const uint32_t sh = 16u * i;
-            float c[4] = {hbits2f((uint16_t)(ur >> sh)), hbits2f((uint16_t)(ug >> sh)), hbits2f((uint16_t)(ub >> sh)),
-                          hbits2f((uint16_t)(ua >> sh))};
+            float c[4] = {h_bits_to_f((uint16_t)(ur >> sh)), h_bits_to_f((uint16_t)(ug >> sh)), h_bits_to_f((uint16_t)(ub >> sh)),
+                          h_bits_to_f((uint16_t)(ua >> sh))};
             if (fmt == GSM_COLOR_FORMAT_RGBA32F) {
                 uint8_t* o = crow + (size_t)(px + i) * 16;
-                if (t.flags & 1) {
+                if (t.flags & kBlendWide) {
                     *(uint4*)o = make_uint4(__float_as_uint(c[0]), __float_as_uint(c[1]), __float_as_uint(c[2]),
                                             __float_as_uint(c[3]));
                 } else {
@@ -117,7 +92,7 @@ __device__ __forceinline__ void pw_write_pair(const PwTarget& t, uint32_t px, ui
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 float x = __builtin_fminf(__builtin_fmaxf(c[k], 0.0f), 1.0f);
-                if (srgb && k < 3) x = srgb_enc(x);
+                if (srgb && k < 3) x = srgb_encode(x);
                 u8[k] = (uint32_t)__builtin_rintf(x * 255.0f);
             }
             const bool bgra = fmt >= GSM_COLOR_FORMAT_BGRA8_UNORM;
@@ -127,7 +102,7 @@ __device__ __forceinline__ void pw_write_pair(const PwTarget& t, uint32_t px, ui
     }
     if (t.depth) {
         uint8_t* drow = t.depth + (size_t)py * t.depthPitch;
-        if ((t.flags & 1) && px + 1 < t.W) {
+        if ((t.flags & kBlendWide) && px + 1 < t.W) {
             *(uint32_t*)(drow + (size_t)px * 2) = ud;
         } else {
             if (px < t.W) *(uint16_t*)(drow + (size_t)px * 2) = (uint16_t)(ud & 0xFFFFu);
@@ -149,66 +124,34 @@ __device__ __forceinline__ void pw_write_pair(const PwTarget& t, uint32_t px, ui
 #undef GSM_BLEND_VIEWS
 
 
-// the pair walk for a frame of half-tile units on one GPU (no multi-GPU gather); `waves` per workgroup
-void launch_blend_pw(const FrameGeometry& g, const DeviceArena& A, const FrameTargets& t, const BlendOptions& o,
+// the pair walk plan_blend chose (plan.walk: PairSingle, PairViews or PairBatch) for a frame of half-tile units on
+// one GPU (no multi-GPU gather): the grid, the waves and both flag words are the plan's
+void launch_blend_pw(const FrameGeometry& g, const DeviceArena& A, const FrameTargets& t, const BlendPlan& plan,
                      hipStream_t s) {
     const uint32_t numTiles = frame_tiles(g);
-    if (numTiles == 0) return;
-    void* const color = t.color;
-    void* const depth = t.depth;
-    const size_t colorPitch = t.colorPitch, depthPitch = t.depthPitch;
-    const int numCUs = o.numCUs, colorFormat = o.colorFormat, waves = o.waves;
-    const bool costOrder = o.costOrder;
-    // (a Views frame's later views: the wide stores need the view strides aligned too)
-    const bool strides = g.kind == FrameKind::Views && g.views > 1;
-    const int vec = ((((uintptr_t)color) & 15u) == 0 && (colorPitch & 15u) == 0 &&
-                     (!strides || (g.colorViewStride & 15u) == 0) &&
-                     (depth == nullptr || ((((uintptr_t)depth) & 3u) == 0 && (depthPitch & 3u) == 0 &&
-                                           (!strides || (g.depthViewStride & 3u) == 0))))
-                        ? 1
-                        : 0;
-    const PwTarget tg{(uint8_t*)color, colorPitch, (uint8_t*)depth, depthPitch, g.width, g.height,
-                      vec | ((colorFormat & 15) << 4)};
-    const int flags = 2 | (costOrder ? 4 : 0);
-    const uint32_t units = numTiles * 2u;
-    // (at most two units per wave in the first round)
-    uint32_t grid = (units + (uint32_t)(2 * waves) - 1u) / (uint32_t)(2 * waves);
-    if (grid > (uint32_t)numCUs) grid = (uint32_t)numCUs;
-    if (grid == 0) grid = 1;
-    const uint32_t* order = costOrder ? A.unitOrder : nullptr;
-#define GSM_LAUNCH_PW(NTH)                                                                                          \
-    hipLaunchKernelGGL((k_blend_pw<NTH>), dim3(grid), dim3(NTH), 0, s, A.tileStart, A.rec, A.expTable, A.tileQueue, \
-                       numTiles, g.tilesX, tg, order, A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1],      \
-                       A.halfCount, g.tileCount, A.costMax, g.rowBegin, g.rowStride, flags)
-#define GSM_LAUNCH_PW_VIEWS(NTH)                                                                                    \
-    hipLaunchKernelGGL((k_blend_pw_views<NTH>), dim3(grid), dim3(NTH), 0, s, A.tileStart, A.rec, A.expTable,         \
-                       A.tileQueue, numTiles, g.tilesX, g.tilesPerView, tg, g.colorViewStride, g.depthViewStride,    \
-                       order, A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1], A.halfCount, g.tileCount,      \
-                       A.costMax, flags)
-    // a batch of different views: the targets, sizes and store widths are per view (BatchTarget)
-#define GSM_LAUNCH_PW_BATCH(NTH)                                                                                    \
-    hipLaunchKernelGGL((k_blend_pw_batch<NTH>), dim3(grid), dim3(NTH), 0, s, A.tileStart, A.rec, A.expTable,         \
-                       A.tileQueue, numTiles, (const BatchViewArgs*)g.batchArgs, g.batchTileView, tg.flags & ~1,     \
-                       order, A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1], A.halfCount, g.tileCount,      \
-                       A.costMax, flags)
-    if (g.kind == FrameKind::Batch) {
-        if (waves >= 16) GSM_LAUNCH_PW_BATCH(1024);
-        else if (waves >= 12) GSM_LAUNCH_PW_BATCH(768);
-        else GSM_LAUNCH_PW_BATCH(512);
-        return;
-    }
-#undef GSM_LAUNCH_PW_BATCH
-    if (g.kind == FrameKind::Views) {
-        if (waves >= 16) GSM_LAUNCH_PW_VIEWS(1024);
-        else if (waves >= 12) GSM_LAUNCH_PW_VIEWS(768);
-        else GSM_LAUNCH_PW_VIEWS(512);
-        return;
-    }
-#undef GSM_LAUNCH_PW_VIEWS
-    if (waves >= 16) GSM_LAUNCH_PW(1024);
-    else if (waves >= 12) GSM_LAUNCH_PW(768);
-    else GSM_LAUNCH_PW(512);
-#undef GSM_LAUNCH_PW
+    const PwTarget tg{(uint8_t*)t.color, t.colorPitch, (uint8_t*)t.depth, t.depthPitch, g.width, g.height,
+                      plan.targetFlags};
+    dispatch_blend(plan, [&](auto NTH, auto) {
+        constexpr int kNth = decltype(NTH)::value;
+        const auto launch = [&](auto kernel, const auto& mid, const auto& last) {
+            launch_blend_walk(kernel, plan, kNth, A, g.tileCount, mid, last, s);
+        };
+        switch (plan.walk) {
+            case BlendWalk::PairBatch:  // (the targets, sizes and store widths are per view, BatchTarget)
+                launch(k_blend_pw_batch<kNth>,
+                       std::make_tuple(numTiles, (const BatchViewArgs*)g.batchArgs, g.batchTileView, plan.targetFlags),
+                       std::make_tuple(plan.flags));
+                break;
+            case BlendWalk::PairViews:
+                launch(k_blend_pw_views<kNth>,
+                       std::make_tuple(numTiles, g.tilesX, g.tilesPerView, tg, g.colorViewStride, g.depthViewStride),
+                       std::make_tuple(plan.flags));
+                break;
+            default:  // BlendWalk::PairSingle
+                launch(k_blend_pw<kNth>, std::make_tuple(numTiles, g.tilesX, tg),
+                       std::make_tuple(g.rowBegin, g.rowStride, plan.flags));
+        }
+    });
 }
 
 }  // namespace gsm

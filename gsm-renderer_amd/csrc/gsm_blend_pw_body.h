@@ -9,7 +9,7 @@
 // may belong to different views, so every lane stores through the target of its own unit.  No include guard.
 #if GSM_BLEND_VIEWS == 2
 // the pair walk of a batch of different views (gsm_global_render_batch): numTiles = the sum of the views' tiles;
-// tgFlags: PwTarget::flags without bit 0, which is the view's own
+// tgFlags: PwTarget::flags without kBlendWide, which is the view's own
 template <int NT>
 __global__ __launch_bounds__(NT) void k_blend_pw_batch(
     const uint32_t* __restrict__ tileStart, const BlendRecord* __restrict__ rec,
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(NT) void k_blend_pw(
     __syncthreads();
 
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const bool agePrio = (flags & 2) != 0, split = (flags & 4) != 0;
+    const bool agePrio = (flags & kBlendAgePrio) != 0, split = (flags & kBlendCostSplit) != 0;
     const h2 ONE = {(h1)1.0f, (h1)1.0f};
     const h2 ZERO = {(h1)0.0f, (h1)0.0f};
     const uint32_t thrBits = (uint32_t)__builtin_bit_cast(uint16_t, (h1)(1.0f / 255.0f));
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(NT) void k_blend_pw(
             // tile within its own grid (pixel coordinates are the view's own)
             const BatchTarget& VT = views[__builtin_amdgcn_readfirstlane((uint32_t)tileView[tile])].tg;
             (k ? TG1 : TG0) = PwTarget{VT.color, VT.colorPitch, VT.depth, VT.depthPitch, VT.width, VT.height,
-                                       tgFlags | (int)(VT.vec & 1u)};
+                                       tgFlags | (int)(VT.vec & (uint32_t)kBlendWide)};
             const uint32_t tilesX = VT.tilesX, ltile = tile - VT.tileBase;
             const uint32_t tileX = ltile % tilesX, tileY = ltile / tilesX;
 #elif GSM_BLEND_VIEWS
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(NT) void k_blend_pw(
                 }
                 LA[lane] = A0;
                 LB[lane] = B0;
-                pw_wave_sync();
+                blend_wave_sync();
                 exactD = blend_exact::batch_depth_nonfinite(B0) || blend_exact::batch_depth_nonfinite(B1);
             }
             // the batch at b0 + BS goes into LDS (neutral records past the lane's list); the registers
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(NT) void k_blend_pw(
                 const bool in = b0 + BS + lo < cntL;
                 LA[lane] = make_uint4(in ? A1.x : padL.x, in ? A1.y : 0u, in ? A1.z : 0u, in ? A1.w : 0u);
                 LB[lane] = in ? B1 : 0u;
-                pw_wave_sync();
+                blend_wave_sync();
                 exactD = exactD || blend_exact::batch_depth_nonfinite(in ? B1 : 0u);
                 A1 = *(const uint4*)(rec + I2);
                 B1 = rec[I2].b;
@@ -297,7 +297,7 @@ __global__ __launch_bounds__(NT) void k_blend_pw(
                     bdc[k] = LB[hb + k];
 #pragma unroll
                     for (int q = 0; q < NP; ++q) {
-                        const uint32_t pb = pw_tbl_bits(pq[q]);
+                        const uint32_t pb = tbl_bits(pq[q]);
                         const h2 ek = as_h2((uint32_t)tbl[pb & 0xFFFFu] | ((uint32_t)tbl[pb >> 16] << 16));
                         // a = min(opacity * exp(-0.5h * p), 0.99h) (GlobalShaders.metal:1124-1131)
                         ac[k][q] = __builtin_elementwise_min(splat_hi(as_h2(ra.z)) * ek, C099);
@@ -327,7 +327,7 @@ __global__ __launch_bounds__(NT) void k_blend_pw(
                                 bdn[k] = LB[nb + k];
 #pragma unroll
                                 for (int q = 0; q < NP; ++q) {
-                                    const uint32_t pb = pw_tbl_bits(pq[q]);
+                                    const uint32_t pb = tbl_bits(pq[q]);
                                     en[k][q].x = tbl[pb & 0xFFFFu];
                                     en[k][q].y = tbl[pb >> 16];
                                 }
@@ -359,10 +359,10 @@ __global__ __launch_bounds__(NT) void k_blend_pw(
                                 for (int q = 0; q < NP; ++q) {
                                     const h2 w = ac[k][q] * T[q];  // (GlobalShaders.metal:1137-1149)
                                     T[q] = T[q] * om[k][q];
-                                    R[q] = acc_fma(R[q], splat_lo(rgv), w);
-                                    G[q] = acc_fma(G[q], splat_hi(rgv), w);
-                                    B[q] = acc_fma(B[q], splat_lo(bdv), w);
-                                    D[q] = acc_fma(D[q], splat_hi(bdv), w);
+                                    R[q] = blend_acc(R[q], splat_lo(rgv), w);
+                                    G[q] = blend_acc(G[q], splat_hi(rgv), w);
+                                    B[q] = blend_acc(B[q], splat_lo(bdv), w);
+                                    D[q] = blend_acc(D[q], splat_hi(bdv), w);
                                 }
                             }
                         }
@@ -432,7 +432,7 @@ __global__ __launch_bounds__(NT) void k_blend_pw(
                     }
                     const uint32_t ng = (uint32_t)__popcll(amAll);
                     if (alive) cs[__popcll(amAll & ((1ull << lane) - 1ull))] = lane;
-                    pw_wave_sync();
+                    blend_wave_sync();
                     const uint32_t s = lane >> 1, c = lane & 1u;
                     valid = s < ng;
                     const uint32_t src = cs[valid ? s : 0u];
@@ -468,7 +468,7 @@ __global__ __launch_bounds__(NT) void k_blend_pw(
                     const uint64_t am = __ballot(alive) & 0x5555555555555555ull;
                     const uint32_t ng = (uint32_t)__popcll(am);
                     if (alive && (lane & 1u) == 0u) cs[__popcll(am & ((1ull << lane) - 1ull))] = lane >> 1;
-                    pw_wave_sync();
+                    blend_wave_sync();
                     const uint32_t g2 = lane >> 2, kk = lane & 1u, rr = (lane >> 1) & 1u;
                     valid = g2 < ng;
                     const uint32_t src = 2u * cs[valid ? g2 : 0u] + kk;

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(NT) void k_blend_px_batch_occ_pick(
     const uint8_t* occIn = nullptr;
     size_t colorPitch = 0, depthPitch = 0, pickPitch = 0, occPitch = 0;
     uint32_t W = 0, H = 0, itemBase = 0;
-    const int flags0 = flags & ~(1 | 8192 | 16384);
+    const int flags0 = flags & ~kBlendPerViewExtras;
 #elif GSM_BLEND_PICK && GSM_BLEND_OCCLUDE
 template <int NT, int P, bool COMPACT = false>
 __global__ __launch_bounds__(NT) void k_blend_px_occ_pick(
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(NT) void k_blend_px_batch(
     uint8_t *color = nullptr, *depth = nullptr;
     size_t colorPitch = 0, depthPitch = 0;
     uint32_t W = 0, H = 0;
-    const int flags0 = flags & ~1;
+    const int flags0 = flags & ~kBlendWide;
 #elif GSM_BLEND_VIEWS
 // the blend of a batch of views (gsm_global_render_views): numTiles = views * tilesPerView
 template <int NT, int P, bool COMPACT = false>
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(NT) void k_blend_px(
         if (py < H) {
 #endif
             const uint8_t* zrow = occIn + (size_t)py * occPitch + (size_t)px * 4;
-            if ((flags & 16384) && px + 1 < W) {
+            if ((flags & kBlendOcc8) && px + 1 < W) {
                 const float2 z = *(const float2*)zrow;
                 z0 = z.x;
                 z1 = z.y;
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(NT) void k_blend_px(
     constexpr uint32_t UPT = 4 / P;      // units per tile
     constexpr uint32_t NW = NT / 64;
     constexpr uint32_t UNROLL = NG;
-    const bool agePrio = (flags & 2) != 0;
+    const bool agePrio = (flags & kBlendAgePrio) != 0;
     __shared__ __attribute__((aligned(16))) uint16_t tbl[65536];
 #if !GSM_BLEND_NOCOMPACT
     __shared__ uint32_t cscr[NW][16];  // compaction: the alive groups of each wave, in order
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(NT) void k_blend_px(
     const uint32_t lane = threadIdx.x & 63;
     // write (GlobalShaders.metal:1152-1186): one pixel pair (px, py), (px + 1, py) in the target's
     // format (flags bits 4-7, gsm_color_format; conversion rules in include/gsm_renderer.h)
-    const int colorFmt = (flags >> 4) & 15;
+    const int colorFmt = (flags >> kBlendFormatShift) & kBlendFormatMask;
     // plain stores, also into rank 0's gathered frame of a multi-GPU frame (flags bit 12: released by the
     // workgroup's L2 write-back at its exit; write-through pixel stores measured slower)
     auto st128 = [&](uint8_t* p, uint4 v) { *(uint4*)p = v; };
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(NT) void k_blend_px(
             const uint32_t p0b = (ub & 0xFFFFu) | (ua << 16);
             const uint32_t p1a = (ur >> 16) | (ug & 0xFFFF0000u);
             const uint32_t p1b = (ub >> 16) | (ua & 0xFFFF0000u);
-            if ((flags & 1) && px + 1 < W) {
+            if ((flags & kBlendWide) && px + 1 < W) {
                 st128(crow + (size_t)px * 8, make_uint4(p0a, p0b, p1a, p1b));
             } else {
                 if (px < W) {  // 4-byte stores: any 4-byte aligned pitch
@@ -234,7 +234,7 @@ __global__ __launch_bounds__(NT) void k_blend_px(
                               h_bits_to_f((uint16_t)(ub >> sh)), h_bits_to_f((uint16_t)(ua >> sh))};
                 if (colorFmt == GSM_COLOR_FORMAT_RGBA32F) {
                     uint8_t* o = crow + (size_t)(px + i) * 16;
-                    if (flags & 1) {
+                    if (flags & kBlendWide) {
                         st128(o, make_uint4(__float_as_uint(c[0]), __float_as_uint(c[1]), __float_as_uint(c[2]),
                                             __float_as_uint(c[3])));
                     } else {
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(NT) void k_blend_px(
             }
         }
         if (depth) {
-            if ((flags & 1) && px + 1 < W) {
+            if ((flags & kBlendWide) && px + 1 < W) {
                 std32(depth + (size_t)py * depthPitch + (size_t)px * 2, ud);
             } else {
                 if (px < W) std16(depth + (size_t)py * depthPitch + (size_t)px * 2, (uint16_t)(ud & 0xFFFFu));
@@ -274,7 +274,7 @@ __global__ __launch_bounds__(NT) void k_blend_px(
         pk1 = pk1 == GSM_PICK_NONE ? pk1 : pk1 - itemBase;
 #endif
         uint8_t* prow = pickOut + (size_t)py * pickPitch + (size_t)px * 4;
-        if ((flags & 8192) && px + 1 < W) {
+        if ((flags & kBlendPick8) && px + 1 < W) {
             *(uint2*)prow = make_uint2(pk0, pk1);
         } else {
             if (px < W) st32(prow, pk0);
@@ -310,7 +310,7 @@ __global__ __launch_bounds__(NT) void k_blend_px(
     // them at the top priority, so each SIMD pairs one long walk with one shorter one and the
     // long walk issues nearly as fast as a wave alone (the makespan is the longest walk's).
     const uint32_t wv = threadIdx.x >> 6;
-    const bool split = (flags & 4) != 0;
+    const bool split = (flags & kBlendCostSplit) != 0;
     constexpr uint32_t NTOP = kBlendTopWaves;
     uint32_t qi = !split ? blockIdx.x * NW + wv
                          : (wv < NTOP ? blockIdx.x * NTOP + wv
@@ -321,7 +321,7 @@ __global__ __launch_bounds__(NT) void k_blend_px(
     // A claim made at the start hides the atomic's latency but hands the next position of the
     // longest-first order to a wave that stays busy for the rest of its unit, so mid-length units
     // started late and ran past the end of the work (r03, config 2: blend 140.4 -> 116.8 us late).
-    const uint32_t claimMode = ((uint32_t)flags >> 8) & 3u;
+    const uint32_t claimMode = ((uint32_t)flags >> kBlendClaimShift) & (uint32_t)kBlendClaimMask;
     uint32_t waveMax = 0;  // this wave's longest walk, for the next frame's schedule (costMax)
     // dynamic units: positions gridWaves + stripe + stripes * k from this workgroup's counter
     const uint32_t stripes = (gridDim.x % kQueueStripes) == 0 ? kQueueStripes : 1u;
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(NT) void k_blend_px(
         depthPitch = VT.depthPitch;
         W = VT.width;
         H = VT.height;
-        flags = flags0 | (int)(VT.vec & 1u);
+        flags = flags0 | (int)(VT.vec & (uint32_t)kBlendWide);
 #if GSM_BLEND_PICK && GSM_BLEND_OCCLUDE
         {  // the view's options line (the same uniform index: scalar loads)
             const BatchExtras& VE = extras[__builtin_amdgcn_readfirstlane((uint32_t)tileView[tile])];
@@ -350,7 +350,7 @@ __global__ __launch_bounds__(NT) void k_blend_px(
             occIn = VE.occluder;
             occPitch = VE.occluderPitch;
             itemBase = VE.itemBase;
-            flags |= (int)(VE.align & (8192u | 16384u));
+            flags |= (int)(VE.align & (uint32_t)(kBlendPick8 | kBlendOcc8));
         }
 #endif
         const uint32_t tilesX = VT.tilesX, ltile = tile - VT.tileBase;

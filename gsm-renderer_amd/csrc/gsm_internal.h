@@ -3,7 +3,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <tuple>
 
+#include "gsm_blend_plan.h"
 #include "gsm_host.h"
 #include "gsm_types.h"
 
@@ -70,7 +72,7 @@ struct BatchTarget {  // what a blend unit reads (one 64-B line of the entry)
     uint8_t* depth;  // null: this view has no depth target
     size_t colorPitch, depthPitch;
     uint32_t tileBase, tilesX, tilesY, width, height;
-    uint32_t vec;    // bit 0: 16-B colour / 4-B depth stores are aligned in this view's targets
+    uint32_t vec;    // kBlendWide (bit 0): 16-B colour / 4-B depth stores are aligned in this view's targets
     uint32_t pad[2];
 };
 static_assert(sizeof(BatchTarget) == 64, "BatchTarget: one 64-B line");
@@ -103,8 +105,8 @@ struct BatchExtras {
     const uint8_t* state;     // a styled view's state bytes, or null and defaultState for all its gaussians
     uint32_t defaultState;
     uint32_t styled;          // nonzero: the view's projection applies the batch's style table
-    uint32_t align;           // the blend's flags bit 13 (8192): 8-byte pick stores, bit 14 (16384): 8-byte occluder
-                              // loads are aligned in this view's own pointer and pitch
+    uint32_t align;           // the blend's flags kBlendPick8 (bit 13): 8-byte pick stores, kBlendOcc8 (bit 14): 8-byte
+                              // occluder loads are aligned in this view's own pointer and pitch
     uint32_t itemBase;        // 256 * blockBase: what the pick store subtracts from an item
     uint32_t pad[2];
 };
@@ -593,12 +595,25 @@ struct BlendOptions {
 };
 int launch_blend(const FrameGeometry& geo, const DeviceArena& A, const FrameTargets& targets,
                  const BlendOptions& options, hipStream_t stream);
-// k_blend_pw (gsm_blend_pw.hip): two half-tile units per wave, one GPU's frame; options.waves as resolved
-void launch_blend_pw(const FrameGeometry& geo, const DeviceArena& A, const FrameTargets& targets,
-                     const BlendOptions& options, hipStream_t stream);
-// blend kernel shape: pixel pairs per lane (0 = quadrant kernel) and blend units per tile
+// k_blend_pw (gsm_blend_pw.hip): two half-tile units per wave, one GPU's frame; the plan launch_blend made
+void launch_blend_pw(const FrameGeometry& geo, const DeviceArena& A, const FrameTargets& targets, const BlendPlan& plan,
+                     hipStream_t stream);
+// blend kernel shape: pixel pairs per lane (1 = quadrant kernel) and blend units per tile (gsm_blend_plan.h)
 int blend_pairs_per_lane(uint32_t numTiles, int numCUs);
 uint32_t blend_units_per_tile(uint32_t numTiles, int numCUs);
+// One blend launch of `threads` lanes per workgroup: the arguments every blend kernel takes, around the kernel's own
+// -- `mid` between the queue and the schedule's order (A.unitOrder under kBlendCostSplit), `last` after costMax.
+template <class K, class Mid, class Last>
+void launch_blend_walk(K kernel, const BlendPlan& plan, int threads, const DeviceArena& A, uint32_t tileCount,
+                       const Mid& mid, const Last& last, hipStream_t stream) {
+    const uint32_t* order = (plan.flags & kBlendCostSplit) ? A.unitOrder : nullptr;
+    std::apply(
+        [&](const auto&... args) { hipLaunchKernelGGL(kernel, dim3(plan.grid), dim3(threads), 0, stream, args...); },
+        std::tuple_cat(std::make_tuple(A.tileStart, A.rec, A.expTable, A.tileQueue), mid,
+                       std::make_tuple(order, A.unitCost, A.blendTrace, A.halfVals[0], A.halfVals[1], A.halfCount,
+                                       tileCount, A.costMax),
+                       last));
+}
 
 // Stable LSD radix sort of (key, value) pairs; n read from device memory *nPtr.
 // Returns the index (0/1) of the ping-pong buffer holding the result (or kSortNoSpace).

@@ -766,11 +766,11 @@ gsm_status GlobalRenderer::enqueueBatch(hipStream_t s, const gsm_global_view* vi
         d.tg.tilesY = d.bin.tilesY;
         d.tg.width = V.width;
         d.tg.height = V.height;
-        // the wide stores (16-B colour, 4-B depth pairs) where this view's targets are aligned for them, as
-        // launch_blend decides for a single frame; the bytes are the same either way
-        d.tg.vec = ((((uintptr_t)V.color) & 15u) == 0 && (V.color_pitch_bytes & 15u) == 0 &&
-                    (!V.depth || ((((uintptr_t)V.depth) & 7u) == 0 && (V.depth_pitch_bytes & 7u) == 0)))
-                       ? 1u
+        // the wide stores (16-B colour, 4-B depth pairs) where this view's targets are aligned for them: plan_blend's
+        // rule for a single frame; the bytes are the same either way
+        d.tg.vec = (blend_aligned((uintptr_t)V.color, V.color_pitch_bytes, 16) &&
+                    (!V.depth || blend_aligned((uintptr_t)V.depth, V.depth_pitch_bytes, 8)))
+                       ? (uint32_t)kBlendWide
                        : 0u;
         blockBase += (n + kProjectBlock - 1) / kProjectBlock;
         tileBase += d.bin.tilesX * d.bin.tilesY;
@@ -795,7 +795,7 @@ gsm_status GlobalRenderer::enqueueBatch(hipStream_t s, const gsm_global_view* vi
     rq.shDegree = sh_degree(sh);
     if (options) {
         // the host copy of the per-view options, to the device array in kernel-argument chunks as the entries
-        // above; the alignment bits follow each view's own pointer and pitch, as launch_blend's for a single frame
+        // above; the alignment bits follow each view's own pointer and pitch, by plan_blend's rule for a single frame
         extrasHost_.resize(viewCount);
         for (uint32_t v = 0; v < viewCount; ++v) {
             const BatchViewOptions& O = options[v];
@@ -810,10 +810,11 @@ gsm_status GlobalRenderer::enqueueBatch(hipStream_t s, const gsm_global_view* vi
                 e.state = O.style.states[0].state;
                 e.defaultState = O.style.states[0].default_state;
             }
-            e.align = ((O.pick.pixels && (((uintptr_t)O.pick.pixels) & 7u) == 0 && (O.pick.pitch & 7u) == 0) ? 8192u : 0u) |
-                      ((O.occluder.pixels && (((uintptr_t)O.occluder.pixels) & 7u) == 0 && (O.occluder.pitch & 7u) == 0)
-                           ? 16384u
-                           : 0u);
+            e.align =
+                ((O.pick.pixels && blend_aligned((uintptr_t)O.pick.pixels, O.pick.pitch, 8)) ? (uint32_t)kBlendPick8 : 0u) |
+                ((O.occluder.pixels && blend_aligned((uintptr_t)O.occluder.pixels, O.occluder.pitch, 8))
+                     ? (uint32_t)kBlendOcc8
+                     : 0u);
             e.itemBase = batchHost_[v].blockBase * (uint32_t)kProjectBlock;
         }
         fill_chunks<ExtrasChunk>(extrasHost_, viewCount, [&](const ExtrasChunk& c, uint32_t v0, uint32_t n) {
