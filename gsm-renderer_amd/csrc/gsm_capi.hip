@@ -391,6 +391,18 @@ gsm_status gsm_global_state_bounds(gsm_renderer* r, void* stream, const gsm_gaus
     return r->impl->stateBounds((hipStream_t)stream, input, state, keep, bounds);
 }
 
+gsm_status gsm_global_transform_from_pose(const float rotation[9], float scale, const float translation[3],
+                                          gsm_global_transform_desc* out) {
+    return gsm::transform_from_pose(rotation, scale, translation, out);
+}
+
+gsm_status gsm_global_transform(gsm_renderer* r, void* stream, const gsm_global_scene* scene,
+                                const gsm_global_state* state, const uint32_t keep[8],
+                                const gsm_global_transform_desc* desc) {
+    if (!r || !r->impl) return GSM_ERR_INVALID_ARGUMENT;
+    return r->impl->transform((hipStream_t)stream, scene, state, keep, desc);
+}
+
 gsm_status gsm_global_pick_owner(gsm_renderer* r, const uint32_t* items, uint32_t n, uint32_t* object,
                                  uint32_t* gaussian) {
     if (!r || !r->impl || (n > 0 && (!items || !object || !gaussian))) return GSM_ERR_INVALID_ARGUMENT;

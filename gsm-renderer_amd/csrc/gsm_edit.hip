@@ -1,8 +1,10 @@
-// gsm_edit.hip -- gfx950 kernels of the Global renderer's scene-editing entries (DESIGN.md 28, 30):
+// gsm_edit.hip -- gfx950 kernels of the Global renderer's scene-editing entries (DESIGN.md 28, 30, 33):
 // gsm_global_extract, a stable compaction of a scene's rows by its state bytes, gsm_global_state_histogram,
-// gsm_global_select_where, a select by a world-space and attribute predicate, and gsm_global_state_bounds, the box
-// of a keep set.  No reference analogue.  The extract copies rows byte for byte; the select's only arithmetic is
-// the nine products and nine sums of its shape test, unfused (-ffp-contract=off), and the bounds only compare.
+// gsm_global_select_where, a select by a world-space and attribute predicate, gsm_global_state_bounds, the box
+// of a keep set, and gsm_global_transform, which bakes a pose into the rows of a keep set.  No reference analogue.
+// The extract copies rows byte for byte; the select's only arithmetic is the nine products and nine sums of its shape
+// test, unfused (-ffp-contract=off), the bounds only compare, and the transform applies given fp32 matrices in the
+// order the header writes down, unfused.
 //
 // The extract is three launches in stream order and the launch boundary is the only barrier between workgroups:
 // no kernel here waits for another workgroup (no look-back, no flag, no ticket).
@@ -378,6 +380,183 @@ __global__ __launch_bounds__(kEditBlock) void k_bounds_final(const uint4* __rest
     }
 }
 
+// The fp32 value rounded once to fp16, to nearest even.  The empty asm keeps the compiler from folding the operation
+// that made f into the conversion: for a product it emits v_fma_mixlo_f16 with an addend of +0, which turns a product
+// of -0 into +0 (seen in the assembly; the numpy restatement keeps the -0).
+__device__ __forceinline__ uint16_t transform_round_h(float f) {
+    asm("" : "+v"(f));
+    return f_to_hbits(f);
+}
+
+// gsm_global_transform.  c'_i = (..(D[i][0]*c_0 + D[i][1]*c_1) + ..) + D[i][N-1]*c_{N-1} for one band
+// of one channel, in place.  D is a member of the kernel argument and, after unrolling, every index is a constant: the
+// entries are scalar operands.
+template <int N>
+__device__ __forceinline__ void transform_band(float* c, const float (&D)[N * N]) {
+    float o[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        float acc = D[i * N] * c[0];
+#pragma unroll
+        for (int j = 1; j < N; ++j) acc = acc + D[i * N + j] * c[j];
+        o[i] = acc;
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) c[i] = o[i];
+}
+
+// bands 1..DEG of the K = (DEG + 1)^2 coefficients of one channel
+template <int DEG>
+__device__ __forceinline__ void transform_channel(float* c, const gsm_global_transform_desc& t) {
+    if constexpr (DEG >= 1) transform_band<3>(c + 1, t.sh1);
+    if constexpr (DEG >= 2) transform_band<5>(c + 4, t.sh2);
+    if constexpr (DEG >= 3) transform_band<7>(c + 9, t.sh3);
+}
+
+// The harmonics row of gaussian g: 3 channels of K coefficients, planar.  wide (uniform): the row is a multiple of
+// 16 bytes at a 16-byte aligned address and goes as 16-byte loads and stores, band 0 with its own bits; otherwise
+// element by element, and band 0 is neither loaded nor stored.
+template <bool HALF, int DEG>
+__device__ __forceinline__ void transform_harmonics(void* __restrict__ harm, size_t g,
+                                                    const gsm_global_transform_desc& t, bool wide) {
+    constexpr int K = (DEG + 1) * (DEG + 1), E = 3 * K;
+    float c[E];
+    if constexpr (HALF) {
+        uint16_t* row = (uint16_t*)harm + g * (size_t)E;
+        if constexpr (DEG == 3) {  // 96 bytes, 16-byte aligned (checked on the host): six accesses, as sh_color reads it
+            uint4* p = (uint4*)row;
+            uint32_t hw[E / 2];  // coefficient 2k in the low half of hw[k], 2k + 1 in the high half
+#pragma unroll
+            for (int q = 0; q < E / 8; ++q) {
+                const uint4 v = p[q];
+                hw[4 * q] = v.x;
+                hw[4 * q + 1] = v.y;
+                hw[4 * q + 2] = v.z;
+                hw[4 * q + 3] = v.w;
+            }
+#pragma unroll
+            for (int i = 0; i < E; ++i) c[i] = hbits_to_f((uint16_t)((i & 1) ? hw[i >> 1] >> 16 : hw[i >> 1] & 0xFFFFu));
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) transform_channel<DEG>(c + ch * K, t);
+#pragma unroll
+            for (int i = 0; i < E; ++i) {
+                if (i % K == 0) continue;  // band 0 keeps its bits
+                const uint32_t h = transform_round_h(c[i]);
+                hw[i >> 1] = (i & 1) ? (hw[i >> 1] & 0x0000FFFFu) | (h << 16) : (hw[i >> 1] & 0xFFFF0000u) | h;
+            }
+#pragma unroll
+            for (int q = 0; q < E / 8; ++q) p[q] = make_uint4(hw[4 * q], hw[4 * q + 1], hw[4 * q + 2], hw[4 * q + 3]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < E; ++i)
+                if (i % K != 0) c[i] = hbits_to_f(row[i]);
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) transform_channel<DEG>(c + ch * K, t);
+#pragma unroll
+            for (int i = 0; i < E; ++i)
+                if (i % K != 0) row[i] = transform_round_h(c[i]);
+        }
+    } else {
+        float* row = (float*)harm + g * (size_t)E;
+        if (E % 4 == 0 && wide) {  // (uniform)
+            float4* p = (float4*)row;
+#pragma unroll
+            for (int q = 0; q < E / 4; ++q) {
+                const float4 v = p[q];
+                c[4 * q] = v.x;
+                c[4 * q + 1] = v.y;
+                c[4 * q + 2] = v.z;
+                c[4 * q + 3] = v.w;
+            }
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) transform_channel<DEG>(c + ch * K, t);
+#pragma unroll
+            for (int q = 0; q < E / 4; ++q) p[q] = make_float4(c[4 * q], c[4 * q + 1], c[4 * q + 2], c[4 * q + 3]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < E; ++i)
+                if (i % K != 0) c[i] = row[i];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) transform_channel<DEG>(c + ch * K, t);
+#pragma unroll
+            for (int i = 0; i < E; ++i)
+                if (i % K != 0) row[i] = c[i];
+        }
+    }
+}
+
+// a (x) q, the Hamilton product of the descriptor's quaternion and the record's, (x, y, z, w), in the header's order
+__device__ __forceinline__ void transform_quaternion(const float (&a)[4], float& x, float& y, float& z, float& w) {
+    const float ax = a[0], ay = a[1], az = a[2], aw = a[3];
+    const float nx = ((aw * x + ax * w) + ay * z) - az * y;
+    const float ny = ((aw * y - ax * z) + ay * w) + az * x;
+    const float nz = ((aw * z + ax * y) - ay * x) + az * w;
+    const float nw = ((aw * w - ax * x) - ay * y) - az * z;
+    x = nx; y = ny; z = nz; w = nw;
+}
+
+// One thread per gaussian.  A thread not in the keep set loads its state byte and nothing else.  The fp32 record is
+// three 16-byte loads and three stores, the fp16 one two and two; the opacity and the pad words go back with the bits
+// they came with.  Every store is to the thread's own record and row.
+template <bool HALF, int DEG>
+__global__ __launch_bounds__(kEditBlock) void k_transform(void* __restrict__ world, void* __restrict__ harm,
+                                                          const uint8_t* __restrict__ state, uint32_t defaultState,
+                                                          uint32_t count, KeepSet keep, gsm_global_transform_desc t,
+                                                          uint32_t wideRows) {
+    uint32_t s;
+    if (!thread_kept(state, defaultState, count, keep, &s)) return;
+    const size_t g = (size_t)blockIdx.x * kEditBlock + threadIdx.x;
+    if constexpr (HALF) {
+        uint4* rec = (uint4*)((uint8_t*)world + g * sizeof(PackedWorldGaussianHalf));
+        uint4 w0 = rec[0], w1 = rec[1];
+        const float px = __builtin_bit_cast(float, w0.x), py = __builtin_bit_cast(float, w0.y),
+                    pz = __builtin_bit_cast(float, w0.z);
+        float p[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+            p[r] = ((t.matrix[4 * r] * px + t.matrix[4 * r + 1] * py) + t.matrix[4 * r + 2] * pz) + t.matrix[4 * r + 3];
+        const float sx = hbits_to_f((uint16_t)(w0.w >> 16)) * t.scale;
+        const float sy = hbits_to_f((uint16_t)(w1.x & 0xFFFFu)) * t.scale;
+        const float sz = hbits_to_f((uint16_t)(w1.x >> 16)) * t.scale;
+        float qx = hbits_to_f((uint16_t)(w1.y & 0xFFFFu)), qy = hbits_to_f((uint16_t)(w1.y >> 16));
+        float qz = hbits_to_f((uint16_t)(w1.z & 0xFFFFu)), qw = hbits_to_f((uint16_t)(w1.z >> 16));
+        transform_quaternion(t.quaternion, qx, qy, qz, qw);
+        w0.x = __builtin_bit_cast(uint32_t, p[0]);
+        w0.y = __builtin_bit_cast(uint32_t, p[1]);
+        w0.z = __builtin_bit_cast(uint32_t, p[2]);
+        w0.w = (w0.w & 0xFFFFu) | ((uint32_t)transform_round_h(sx) << 16);
+        w1.x = (uint32_t)transform_round_h(sy) | ((uint32_t)transform_round_h(sz) << 16);
+        w1.y = (uint32_t)transform_round_h(qx) | ((uint32_t)transform_round_h(qy) << 16);
+        w1.z = (uint32_t)transform_round_h(qz) | ((uint32_t)transform_round_h(qw) << 16);
+        rec[0] = w0;
+        rec[1] = w1;
+    } else {
+        uint4* rec = (uint4*)((uint8_t*)world + g * sizeof(PackedWorldGaussian));
+        uint4 w0 = rec[0], w1 = rec[1], w2 = rec[2];
+        const float px = __builtin_bit_cast(float, w0.x), py = __builtin_bit_cast(float, w0.y),
+                    pz = __builtin_bit_cast(float, w0.z);
+        float p[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+            p[r] = ((t.matrix[4 * r] * px + t.matrix[4 * r + 1] * py) + t.matrix[4 * r + 2] * pz) + t.matrix[4 * r + 3];
+        float qx = __builtin_bit_cast(float, w2.x), qy = __builtin_bit_cast(float, w2.y);
+        float qz = __builtin_bit_cast(float, w2.z), qw = __builtin_bit_cast(float, w2.w);
+        transform_quaternion(t.quaternion, qx, qy, qz, qw);
+        w0.x = __builtin_bit_cast(uint32_t, p[0]);
+        w0.y = __builtin_bit_cast(uint32_t, p[1]);
+        w0.z = __builtin_bit_cast(uint32_t, p[2]);
+        w1.x = __builtin_bit_cast(uint32_t, __builtin_bit_cast(float, w1.x) * t.scale);
+        w1.y = __builtin_bit_cast(uint32_t, __builtin_bit_cast(float, w1.y) * t.scale);
+        w1.z = __builtin_bit_cast(uint32_t, __builtin_bit_cast(float, w1.z) * t.scale);
+        w2 = make_uint4(__builtin_bit_cast(uint32_t, qx), __builtin_bit_cast(uint32_t, qy),
+                        __builtin_bit_cast(uint32_t, qz), __builtin_bit_cast(uint32_t, qw));
+        rec[0] = w0;
+        rec[1] = w1;
+        rec[2] = w2;
+    }
+    if constexpr (DEG > 0) transform_harmonics<HALF, DEG>(harm, g, t, wideRows != 0);
+}
+
 // the widest chunk (a power of two, at most 16 bytes) that both addresses and the row width are multiples of
 static uint32_t chunk_width(const void* src, const void* dst, uint64_t rowBytes) {
     const uint64_t x = (uint64_t)(uintptr_t)src | (uint64_t)(uintptr_t)dst | rowBytes | 16u;
@@ -422,6 +601,26 @@ void launch_state_bounds(bool halfInput, const void* world, const uint8_t* state
         hipLaunchKernelGGL(k, dim3(blocks), dim3(kEditBlock), 0, s, world, state, defaultState, count, keep, partials);
     }
     hipLaunchKernelGGL(k_bounds_final, dim3(1), dim3(kEditBlock), 0, s, (const uint4*)partials, blocks, bounds);
+}
+
+template <bool HALF>
+static auto transform_kernel(uint32_t shDegree) {
+    switch (shDegree) {
+        case 0: return k_transform<HALF, 0>;
+        case 1: return k_transform<HALF, 1>;
+        case 2: return k_transform<HALF, 2>;
+        default: return k_transform<HALF, 3>;
+    }
+}
+
+void launch_transform(bool halfInput, uint32_t shDegree, void* world, void* harmonics, const uint8_t* state,
+                      uint32_t defaultState, uint32_t count, const KeepSet& keep, const gsm_global_transform_desc& desc,
+                      bool wideRows, hipStream_t s) {
+    const uint32_t blocks = (count + kEditBlock - 1u) / kEditBlock;
+    if (blocks == 0) return;
+    const auto k = halfInput ? transform_kernel<true>(shDegree) : transform_kernel<false>(shDegree);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(kEditBlock), 0, s, world, harmonics, state, defaultState, count, keep, desc,
+                       wideRows ? 1u : 0u);
 }
 
 }  // namespace gsm

@@ -532,6 +532,13 @@ void launch_select_where(bool halfInput, const void* world, const SelectWhereArg
 constexpr size_t kBoundsPartialBytes = 32;
 void launch_state_bounds(bool halfInput, const void* world, const uint8_t* state, uint32_t defaultState,
                          uint32_t count, const KeepSet& keep, uint4* partials, uint32_t* bounds, hipStream_t stream);
+// gsm_global_transform (gsm_edit.hip: k_transform): one thread per gaussian; one in the keep set
+// rewrites its record and, with shDegree > 0, bands 1..shDegree of its harmonics row in place, by the descriptor's
+// fp32 matrices in the header's order.  The descriptor travels as a kernel argument.  wideRows: the harmonics rows
+// go as 16-byte accesses (transform_wide_rows; always so for the fp16 row of 16).  A count of 0 launches nothing.
+void launch_transform(bool halfInput, uint32_t shDegree, void* world, void* harmonics, const uint8_t* state,
+                      uint32_t defaultState, uint32_t count, const KeepSet& keep, const gsm_global_transform_desc& desc,
+                      bool wideRows, hipStream_t stream);
 // exclusive scan of the per-block sums, total + clamp into the header (GlobalShaders.metal:685-712)
 // project gaussians [0, a.count) of world/harm (already offset to the rank's range) and pack
 // the records of each slab's gaussians into `send` (slab-major, ascending id), counts to sendCounts

@@ -391,6 +391,24 @@ gsm_status GlobalRenderer::stateBounds(hipStream_t s, const gsm_gaussian_input* 
     return GSM_OK;
 }
 
+gsm_status GlobalRenderer::transform(hipStream_t s, const gsm_global_scene* scene, const gsm_global_state* state,
+                                     const uint32_t* keep, const gsm_global_transform_desc* desc) {
+    const bool half = config_.precision == GSM_PRECISION_FLOAT16;
+    const gsm_status st = transform_check(maxGaussians_, half, scene, state, keep, desc);
+    if (st != GSM_OK) return st;
+    if (scene->gaussian_count == 0) return GSM_OK;
+    if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
+    KeepSet k;
+    for (int i = 0; i < 8; ++i) k.w[i] = keep[i];
+    const uint32_t degree = (uint32_t)transform_degree(scene->sh_components);
+    (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's)
+    launch_transform(half, degree, scene->gaussians, degree ? scene->harmonics : nullptr, state->state,
+                     state->default_state, scene->gaussian_count, k, *desc,
+                     degree && transform_wide_rows(half, scene->sh_components, scene->harmonics), s);
+    if (hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;
+    return GSM_OK;
+}
+
 GlobalRenderer::FrameRequest GlobalRenderer::request(FrameKind kind, const ProjectArgs& args, uint32_t width,
                                                      uint32_t height, const FrameTargets& targets) const {
     FrameRequest rq;

@@ -12,6 +12,7 @@
 #include "gsm_internal.h"
 #include "gsm_schedule_key.h"
 #include "gsm_select_check.h"
+#include "gsm_transform_check.h"
 
 namespace gsm {
 
@@ -91,6 +92,10 @@ class GlobalRenderer {
     // the axis-aligned box and the count of the gaussians whose state byte is in the keep set (gsm_global_state_bounds)
     gsm_status stateBounds(hipStream_t stream, const gsm_gaussian_input* input, const gsm_global_state* state,
                            const uint32_t* keep, gsm_global_bounds* bounds);
+    // the pose of `desc` baked into the records and harmonics of the gaussians whose state byte is in the keep set,
+    // in place (gsm_global_transform): no frame state, nothing allocated
+    gsm_status transform(hipStream_t stream, const gsm_global_scene* scene, const gsm_global_state* state,
+                         const uint32_t* keep, const gsm_global_transform_desc* desc);
     // items of the last enqueued pick frame -> (object of the call, gaussian id within it); host only, no sync
     gsm_status pickOwner(const uint32_t* items, uint32_t n, uint32_t* object, uint32_t* gaussian) const;
 

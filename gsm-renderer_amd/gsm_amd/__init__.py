@@ -307,6 +307,20 @@ SELECT_QUERY_BYTES, BOUNDS_BYTES = 80, 32  # include/gsm_renderer.h: asserted th
 assert C.sizeof(_SelectQuery) == SELECT_QUERY_BYTES and C.sizeof(_Bounds) == BOUNDS_BYTES
 
 
+class _Scene(C.Structure):  # gsm_global_scene
+    _fields_ = [("gaussians", C.c_void_p), ("harmonics", C.c_void_p),
+                ("gaussian_count", C.c_uint32), ("sh_components", C.c_uint32)]
+
+
+class _TransformDesc(C.Structure):  # gsm_global_transform_desc
+    _fields_ = [("matrix", C.c_float * 12), ("quaternion", C.c_float * 4), ("scale", C.c_float),
+                ("sh1", C.c_float * 9), ("sh2", C.c_float * 25), ("sh3", C.c_float * 49)]
+
+
+SCENE_BYTES, TRANSFORM_DESC_BYTES = 24, 400  # include/gsm_renderer.h: asserted there
+assert C.sizeof(_Scene) == SCENE_BYTES and C.sizeof(_TransformDesc) == TRANSFORM_DESC_BYTES
+
+
 class _FrameSortDesc(C.Structure):  # gsm_debug_frame_sort_desc (include/gsm_debug.h)
     _fields_ = [("shift", C.c_uint32), ("num_tiles", C.c_uint32), ("all_tiles", C.c_uint32),
                 ("depth_sort", C.c_uint32), ("full", C.c_uint32), ("reserved", C.c_uint32)]
@@ -407,6 +421,10 @@ _SIGNATURES = {
                                  C.POINTER(_Style), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p], C.c_int),
     "gsm_global_state_bounds": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_State),
                                  C.POINTER(C.c_uint32), C.c_void_p], C.c_int),
+    "gsm_global_transform_from_pose": ([C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float),
+                                        C.POINTER(_TransformDesc)], C.c_int),
+    "gsm_global_transform": ([C.c_void_p, C.c_void_p, C.POINTER(_Scene), C.POINTER(_State), C.POINTER(C.c_uint32),
+                              C.POINTER(_TransformDesc)], C.c_int),
     "gsm_global_render_stereo": ([C.c_void_p, C.c_void_p, C.POINTER(_Input), C.POINTER(_Camera),
                                   C.POINTER(_Camera), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                   C.c_void_p, C.c_size_t], C.c_int),
@@ -998,6 +1016,18 @@ class GlobalRenderer(_Renderer):
                                             None if state is None else C.byref(_state_struct(state)), words,
                                             _ptr(bounds))
         _check(st, "gsm_global_state_bounds")
+
+    def transform(self, gaussians, harmonics, count: int, sh_components: int, state, keep, transform, stream=None):
+        """gsm_global_transform: the pose of `transform` (a Transform; None: NULL) baked, in place, into the records
+        `gaussians` and the rows `harmonics` (CUDA tensors) of the gaussians whose state byte has its bit in `keep`:
+        position, scales and rotation moved, bands 1 and up of the harmonics rotated.  state and keep: as
+        GlobalRenderer.extract takes them.  harmonics may be None with sh_components 0 or 1."""
+        scene = _Scene(_ptr(gaussians), _ptr(harmonics), int(count), int(sh_components))
+        words = None if keep is None else (C.c_uint32 * 8)(*[int(w) & 0xFFFFFFFF for w in keep])
+        st = _lib().gsm_global_transform(self._h, _stream_handle(stream), C.byref(scene),
+                                         None if state is None else C.byref(_state_struct(state)), words,
+                                         None if transform is None else C.byref(transform.struct()))
+        _check(st, "gsm_global_transform")
 
     def pick_owner(self, items):
         """gsm_global_pick_owner: items of the last enqueued pick frame (any integer array, host) ->
@@ -1658,6 +1688,47 @@ def keep_masked(test_mask: int, test_value: int) -> list:
     keep = (C.c_uint32 * 8)()
     _lib().gsm_global_keep_masked(int(test_mask) & 0xFFFFFFFF, int(test_value) & 0xFFFFFFFF, keep)
     return [int(w) for w in keep]
+
+
+class Transform:
+    """gsm_global_transform_desc: a rotation, a uniform scale and a translation as GlobalRenderer.transform applies
+    them -- matrix (12 floats, row-major 3x4, s R | t), quaternion (x, y, z, w of R), scale, and sh1, sh2, sh3, the
+    row-major band matrices of R for the harmonics.  All float32 arrays; the entry applies them as they are."""
+
+    def __init__(self, matrix, quaternion, scale, sh1, sh2, sh3):
+        f = lambda v, n: np.ascontiguousarray(np.asarray(v, np.float32).reshape(n))
+        self.matrix, self.quaternion, self.scale = f(matrix, 12), f(quaternion, 4), np.float32(scale)
+        self.sh1, self.sh2, self.sh3 = f(sh1, 9), f(sh2, 25), f(sh3, 49)
+
+    @classmethod
+    def from_pose(cls, rotation, scale: float, translation) -> "Transform":
+        """gsm_global_transform_from_pose: rotation is a 3x3 (row-major when flat), scale > 0, translation 3 values,
+        each rounded to float32 on the way in.  Raises RendererError where the helper refuses."""
+        R = (C.c_float * 9)(*[float(v) for v in np.asarray(rotation, np.float64).reshape(9)])
+        t = (C.c_float * 3)(*[float(v) for v in np.asarray(translation, np.float64).reshape(3)])
+        d = _TransformDesc()
+        _check(_lib().gsm_global_transform_from_pose(R, float(scale), t, C.byref(d)), "gsm_global_transform_from_pose")
+        return cls(list(d.matrix), list(d.quaternion), d.scale, list(d.sh1), list(d.sh2), list(d.sh3))
+
+    @classmethod
+    def from_matrix(cls, M) -> "Transform":
+        """The Transform of a similarity M: a 4x4, column-major flat as scenes.object_camera and scenes.pose_matrix
+        have it.  M is split in float64 into s = det(A)^(1/3), R = A / s and t, A its upper 3x3; ValueError when its
+        last row is not (0, 0, 0, 1) or its determinant is not positive, RendererError when R is no rotation."""
+        m = np.asarray(M, np.float64).reshape(4, 4).T
+        if not np.array_equal(m[3], [0.0, 0.0, 0.0, 1.0]):
+            raise ValueError("Transform.from_matrix: the last row is not (0, 0, 0, 1)")
+        det = float(np.linalg.det(m[:3, :3]))
+        if not (np.isfinite(det) and det > 0.0):
+            raise ValueError("Transform.from_matrix: the determinant is not positive")
+        s = det ** (1.0 / 3.0)
+        return cls.from_pose(m[:3, :3] / s, s, m[:3, 3])
+
+    def struct(self) -> _TransformDesc:
+        d = _TransformDesc()
+        d.matrix[:], d.quaternion[:], d.scale = self.matrix.tolist(), self.quaternion.tolist(), float(self.scale)
+        d.sh1[:], d.sh2[:], d.sh3[:] = self.sh1.tolist(), self.sh2.tolist(), self.sh3.tolist()
+        return d
 
 
 def select_query_default() -> SelectQuery:

@@ -107,6 +107,16 @@ def object_camera(cam: dict, model) -> dict:
     return out
 
 
+def pose_matrix(rotation, scale: float, translation) -> np.ndarray:
+    """The model matrix of a rotation (3x3, rows by columns), a uniform scale and a translation: sixteen float64,
+    column-major flat like `model` of object_camera and scene_transform, with scale * rotation in its upper 3x3 and
+    the translation in its last column.  Transform.from_matrix takes it apart again."""
+    M = np.eye(4)
+    M[:3, :3] = float(scale) * np.asarray(rotation, np.float64).reshape(3, 3)
+    M[:3, 3] = np.asarray(translation, np.float64).reshape(3)
+    return M.T.reshape(16).copy()
+
+
 def box_to_shape(center, half_extents, rotation=None) -> np.ndarray:
     """SelectQuery.to_shape of an oriented box (GlobalRenderer.select_where, SELECT_BOX; with SELECT_ELLIPSOID the
     ellipsoid inscribed in it): twelve float32, the row-major 3x4 that takes scene space to the box's unit cube.

@@ -702,9 +702,9 @@ gsm_status gsm_global_select_pick_ids(gsm_renderer *renderer, void *stream,
  *   GSM_ERR_MISSING_REQUIRED_BUFFER  histogram NULL, or state NULL with a count > 0;
  *   GSM_ERR_INVALID_BUFFER_SIZE      histogram not 4-byte aligned.
  *
- * Out of scope: transforming the kept gaussians (baking a pose rotates the SH rows: arithmetic), merging scenes (a
- * plain copy concatenates their rows), extraction in place, and the DepthFirst, Local and multi-GPU renderers,
- * which have no state bytes. */
+ * Transforming the kept gaussians is gsm_global_transform's (below; baking a pose rotates the SH rows: arithmetic,
+ * stated there).  Out of scope: merging scenes (a plain copy concatenates their rows), extraction in place, and the
+ * DepthFirst, Local and multi-GPU renderers, which have no state bytes. */
 typedef struct {
     void *gaussians;   /* capacity records of the handle's precision (48 B or 32 B) */
     void *harmonics;   /* capacity rows of 3 * sh_components floats or halfs; ignored when sh_components == 0 */
@@ -790,9 +790,9 @@ gsm_status gsm_global_state_histogram(gsm_renderer *renderer, void *stream, cons
  *   GSM_ERR_INVALID_BUFFER_SIZE      bounds not 4-byte aligned;
  *   GSM_ERR_INVALID_ARGUMENT         default_state > 255.
  *
- * Out of scope: transforming or re-encoding records, colour or SH predicates, a centroid or covariance, shapes
- * beyond an affine image of the unit cube and the unit ball, selection growth, and the DepthFirst, Local and
- * multi-GPU renderers, which have no state bytes. */
+ * Transforming the records is gsm_global_transform's (below).  Out of scope: re-encoding records, colour or SH
+ * predicates, a centroid or covariance, shapes beyond an affine image of the unit cube and the unit ball, selection
+ * growth, and the DepthFirst, Local and multi-GPU renderers, which have no state bytes. */
 #define GSM_SELECT_ALL        0u   /* no shape: to_shape is not read */
 #define GSM_SELECT_BOX        1u
 #define GSM_SELECT_ELLIPSOID  2u
@@ -827,6 +827,87 @@ gsm_status gsm_global_select_where(gsm_renderer *renderer, void *stream, const g
 gsm_status gsm_global_state_bounds(gsm_renderer *renderer, void *stream, const gsm_gaussian_input *input,
                                    const gsm_global_state *state, const uint32_t keep[8],
                                    gsm_global_bounds *bounds /* device */);
+
+/* Moving a selection for good (no reference analogue): gsm_global_transform bakes a similarity -- a
+ * rotation R, a uniform scale s > 0 and a translation t -- into the records and the harmonics of the gaussians of a
+ * keep set, in place.  It is what a move-rotate-scale gizmo ends in; until then the same pose can be previewed as an
+ * object of gsm_global_render_composite, whose pose does not rescale the gaussians while this entry does.
+ *
+ * gsm_global_transform_from_pose (host only, no handle) derives the descriptor.  It refuses, with
+ * GSM_ERR_INVALID_ARGUMENT, a NULL pointer, a non-finite input, scale <= 0, and a rotation whose R R^T differs from
+ * the identity by more than 1e-4 in any entry or whose determinant is negative.  Otherwise it works in double,
+ * takes for R the rotation nearest to the nine floats (the orthogonal factor of their polar decomposition; an
+ * orthonormal input is kept bit for bit) and rounds every output once to fp32: matrix = s R | t; quaternion = the unit quaternion of R with w >= 0; scale = s;
+ * sh1, sh2, sh3 = the band matrices D_1, D_2, D_3 of R, D_l being the (2l+1) x (2l+1) matrix with
+ *     sum_k (D_l c)_k b_k(d) = sum_k c_k b_k(R^T d)   for every coefficient vector c of band l and unit direction d,
+ * b the renderer's own basis (the signs and constants of its SH evaluation).  D_l is solved once, without iteration,
+ * over 2l+1 fixed directions; the identity rotation gives identity matrices exactly.
+ *
+ * gsm_global_transform.  The state and the keep set are gsm_global_extract's: gaussian g < gaussian_count takes part
+ * when bit s_g of `keep` is set; {NULL, default_state} with a full set transforms the whole scene.  A gaussian that
+ * does not take part keeps every byte, and so does every byte at or past gaussian_count.  For one that takes part,
+ * every multiplication and addition below is one IEEE fp32 operation in exactly the written order, none fused; fp16
+ * fields are widened exactly and rounded back once, to nearest even.  With m = desc->matrix, a = desc->quaternion:
+ *   position   p'_r = ((m[r][0]*px + m[r][1]*py) + m[r][2]*pz) + m[r][3]   for each row r;
+ *   scales     s'_k = s_k * desc->scale;
+ *   rotation   (x, y, z, w), the Hamilton product a (x) q, not renormalised (the projection normalises):
+ *                x' = ((aw*x + ax*w) + ay*z) - az*y
+ *                y' = ((aw*y - ax*z) + ay*w) + az*x
+ *                z' = ((aw*z + ax*y) - ay*x) + az*w
+ *                w' = ((aw*w - ax*x) - ay*y) - az*z;
+ *   opacity, the pad words and the band-0 coefficients: unchanged, byte for byte;
+ *   harmonics  for each channel and each band l present (sh_components 4: band 1; 9: bands 1-2; 16: bands 1-3), with
+ *              c the band's 2l+1 coefficients in the planar row and D = desc->sh<l> (row-major):
+ *                c'_i = (...((D[i][0]*c_0 + D[i][1]*c_1) + D[i][2]*c_2)...) + D[i][2l]*c_2l.
+ * With sh_components 0 or 1, harmonics is neither read nor written and may be NULL.  The descriptor is applied as
+ * given: a caller who fills one by hand gets that arithmetic.  The fp16 row of 16 components is read and written as
+ * six 16-byte accesses, as the projection reads it, so that harmonics pointer must be 16-byte aligned; every other
+ * row needs its element's alignment and goes as 16-byte accesses where its address allows.
+ *
+ * The structs and `keep` are host memory, consumed before the call returns; what the scene points to is device
+ * memory.  Enqueue-only on `stream`, capturable, nothing is allocated.  A captured call replays the descriptor, the
+ * keep set and the pointers it was captured with and reads the state bytes of the replay; every replay applies the
+ * transform again, on top of the last.  It neither reads nor changes the handle's last-frame or last-pick state.
+ *
+ * Checks, all before anything is enqueued; the first failing row in this order decides:
+ *   GSM_ERR_INVALID_ARGUMENT         renderer NULL;
+ *   GSM_ERR_INVALID_GAUSSIAN_COUNT   gaussian_count > max_gaussians (the count of a NULL scene cannot be read: that
+ *                                    call falls to the next row);
+ *   GSM_ERR_MISSING_REQUIRED_BUFFER  scene, state, keep or desc NULL; with a count > 0: scene->gaussians NULL, or
+ *                                    scene->harmonics NULL while sh_components > 1;
+ *   GSM_ERR_INVALID_BUFFER_SIZE      scene->gaussians not 16-byte aligned; with sh_components > 1, scene->harmonics
+ *                                    not aligned to its element (2 or 4 bytes; 16 bytes for fp16 rows of 16);
+ *   GSM_ERR_INVALID_ARGUMENT         default_state > 255; sh_components not in {0, 1, 4, 9, 16}; a non-finite entry
+ *                                    of the descriptor; desc->scale <= 0; the records' and the harmonics' byte ranges
+ *                                    meeting.
+ * A count of 0 is a no-op.
+ *
+ * Out of scope: a non-uniform scale or a shear (the record cannot hold the result), transforms out of place, merging
+ * scenes, a centroid, and the DepthFirst, Local and multi-GPU renderers. */
+typedef struct {            /* the mutable twin of gsm_gaussian_input */
+    void *gaussians;
+    void *harmonics;
+    uint32_t gaussian_count;
+    uint32_t sh_components;
+} gsm_global_scene;
+typedef struct {
+    float matrix[12];       /* row-major 3x4: s*R | t, scene space -> scene space */
+    float quaternion[4];    /* x, y, z, w of R, unit */
+    float scale;            /* s > 0 */
+    float sh1[9], sh2[25], sh3[49];  /* row-major band matrices D_1, D_2, D_3 of R */
+} gsm_global_transform_desc;
+#ifdef __cplusplus
+static_assert(sizeof(gsm_global_scene) == 24, "gsm_global_scene is 24 bytes");
+static_assert(sizeof(gsm_global_transform_desc) == 400, "gsm_global_transform_desc is 400 bytes");
+#else
+_Static_assert(sizeof(gsm_global_scene) == 24, "gsm_global_scene is 24 bytes");
+_Static_assert(sizeof(gsm_global_transform_desc) == 400, "gsm_global_transform_desc is 400 bytes");
+#endif
+gsm_status gsm_global_transform_from_pose(const float rotation[9] /* row-major */, float scale,
+                                          const float translation[3], gsm_global_transform_desc *out);
+gsm_status gsm_global_transform(gsm_renderer *renderer, void *stream, const gsm_global_scene *scene,
+                                const gsm_global_state *state, const uint32_t keep[8],
+                                const gsm_global_transform_desc *desc);
 
 /* GlobalRenderer.renderStereo (GlobalRenderer.swift:240-255) calls fatalError for
  * every target; this entry returns GSM_ERR_UNSUPPORTED instead. */
