@@ -33,7 +33,7 @@ class FrameSorter {
                 M.alloc(st, f->half_[i], (size_t)capacity * 4);
             }
             M.alloc(st, f->count_, 4);
-            f->histBytes_ = radix_workspace_bytes(capacity);
+            f->histBytes_ = sort_workspace_bytes(capacity);
             M.alloc(st, f->hist_, f->histBytes_);
             M.alloc(st, f->binTotals_, kSortTotalsWords * sizeof(uint32_t));
             M.alloc(st, f->buckets_, ((size_t)kWideBins + 1) * sizeof(uint32_t));
@@ -68,14 +68,15 @@ class FrameSorter {
         hipMemcpyAsync(count_, &hostCount_, 4, hipMemcpyHostToDevice, s);
         const SortSpace ws{hist_, histBytes_, binTotals_, kSortTotalsWords};
         const bool ballot = tuning_.ballotRank;
-        // GlobalRenderer::runFrame (shift 16) and DepthFirstRenderer::sortTiles (shift 0)
-        const int res = d.all_tiles > kFrameSortMaxTiles16
-                            ? radix_sort_tiles_wide(keys_, vals_, count_, capacity_, ws, tileStart_, buckets_, d.all_tiles, s,
-                                                    ballot)
-                            : radix_sort_tiles(keys_, vals_, count_, capacity_, d.shift, ws, tileStart_, 0u, d.num_tiles,
-                                               d.all_tiles, s, ballot, tuning_.wideSort, tuning_.sortScanless);
+        // GlobalRenderer::runFrame (shift 16) and DepthFirstRenderer::sortTiles (shift 0): radix_sort_tiles_wide's
+        // plan and radix_sort_tiles', whose kind is the plan reported
+        const SortPlan plan = d.all_tiles > kFrameSortMaxTiles16
+                                  ? plan_sort_tiles_wide(capacity_, d.all_tiles)
+                                  : plan_sort_tiles(capacity_, d.shift, 0u, d.num_tiles, d.all_tiles, tuning_.wideSort,
+                                                    tuning_.sortScanless);
+        const int res = run_sort_plan(plan, keys_, vals_, count_, ws, tileStart_, buckets_, s, ballot);
         if (res == kSortNoSpace) return GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;  // (nothing of the sort launched)
-        out->plan = frame_sort_plan(d.all_tiles, res);
+        out->plan = plan.kind;
         int sorted = res;
         if (d.depth_sort) {
             // k_tile_sort indexes the runs by the starts: they are checked here first (a renderer does not look)
@@ -492,7 +493,7 @@ gsm_status gsm_global_set_tile_rows(gsm_renderer* r, uint32_t b, uint32_t e) {
     return r->impl->setTileRows(b, e);
 }
 
-size_t gsm_debug_sort_workspace_bytes(uint32_t capacity) { return gsm::radix_workspace_bytes(capacity); }
+size_t gsm_debug_sort_workspace_bytes(uint32_t capacity) { return gsm::sort_workspace_bytes(capacity); }
 
 gsm_status gsm_debug_sort_plan_fits(uint32_t capacity, uint32_t key_bits, int wide, size_t hist_bytes) {
     if (key_bits == 0 || key_bits > 32) return GSM_ERR_INVALID_ARGUMENT;
@@ -509,20 +510,20 @@ gsm_status gsm_sort_pairs_u32(void* keys, void* values, uint32_t n, uint32_t key
     uint32_t *k2 = nullptr, *v2 = nullptr, *hist = nullptr, *bins = nullptr, *np = nullptr;
     gsm_status st = GSM_OK;
     if (hipMalloc(&k2, (size_t)n * 4) != hipSuccess || hipMalloc(&v2, (size_t)n * 4) != hipSuccess ||
-        hipMalloc(&hist, gsm::radix_workspace_bytes(n)) != hipSuccess || hipMalloc(&bins, 256 * 4) != hipSuccess ||
+        hipMalloc(&hist, gsm::sort_workspace_bytes(n)) != hipSuccess || hipMalloc(&bins, 256 * 4) != hipSuccess ||
         hipMalloc(&np, 4) != hipSuccess) {
         st = GSM_ERR_FAILED_TO_ALLOCATE_BUFFER;
     }
     if (st == GSM_OK) {
         hipMemcpyAsync(np, &n, 4, hipMemcpyHostToDevice, s);
-        hipMemsetAsync(hist, 0, gsm::radix_workspace_bytes(n), s);
+        hipMemsetAsync(hist, 0, gsm::sort_workspace_bytes(n), s);
         uint32_t* kb[2] = {(uint32_t*)keys, k2};
         uint32_t* vb[2] = {(uint32_t*)values, v2};
         const int digits = (int)((key_bits + 7) / 8);
         int dev = 0;
         hipGetDevice(&dev);
         const gsm::Tuning tn = gsm::tuning_from_env(dev);  // read per call: no renderer here
-        const gsm::SortSpace ws{hist, gsm::radix_workspace_bytes(n), bins, 256};
+        const gsm::SortSpace ws{hist, gsm::sort_workspace_bytes(n), bins, 256};
         int res = gsm::radix_sort_pairs(kb, vb, np, n, 0, digits, ws, s, tn.ballotRank, tn.sortScanless);
         if (res == gsm::kSortNoSpace) st = GSM_ERR_INVALID_ASSIGNMENT_CAPACITY;
         if (res == 1) {

@@ -86,7 +86,7 @@ gsm_status DepthFirstRenderer::create(const gsm_renderer_config& cfg, int hipDev
     const uint32_t maxW = cfg.max_width ? cfg.max_width : 1u, maxH = cfg.max_height ? cfg.max_height : 1u;
     const uint64_t tiles = (uint64_t)((maxW + kDfTile - 1) / kDfTile) * ((maxH + kDfTile - 1) / kDfTile);
     const bool tile32 = opt.tile_id_bits == 32u;
-    // 16-bit tile ids (DepthFirstResources.swift); 32-bit: the tile sort's two passes (radix_sort_tiles_wide)
+    // 16-bit tile ids (DepthFirstResources.swift); 32-bit: the tile sort's two passes (plan_sort_tiles_wide)
     static_assert((1u << kTilesWideMaxBits) == GSM_DF_MAX_TILES_32, "the header's limit is the tile sort's");
     if (tiles > (tile32 ? (uint64_t)GSM_DF_MAX_TILES_32 : 65535u)) return GSM_ERR_INVALID_TILE_COUNT;
     // tile rects are short4 (DfArena::bounds): a 32-bit grid may not exceed GSM_DF_MAX_TILES_AXIS per axis
@@ -129,7 +129,7 @@ gsm_status DepthFirstRenderer::create(const gsm_renderer_config& cfg, int hipDev
         M.alloc(st, A.ikeys[i], cap * 4);
         M.alloc(st, A.ivals[i], cap * 4);
     }
-    A.radixHistBytes = radix_workspace_bytes(r->maxInstances_ > r->maxGaussians_ ? r->maxInstances_ : r->maxGaussians_);
+    A.radixHistBytes = sort_workspace_bytes(r->maxInstances_ > r->maxGaussians_ ? r->maxInstances_ : r->maxGaussians_);
     M.alloc(st, A.radixHist, A.radixHistBytes);
     if (st == GSM_OK && hipMemset(A.radixHist, 0, A.radixHistBytes) != hipSuccess) st = GSM_ERR_FAILED_TO_ALLOCATE_BUFFER;
     M.alloc(st, A.radixBinTotals, kSortTotalsWords * 4);  // radix_sort_tiles: totals + block table
@@ -171,10 +171,10 @@ gsm_status DepthFirstRenderer::create(const gsm_renderer_config& cfg, int hipDev
     return GSM_OK;
 }
 
-// DepthRadixSortEncoder (DepthFirstRenderer.swift:664-681): stable LSD over the compacted keys.
-// 32-bit keys: 3 wide passes of 11/11/10 bits unless GSM_SORT_WIDE=0; 16-bit keys (depth_key_bits 16):
-// the low 16 bits in 2 passes of 8 bits (DepthRadixSortEncoder.swift:13-24) -- the same stable order
-// with either switch.  Returns the ping-pong index of the result (or kSortNoSpace: nothing launched).
+// DepthRadixSortEncoder (DepthFirstRenderer.swift:664-681): stable LSD over the compacted keys, all 32
+// bits or (depth_key_bits 16, DepthRadixSortEncoder.swift:13-24) the low 16.  The passes: plan_sort_bits
+// (gsm_sort_plan.h) -- the same stable order with either switch.  Returns the ping-pong index of the
+// result (or kSortNoSpace: nothing launched).
 int DepthFirstRenderer::sortDepth(hipStream_t s) {
     return radix_sort_bits(A_.dkeys, A_.dvals, &A_.visHdr->totalAssignments, maxGaussians_, 0, key16_ ? 16u : 32u,
                            sort_space(A_), s, tuning_.ballotRank, tuning_.wideSort, tuning_.sortScanless);
@@ -182,8 +182,8 @@ int DepthFirstRenderer::sortDepth(hipStream_t s) {
 
 // TileSortEncoder (DepthFirstRenderer.swift:683-768): stable sort by the tile id; the last pass also
 // writes the tile ranges' starts (no pass over the instances).  A frame of more than 65,536 tiles (only
-// with tile_id_bits 32) takes the two passes of radix_sort_tiles_wide; every other frame, in either
-// mode, the 16-bit field's passes.
+// with tile_id_bits 32) takes plan_sort_tiles_wide; every other frame, in either mode, plan_sort_tiles
+// (gsm_sort_plan.h).
 int DepthFirstRenderer::sortTiles(const DfArgs& a, hipStream_t s) {
     if (a.tileCount > 65536u)
         return radix_sort_tiles_wide(A_.ikeys, A_.ivals, &A_.instHdr->totalAssignments, maxInstances_, sort_space(A_),

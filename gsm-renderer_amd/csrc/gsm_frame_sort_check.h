@@ -1,5 +1,6 @@
-// gsm_frame_sort_check.h -- the host checks of gsm_debug_frame_sort_create / _run, the plan a run
-// reports and the guard on the tile starts between the tile passes and the depth sort.  Plain C++17 over
+// gsm_frame_sort_check.h -- the host checks of gsm_debug_frame_sort_create / _run and the guard on
+// the tile starts between the tile passes and the depth sort (the plan a run reports: SortPlan::kind,
+// gsm_sort_plan.h).  Plain C++17 over
 // include/gsm_debug.h alone: no HIP, so a stand-alone CPU program (tests/host/frame_sort_check_test.cpp) runs every
 // row without a device.
 #pragma once
@@ -37,15 +38,6 @@ inline gsm_status frame_sort_run_check(uint32_t capacity, uint32_t maxTiles, con
         return GSM_ERR_INVALID_ARGUMENT;
     if (desc->shift == 16u && desc->all_tiles > kFrameSortMaxTiles16) return GSM_ERR_INVALID_ARGUMENT;
     return GSM_OK;
-}
-
-// The plan behind a finished sort: `result` is the ping-pong index radix_sort_tiles / radix_sort_tiles_wide
-// returned -- 1 after one pass, 0 after two -- so the report follows what ran, not a second copy of the rule; a
-// single pass over a field of more than 8 bits can only be the wide one.
-inline uint32_t frame_sort_plan(uint32_t allTiles, int result) {
-    if (allTiles > kFrameSortMaxTiles16) return GSM_FRAME_SORT_WIDE_THEN_NARROW;
-    if (result == 0) return GSM_FRAME_SORT_TWO_NARROW;
-    return allTiles > 256u ? GSM_FRAME_SORT_ONE_WIDE : GSM_FRAME_SORT_ONE_NARROW;
 }
 
 // The tile starts as k_tile_sort needs them before it may run on them: non-decreasing over [0, numTiles] and at

@@ -7,6 +7,7 @@
 
 #include "gsm_blend_plan.h"
 #include "gsm_host.h"
+#include "gsm_sort_plan.h"
 #include "gsm_types.h"
 
 namespace gsm {
@@ -332,17 +333,18 @@ __device__ __forceinline__ void st_sys128_at(void* base, uint32_t bytes, uint32_
     __builtin_amdgcn_raw_buffer_store_b128(w, sys_rsrc(base, bytes), (int)off, 0, kSysCoherent);
 }
 
-// A sort's device workspace and its sizes.  Every sort below plans its passes first and launches
-// nothing (returns kSortNoSpace) when one pass's per-block digit counts, super-group rows or digit
-// totals would not fit -- a knob or a grid rule changed without the allocation (the r05 wide-pass
-// A/B fault class); callers report GSM_ERR_INVALID_ASSIGNMENT_CAPACITY.
+// A sort's device workspace and its sizes.  Every sort below plans its passes first (gsm_sort_plan.h) and
+// launches nothing (returns kSortNoSpace) when the plan does not fit it (sort_plan_fits); callers report
+// GSM_ERR_INVALID_ASSIGNMENT_CAPACITY.
 struct SortSpace {
-    uint32_t* hist = nullptr;      // radix_workspace_bytes(capacity) bytes, zeroed once at allocation
+    uint32_t* hist = nullptr;      // sort_workspace_bytes(capacity) bytes, zeroed once at allocation
     size_t histBytes = 0;
     uint32_t* binTotals = nullptr;  // digit totals (+ the tile passes' bucket starts)
     size_t binWords = 0;
 };
-constexpr int kSortNoSpace = -1;
+inline bool sort_plan_fits(const SortPlan& plan, const SortSpace& ws, bool haveBuckets = true) {
+    return sort_plan_fits(plan, ws.histBytes, ws.binWords, ws.hist != nullptr, ws.binTotals != nullptr, haveBuckets);
+}
 
 // Device buffers of one renderer (the GlobalViewResources analogue, GlobalResources.swift:6-362).
 struct DeviceArena {
@@ -359,7 +361,7 @@ struct DeviceArena {
     uint32_t* valsKeep = nullptr;
     unsigned long long* blendTrace = nullptr;  // [4 * tiles * 4] (profiling bit 2 only)
     uint32_t* costMax = nullptr;               // [kCostMaxSlots] longest walk of the last blend
-    uint32_t* radixHist = nullptr;             // radix_workspace_bytes(maxAssignments) bytes
+    uint32_t* radixHist = nullptr;             // sort_workspace_bytes(maxAssignments) bytes
     size_t radixHistBytes = 0;
     uint32_t* radixBinTotals = nullptr;        // [kSortTotalsWords] (radix_sort_tiles)
     uint32_t* tileStart = nullptr;             // [tileCount + 1] first sorted entry of each tile
@@ -426,14 +428,6 @@ constexpr float kBlendZeroP = 34.65625f;
 constexpr int kProjectBlock = 256;
 // entries of the sincos table (one per quantised angle); the 256 byte-table entries follow (gsm_detmath.h)
 constexpr uint32_t kSincosEntries = 65536;
-constexpr int kRadixBlock = 256;
-constexpr int kRadixItems = 16;  // keys per thread per chunk (4096-key chunks)
-constexpr int kRadixChunk = kRadixBlock * kRadixItems;
-// wide radix digits (gsm_sort.hip): up to 11 bits, 2048 bins
-constexpr uint32_t kWideMaxBits = 11, kWideBins = 1u << kWideMaxBits;
-// radix_sort_tiles' workspace beside the histogram: two passes' digit totals + the bucket starts
-// (narrow passes, 768 words), or one wide pass's 2048 digit totals
-constexpr size_t kSortTotalsWords = kWideBins;
 inline SortSpace sort_space(const DeviceArena& A) { return SortSpace{A.radixHist, A.radixHistBytes, A.radixBinTotals, kSortTotalsWords}; }
 
 // project + cull + SH + tile count + per-block count sums (GlobalShaders.metal:19-123, 563-616): the projection
@@ -622,40 +616,37 @@ void launch_blend_walk(K kernel, const BlendPlan& plan, int threads, const Devic
                        last));
 }
 
-// Stable LSD radix sort of (key, value) pairs; n read from device memory *nPtr.
-// Returns the index (0/1) of the ping-pong buffer holding the result (or kSortNoSpace).
-// ballot: ranks from ballot matches (Tuning::ballotRank) instead of lane-ordered LDS atomics.
+// Stable LSD radix sorts of (key, value) pairs; n read from device memory *nPtr.  Each entry asks its planner of
+// gsm_sort_plan.h (plan_sort_pairs, _bits, _tiles, _tiles_wide: the passes, their digits and what each writes) and
+// runs the plan; it returns the index (0/1) of the ping-pong buffer holding the result, or kSortNoSpace with nothing
+// launched.  ballot: ranks from ballot matches (Tuning::ballotRank) instead of lane-ordered LDS atomics.
+// wide / scanless: Tuning::wideSort / sortScanless -- the same order either way.
 int radix_sort_pairs(uint32_t* keys[2], uint32_t* vals[2], const uint32_t* nPtr, uint32_t capacity,
                      int firstDigit, int numDigits, const SortSpace& ws,
                      hipStream_t stream, bool ballot, bool scanless = true);
-// Stable LSD radix sort by bits [shift, shift + bits) only, in ceil(bits / 8) passes of
-// near-equal digit widths (4..8 bits), or -- `wide` and where that saves a pass -- ceil(bits / 11)
-// passes of 9..11 bits.  binTotals: kSortTotalsWords words.  Returns the ping-pong index of the result.
 int radix_sort_bits(uint32_t* keys[2], uint32_t* vals[2], const uint32_t* nPtr, uint32_t capacity,
                     uint32_t shift, uint32_t bits, const SortSpace& ws, hipStream_t stream,
                     bool ballot, bool wide = false, bool scanless = true);
-// the frame sort's tile field (tiles [tileBase, tileBase + numTiles) of allTiles, bits <= 16) with
-// the tile starts written by its last pass (tileStart[0..allTiles], lower bounds for empty tiles);
-// one wide pass relative to tileBase when numTiles <= 2048 and `wide`; binTotals: kSortTotalsWords words
+// tileStart[0 .. allTiles] written by the last pass (lower bounds for empty tiles); binTotals: kSortTotalsWords words
 int radix_sort_tiles(uint32_t* keys[2], uint32_t* vals[2], const uint32_t* nPtr, uint32_t capacity, uint32_t shift,
                      const SortSpace& ws, uint32_t* tileStart, uint32_t tileBase, uint32_t numTiles,
                      uint32_t allTiles, hipStream_t stream, bool ballot, bool wide = true, bool scanless = true);
-// a tile field of 17 .. kTilesWideMaxBits bits (more than 65,536 tiles: DepthFirst tile_id_bits
-// 32) in two passes, the starts written by the last one as above; `buckets`: kWideBins + 1 words
+// `buckets`: kWideBins + 1 words
 int radix_sort_tiles_wide(uint32_t* keys[2], uint32_t* vals[2], const uint32_t* nPtr, uint32_t capacity,
                           const SortSpace& ws, uint32_t* tileStart, uint32_t* buckets, uint32_t allTiles,
                           hipStream_t stream, bool ballot);
-constexpr uint32_t kTilesWideMaxBits = kWideMaxBits + 8u;  // one wide pass + one 8-bit pass
-bool sort_tiles_wide_fits(uint32_t capacity, uint32_t allTiles, const SortSpace& ws);
-// the workspace footprint of one pass (words of `hist`, incl. the super-group rows in front), and
-// whether every pass radix_sort_bits plans fits `ws` (host only: no launch)
-size_t sort_pass_hist_words(bool wide, int bits, uint32_t grid);
-bool sort_bits_plan_fits(uint32_t capacity, uint32_t bits, bool wide, const SortSpace& ws);
-// scanless: narrow passes without the k_radix_scan launch (super-group digit rows, gsm_sort.hip;
-// Tuning::sortScanless) -- the same order either way
-uint32_t radix_grid_for_capacity(uint32_t capacity);
-// bytes of the sort workspace (`hist` argument above) for a capacity; zero it once at allocation
-size_t radix_workspace_bytes(uint32_t capacity);
+// The one launcher behind them: checks that the plan fits (or launches nothing: kSortNoSpace), then enqueues every
+// pass, keys[0] -> keys[1] -> keys[0] ...; returns plan.result.  tileStart / buckets: what the plan's passes write
+// (null where it has no such pass).
+int run_sort_plan(const SortPlan& plan, uint32_t* keys[2], uint32_t* vals[2], const uint32_t* nPtr, const SortSpace& ws,
+                  uint32_t* tileStart, uint32_t* buckets, hipStream_t stream, bool ballot);
+// whether the plans of radix_sort_tiles_wide / radix_sort_bits fit `ws` (host only: no launch)
+inline bool sort_tiles_wide_fits(uint32_t capacity, uint32_t allTiles, const SortSpace& ws) {
+    return sort_plan_fits(plan_sort_tiles_wide(capacity, allTiles), ws);
+}
+inline bool sort_bits_plan_fits(uint32_t capacity, uint32_t bits, bool wide, const SortSpace& ws) {
+    return sort_plan_fits(plan_sort_bits(capacity, 0u, bits, wide, false), ws);
+}
 // stable per-tile sort by the 16-bit depth key of runs already grouped by tile (one workgroup per
 // tile), which writes the blend's half-tile lists (as launch_half_lists) and, when `full`, the sorted
 // keys and values (keysOut / valsOut; the reference's sorted arrays, read back by captured frames)

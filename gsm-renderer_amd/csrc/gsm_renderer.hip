@@ -66,7 +66,7 @@ gsm_status GlobalRenderer::create(const gsm_renderer_config& cfg, int hipDevice,
     M.alloc(st, A.keys[1], cap * sizeof(uint32_t));
     M.alloc(st, A.vals[0], cap * sizeof(uint32_t));
     M.alloc(st, A.vals[1], cap * sizeof(uint32_t));
-    A.radixHistBytes = radix_workspace_bytes(r->maxAssignments_);
+    A.radixHistBytes = sort_workspace_bytes(r->maxAssignments_);
     M.alloc(st, A.radixHist, A.radixHistBytes);
     if (st == GSM_OK && hipMemset(A.radixHist, 0, A.radixHistBytes) != hipSuccess) st = GSM_ERR_FAILED_TO_ALLOCATE_BUFFER;
     M.alloc(st, A.radixBinTotals, kSortTotalsWords * sizeof(uint32_t));  // radix_sort_tiles: totals + block table

@@ -82,11 +82,7 @@ __device__ __forceinline__ uint32_t wave_rank(uint32_t* cnt, uint32_t d, bool va
 // call starts and ends with set 0 zero; calls of an odd number of narrow passes keep k_radix_scan.
 // (A ticket taken by the downsweep's last block to zero the rows costs more than the scan it replaces:
 // a single ticket serializes at ~36 ns an atomic, and an agent-scope fence per block writes back the
-// XCD's L2 -- +35 us a pass, measured.)
-constexpr uint32_t kSuperGroup = 32;
-constexpr uint32_t kSuperRows = 1024 / kSuperGroup;  // radix_grid_for_capacity caps the grid at 1024
-constexpr size_t kSuperSetWords = (size_t)kSuperRows * 256;
-constexpr size_t kSuperWords = 2 * kSuperSetWords;
+// XCD's L2 -- +35 us a pass, measured.)  kSuperGroup, kSuperRows and the sets' words: gsm_sort_plan.h.
 static_assert(kRadixBlock == 256 && kRadixBlock / 64 == 4, "the scanless base reduction assumes 4 waves");
 
 
@@ -430,11 +426,7 @@ __global__ __launch_bounds__(kRadixBlock) void k_radix_downsweep(
 }
 
 // ---------------------------------------------------------------------------
-// Wide passes take chunks of kWideChunk keys (kWideItems per thread; 8 measured slower): their per-chunk digit
-// bookkeeping is heavier, so their blocks are fewer per CU.
-constexpr int kWideItems = 16;
-constexpr int kWideChunk = kRadixBlock * kWideItems;
-static_assert(kWideItems % 4 == 0 && kWideItems <= kRadixItems, "wide chunks: 16-B loads, <= the narrow chunk");
+// Wide passes take chunks of kWideChunk keys (kWideItems per thread: gsm_sort_plan.h).
 __device__ __forceinline__ void block_range_w(uint32_t n, uint32_t grid, uint32_t b, uint32_t* begin, uint32_t* end) {
     uint32_t per = (n + grid - 1) / grid;
     per = (per + kWideChunk - 1) / kWideChunk * kWideChunk;
@@ -456,9 +448,6 @@ __device__ __forceinline__ void block_range_w(uint32_t n, uint32_t grid, uint32_
 // digit(k) = ((k >> shift) - base) & (2^BITS - 1): base = the slab's first tile (0 otherwise).
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t wide_pad(uint32_t d) { return d + (d >> 3); }
-// block-major count rows of 2^BITS words, padded by 256 B (rows of a power-of-two stride all start on
-// the same HBM channel group)
-constexpr uint32_t kWideRowPad = 64;
 
 template <int BITS>
 __global__ __launch_bounds__(kRadixBlock) void k_wide_upsweep(const uint32_t* __restrict__ keys,
@@ -712,267 +701,108 @@ __global__ __launch_bounds__(kRadixBlock) void k_wide_downsweep(
     }
 }
 
-static uint32_t wide_grid_for_capacity(uint32_t capacity) {
-    uint32_t g = (capacity + kWideChunk - 1) / kWideChunk;  // (<= 1024 rows: radix_workspace_bytes)
-    if (g > 1024) g = 1024;
-    if (g < 1) g = 1;
-    return g;
+// two run-time switches -> f(std::bool_constant, std::bool_constant)
+template <class F>
+static void dispatch_flags(bool a, bool b, F&& f) {
+    auto second = [&](auto A) { b ? f(A, std::true_type{}) : f(A, std::false_type{}); };
+    a ? second(std::true_type{}) : second(std::false_type{});
 }
 
-static void wide_pass(uint32_t* kin, uint32_t* vin, uint32_t* kout, uint32_t* vout, const uint32_t* nPtr,
-                      uint32_t grid, uint32_t shift, uint32_t base, int bits, uint32_t* hist, uint32_t* binTotals,
-                      hipStream_t s, bool ballot, bool starts, uint32_t* tileStart, uint32_t numTiles,
-                      uint32_t allTiles) {
-    hist += kSuperWords;  // (radix_workspace_bytes: the narrow passes' super-group rows come first)
-#define GSM_WIDE_DOWN(B, BAL, S)                                                                              \
-    hipLaunchKernelGGL((k_wide_downsweep<B, BAL, S>), dim3(grid), dim3(kRadixBlock), 0, s, kin, vin, kout, vout, \
-                       nPtr, shift, base, hist, binTotals, tileStart, numTiles, allTiles)
-#define GSM_WIDE_PASS(B)                                                                                         \
-    hipLaunchKernelGGL(k_wide_upsweep<B>, dim3(grid), dim3(kRadixBlock), 0, s, kin, nPtr, shift, base, hist);    \
-    hipLaunchKernelGGL(k_wide_scan<B>, dim3((1u << B) / kWideScanDigits), dim3(256), 0, s, hist, grid, nPtr, binTotals); \
-    if (ballot) {                                                                                                \
-        if (starts) GSM_WIDE_DOWN(B, true, true);                                                                \
-        else GSM_WIDE_DOWN(B, true, false);                                                                      \
-    } else {                                                                                                     \
-        if (starts) GSM_WIDE_DOWN(B, false, true);                                                               \
-        else GSM_WIDE_DOWN(B, false, false);                                                                     \
+// pass -> f(BITS, BALLOT, STARTS, BIGL) as integral constants: the template arguments of its kernels.  BIGL goes with
+// the 8-bit STARTS pass alone (FromBigBuckets), so no other width gets such an instance.
+template <class F>
+static void dispatch_sort_pass(const SortPass& p, bool ballot, F&& f) {
+    dispatch_flags(ballot, sort_writes_starts(p.starts), [&](auto BAL, auto ST) {
+        auto bits = [&](auto B) { f(B, BAL, ST, std::false_type{}); };
+        switch (p.bits) {
+            case 4: bits(std::integral_constant<int, 4>{}); break;
+            case 5: bits(std::integral_constant<int, 5>{}); break;
+            case 6: bits(std::integral_constant<int, 6>{}); break;
+            case 7: bits(std::integral_constant<int, 7>{}); break;
+            case 8:
+                if constexpr (decltype(ST)::value) {
+                    if (p.starts == SortStarts::FromBigBuckets) {
+                        f(std::integral_constant<int, 8>{}, BAL, ST, std::true_type{});
+                        break;
+                    }
+                }
+                bits(std::integral_constant<int, 8>{});
+                break;
+            case 9: bits(std::integral_constant<int, 9>{}); break;
+            case 10: bits(std::integral_constant<int, 10>{}); break;
+            default: bits(std::integral_constant<int, 11>{}); break;
+        }
+    });
+}
+
+// The one launcher of the sorts below (plan: gsm_sort_plan.h).  A narrow pass is upsweep, k_radix_scan unless
+// scanless, downsweep; a wide one upsweep, scan, downsweep.  `hist`: the super-group row sets, then the block counts.
+int run_sort_plan(const SortPlan& plan, uint32_t* keys[2], uint32_t* vals[2], const uint32_t* nPtr, const SortSpace& ws,
+                  uint32_t* tileStart, uint32_t* buckets, hipStream_t s, bool ballot) {
+    if (!sort_plan_fits(plan, ws, buckets != nullptr)) return kSortNoSpace;  // the plan fits, or no launch
+    uint32_t* const hist = ws.hist + kSuperWords;
+    for (uint32_t i = 0, cur = 0; i < plan.count; ++i, cur ^= 1u) {
+        const SortPass& p = plan.pass[i];
+        uint32_t *kin = keys[cur], *vin = vals[cur], *kout = keys[cur ^ 1u], *vout = vals[cur ^ 1u];
+        uint32_t* binTotals = ws.binTotals + p.totalsAt;
+        const dim3 grid(p.grid), block(kRadixBlock);
+        dispatch_sort_pass(p, ballot, [&](auto BITS, auto BAL, auto ST, auto BIGL) {
+            constexpr int kBits = decltype(BITS)::value;
+            constexpr bool kBallot = decltype(BAL)::value, kStarts = decltype(ST)::value;
+            if constexpr (kBits > 8) {
+                uint32_t* starts = p.starts == SortStarts::WideTiles     ? tileStart
+                                   : p.starts == SortStarts::WideBuckets ? buckets
+                                                                         : nullptr;
+                hipLaunchKernelGGL(k_wide_upsweep<kBits>, grid, block, 0, s, kin, nPtr, p.shift, p.base, hist);
+                hipLaunchKernelGGL(k_wide_scan<kBits>, dim3((1u << kBits) / kWideScanDigits), dim3(256), 0, s, hist,
+                                   p.grid, nPtr, binTotals);
+                hipLaunchKernelGGL((k_wide_downsweep<kBits, kBallot, kStarts>), grid, block, 0, s, kin, vin, kout, vout,
+                                   nPtr, p.shift, p.base, hist, binTotals, starts, p.numTiles, p.allTiles);
+            } else {
+                TileStarts ts{};
+                if (p.starts == SortStarts::FromBuckets) ts.bucketStart = ws.binTotals + kSortBucketsAt;
+                if (p.starts == SortStarts::FromBigBuckets) ts.bucketStart = buckets;
+                if (p.starts == SortStarts::BucketsOut) ts.bucketStartOut = ws.binTotals + kSortBucketsAt;
+                ts.lowBits = p.lowBits;
+                ts.numTiles = p.allTiles;
+                ts.tileStart = kStarts ? tileStart : nullptr;
+                // scanless: the pass's row set, and the other one for its upsweep to zero
+                uint32_t* super = p.superSet >= 0 ? ws.hist + (size_t)p.superSet * kSuperSetWords : nullptr;
+                uint32_t* superClear = p.superSet >= 0 ? ws.hist + (size_t)(p.superSet ^ 1) * kSuperSetWords : nullptr;
+                hipLaunchKernelGGL(k_radix_upsweep<kBits>, grid, block, 0, s, kin, nPtr, p.shift, hist, super, superClear);
+                if (!super) hipLaunchKernelGGL(k_radix_scan, dim3(1u << kBits), dim3(256), 0, s, hist, p.grid, binTotals);
+                hipLaunchKernelGGL((k_radix_downsweep<kBits, kBallot, kStarts, decltype(BIGL)::value>), grid, block,
+                                   p.ldsBytes, s, kin, vin, kout, vout, nPtr, p.shift, hist, binTotals, ts, super);
+            }
+        });
     }
-    switch (bits) {
-        case 9: GSM_WIDE_PASS(9); break;
-        case 10: GSM_WIDE_PASS(10); break;
-        default: GSM_WIDE_PASS(11); break;
-    }
-#undef GSM_WIDE_PASS
-#undef GSM_WIDE_DOWN
-}
-
-size_t sort_pass_hist_words(bool wide, int bits, uint32_t grid) {
-    // narrow: digit-major counts hist[d][block] (k_radix_upsweep / k_radix_scan); wide: block-major rows
-    // of 2^bits + kWideRowPad words (k_wide_upsweep); both behind the scanless super-group row sets
-    const size_t rows = wide ? ((size_t)1 << bits) + kWideRowPad : ((size_t)1 << bits);
-    return kSuperWords + rows * grid;
-}
-
-size_t radix_workspace_bytes(uint32_t capacity) {
-    // the scanless super-group row sets (zero at allocation; see kSuperGroup), then the per-block digit
-    // counts of the widest pass any sort of this capacity plans: 256 digits (narrow) or 2^kWideMaxBits
-    const size_t narrow = sort_pass_hist_words(false, 8, radix_grid_for_capacity(capacity));
-    const size_t wide = sort_pass_hist_words(true, (int)kWideMaxBits, wide_grid_for_capacity(capacity));
-    return std::max(narrow, wide) * sizeof(uint32_t);
-}
-
-// the passes' footprints against the workspace (nothing is launched for a plan that does not fit)
-static bool pass_fits(const SortSpace& ws, bool wide, int bits, uint32_t grid, size_t binWords) {
-    if (!ws.hist || !ws.binTotals) return false;
-    if (sort_pass_hist_words(wide, bits, grid) * sizeof(uint32_t) > ws.histBytes) return false;
-    // narrow passes read <= 1024 blocks' rows (k_radix_scan's column in registers, the super rows)
-    if (!wide && grid > kSuperRows * kSuperGroup) return false;
-    return binWords <= ws.binWords;
-}
-
-uint32_t radix_grid_for_capacity(uint32_t capacity) {
-    // <= 1024 blocks: k_radix_scan holds a digit's column in 4 registers per thread
-    uint32_t g = (capacity + kRadixChunk - 1) / kRadixChunk;
-    if (g > 1024) g = 1024;
-    if (g < 1) g = 1;
-    return g;
-}
-
-// one LSD pass; ts: a pass of radix_sort_tiles (its first writes the bucket starts, its last --
-// starts = true -- the tile starts)
-static void radix_pass(uint32_t* kin, uint32_t* vin, uint32_t* kout, uint32_t* vout, const uint32_t* nPtr,
-                       uint32_t grid, uint32_t shift, int bits, uint32_t* hist, uint32_t* binTotals,
-                       hipStream_t s, bool ballot, const TileStarts* ts = nullptr, bool starts = false,
-                       int superSet = -1) {
-    const TileStarts t = ts ? *ts : TileStarts{};
-    // scanless (superSet 0 or 1): the row sets sit in front of the block counts
-    uint32_t* super = superSet >= 0 ? hist + (size_t)superSet * kSuperSetWords : nullptr;
-    uint32_t* superClear = superSet >= 0 ? hist + (size_t)(superSet ^ 1) * kSuperSetWords : nullptr;
-    hist += kSuperWords;
-    // 1 KiB of dynamic LDS on the downsweeps without tile starts: > 40 KiB a block, 3 blocks per CU like
-    // the STARTS pass -- the first 4K tile pass at 4 blocks per CU measured 2.5 us slower (64.4-65.9
-    // against 62.2-62.4 us; 1080p unchanged; r06, profiles/r06_sort_occupancy_ab.txt)
-    const uint32_t ldsPad = starts ? 0u : 1024u;
-#define GSM_RADIX_PASS(B, S)                                                                                \
-    hipLaunchKernelGGL(k_radix_upsweep<B>, dim3(grid), dim3(kRadixBlock), 0, s, kin, nPtr, shift, hist, super, \
-                       superClear);                                                                         \
-    if (!super) hipLaunchKernelGGL(k_radix_scan, dim3(1u << B), dim3(256), 0, s, hist, grid, binTotals);  \
-    if (ballot)                                                                                             \
-        hipLaunchKernelGGL((k_radix_downsweep<B, true, S>), dim3(grid), dim3(kRadixBlock), ldsPad, s, kin, vin, kout, \
-                           vout, nPtr, shift, hist, binTotals, t, super);                                   \
-    else                                                                                                    \
-        hipLaunchKernelGGL((k_radix_downsweep<B, false, S>), dim3(grid), dim3(kRadixBlock), ldsPad, s, kin, vin, kout, \
-                           vout, nPtr, shift, hist, binTotals, t, super)
-#define GSM_RADIX_BITS(S)                    \
-    switch (bits) {                          \
-        case 4: GSM_RADIX_PASS(4, S); break; \
-        case 5: GSM_RADIX_PASS(5, S); break; \
-        case 6: GSM_RADIX_PASS(6, S); break; \
-        case 7: GSM_RADIX_PASS(7, S); break; \
-        default: GSM_RADIX_PASS(8, S); break; \
-    }
-    if (starts) {
-        GSM_RADIX_BITS(true)
-    } else {
-        GSM_RADIX_BITS(false)
-    }
-#undef GSM_RADIX_BITS
-#undef GSM_RADIX_PASS
+    return plan.result;
 }
 
 int radix_sort_pairs(uint32_t* keys[2], uint32_t* vals[2], const uint32_t* nPtr, uint32_t capacity,
-                     int firstDigit, int numDigits, const SortSpace& ws, hipStream_t s, bool ballot, bool scanlessOn) {
-    const uint32_t grid = radix_grid_for_capacity(capacity);
-    if (!pass_fits(ws, false, 8, grid, 256)) return kSortNoSpace;
-    int cur = 0;
-    const bool scanless = scanlessOn && numDigits % 2 == 0;
-    for (int dgt = firstDigit; dgt < firstDigit + numDigits; ++dgt) {
-        radix_pass(keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], nPtr, grid, (uint32_t)dgt * 8u, 8, ws.hist,
-                   ws.binTotals, s, ballot, nullptr, false, scanless ? (dgt - firstDigit) & 1 : -1);
-        cur ^= 1;
-    }
-    return cur;
-}
-
-bool sort_bits_plan_fits(uint32_t capacity, uint32_t bits, bool wide, const SortSpace& ws) {
-    const uint32_t grid = radix_grid_for_capacity(capacity), wgrid = wide_grid_for_capacity(capacity);
-    const uint32_t narrowPasses = (bits + 7) / 8, widePasses = (bits + kWideMaxBits - 1) / kWideMaxBits;
-    const bool useWide = wide && widePasses < narrowPasses;
-    const uint32_t passes = useWide ? widePasses : narrowPasses;
-    for (uint32_t p = 0, done = 0; p < passes; ++p) {
-        uint32_t b = (bits - done + (passes - p) - 1) / (passes - p);
-        b = useWide ? (b < 9 ? 9u : b) : (b < 4 ? 4u : b);
-        if (!pass_fits(ws, useWide, (int)b, useWide ? wgrid : grid, (size_t)1 << b)) return false;
-        done += b;
-    }
-    return true;
+                     int firstDigit, int numDigits, const SortSpace& ws, hipStream_t s, bool ballot, bool scanless) {
+    return run_sort_plan(plan_sort_pairs(capacity, firstDigit, numDigits, scanless), keys, vals, nPtr, ws, nullptr, nullptr,
+                         s, ballot);
 }
 
 int radix_sort_bits(uint32_t* keys[2], uint32_t* vals[2], const uint32_t* nPtr, uint32_t capacity,
                     uint32_t shift, uint32_t bits, const SortSpace& ws, hipStream_t s,
-                    bool ballot, bool wide, bool scanlessOn) {
-    const uint32_t grid = radix_grid_for_capacity(capacity), wgrid = wide_grid_for_capacity(capacity);
-    const uint32_t narrowPasses = (bits + 7) / 8;
-    const uint32_t widePasses = (bits + kWideMaxBits - 1) / kWideMaxBits;
-    // wide digits where they save a whole pass (32-bit keys: 3 passes of 11/11/10 bits instead of 4)
-    const bool useWide = wide && widePasses < narrowPasses;
-    const uint32_t passes = useWide ? widePasses : narrowPasses;
-    const bool scanless = !useWide && scanlessOn && passes % 2 == 0;
-    // near-equal digit widths; a digit wider than the bits left reads zero bits above the field
-    auto width = [&](uint32_t p, uint32_t done) {
-        const uint32_t b = (bits - done + (passes - p) - 1) / (passes - p);
-        return useWide ? (b < 9 ? 9u : b) : (b < 4 ? 4u : b);
-    };
-    if (!sort_bits_plan_fits(capacity, bits, wide, ws)) return kSortNoSpace;  // the plan fits, or no launch
-    int cur = 0;
-    uint32_t done = 0;
-    for (uint32_t p = 0; p < passes; ++p) {
-        const uint32_t b = width(p, done);
-        if (useWide)
-            wide_pass(keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], nPtr, wgrid, shift + done, 0u, (int)b, ws.hist,
-                      ws.binTotals, s, ballot, false, nullptr, 0u, 0u);
-        else
-            radix_pass(keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], nPtr, grid, shift + done, (int)b, ws.hist,
-                       ws.binTotals, s, ballot, nullptr, false, scanless ? (int)(p & 1u) : -1);
-        done += b;
-        cur ^= 1;
-    }
-    return cur;
+                    bool ballot, bool wide, bool scanless) {
+    return run_sort_plan(plan_sort_bits(capacity, shift, bits, wide, scanless), keys, vals, nPtr, ws, nullptr, nullptr, s,
+                         ballot);
 }
 
-// The frame sort's tile passes with the tile starts written by the last pass (TileStarts above).
-// The keys' tile field holds tiles [tileBase, tileBase + numTiles) of allTiles.  With <= 2048 tiles
-// in that range (a multi-GPU slab) and wide digits on, one wide pass sorts it, digits counted
-// from tileBase; otherwise radix_sort_bits' narrow passes over the whole tile field (bits <= 16:
-// one or two passes).  binTotals holds kSortTotalsWords words: the last pass's digit totals, the
-// first pass's at +256, its bucket starts at +512 (narrow); the wide pass's 2048 totals.
 int radix_sort_tiles(uint32_t* keys[2], uint32_t* vals[2], const uint32_t* nPtr, uint32_t capacity, uint32_t shift,
                      const SortSpace& ws, uint32_t* tileStart, uint32_t tileBase, uint32_t numTiles,
-                     uint32_t allTiles, hipStream_t s, bool ballot, bool wide, bool scanlessOn) {
-    const uint32_t grid = radix_grid_for_capacity(capacity);
-    auto bitsFor = [](uint32_t tiles) {
-        uint32_t b = 1;
-        while (b < 16 && ((tiles - 1u) >> b)) b++;
-        return b;
-    };
-    uint32_t bits = bitsFor(allTiles);
-    const uint32_t localBits = bitsFor(numTiles);
-    if (wide && bits > 8 && localBits <= kWideMaxBits) {
-        const uint32_t wb = localBits < 9 ? 9 : localBits, wgrid = wide_grid_for_capacity(capacity);
-        if (!pass_fits(ws, true, (int)wb, wgrid, (size_t)1 << wb)) return kSortNoSpace;
-        wide_pass(keys[0], vals[0], keys[1], vals[1], nPtr, wgrid, shift, tileBase, (int)wb, ws.hist, ws.binTotals, s,
-                  ballot, true, tileStart, numTiles, allTiles);
-        return 1;
-    }
-    TileStarts ts{};
-    ts.numTiles = allTiles;
-    ts.tileStart = tileStart;
-    if (bits <= 8) {  // one pass, one bucket
-        const int b = (int)(bits < 4 ? 4 : bits);
-        if (!pass_fits(ws, false, b, grid, 256)) return kSortNoSpace;
-        radix_pass(keys[0], vals[0], keys[1], vals[1], nPtr, grid, shift, b, ws.hist, ws.binTotals, s, ballot, &ts, true);
-        return 1;
-    }
-    // radix_sort_bits' digit widths (balanced: 6 + 8 / 8 + 6 at 4K and 5 + 7 / 7 + 5 at 1080p measured slower)
-    const uint32_t lo = (bits + 1u) / 2u;
-    const uint32_t hi = bits - lo < 4u ? 4u : bits - lo;  // (a digit wider than the bits left reads zeros)
-    // totals of the last pass at 0, the first pass's at +256, its bucket starts at +512 (<= 256 each)
-    if (!pass_fits(ws, false, (int)lo, grid, 768) || !pass_fits(ws, false, (int)hi, grid, 768)) return kSortNoSpace;
-    TileStarts first{};
-    first.bucketStartOut = ws.binTotals + 512;
-    const bool scanless = scanlessOn;
-    radix_pass(keys[0], vals[0], keys[1], vals[1], nPtr, grid, shift, (int)lo, ws.hist, ws.binTotals + 256, s, ballot,
-               &first, false, scanless ? 0 : -1);
-    ts.bucketStart = ws.binTotals + 512;
-    ts.lowBits = lo;
-    radix_pass(keys[1], vals[1], keys[0], vals[0], nPtr, grid, shift + lo, (int)hi, ws.hist, ws.binTotals, s, ballot,
-               &ts, true, scanless ? 1 : -1);
-    return 0;
+                     uint32_t allTiles, hipStream_t s, bool ballot, bool wide, bool scanless) {
+    return run_sort_plan(plan_sort_tiles(capacity, shift, tileBase, numTiles, allTiles, wide, scanless), keys, vals, nPtr,
+                         ws, tileStart, nullptr, s, ballot);
 }
 
-// The tile field of a grid above 65,536 tiles (DepthFirst tile_id_bits 32): 17..19 bits in two passes.
-// One wide pass over the low lo = bits - 8 bits (9..11) whose block 0 also writes its digits' global
-// bases -- the low-digit buckets' starts, as a STARTS pass "tile starts" of 2^lo tiles -- into
-// `buckets` (2^lo + 1 words), then one 8-bit pass over the high digit that writes the tile starts from
-// those buckets (TileStarts with up to 2048 buckets: k_radix_downsweep BIGL).  The plan does not depend
-// on `wide` / GSM_SORT_WIDE (three narrow passes could not write the starts); ballot ranks apply to both.
-// The reference sorts such a field in ceil(bits / 8) = 3 passes (TileSortEncoder.swift:60-62).
-static uint32_t tiles_wide_bits(uint32_t allTiles) {
-    uint32_t b = 17;
-    while (b < 32 && ((allTiles - 1u) >> b)) b++;
-    return b;
-}
-bool sort_tiles_wide_fits(uint32_t capacity, uint32_t allTiles, const SortSpace& ws) {
-    const uint32_t bits = tiles_wide_bits(allTiles);
-    if (bits > kTilesWideMaxBits) return false;
-    const uint32_t lo = bits - 8u;
-    return pass_fits(ws, true, (int)lo, wide_grid_for_capacity(capacity), (size_t)1 << lo) &&
-           pass_fits(ws, false, 8, radix_grid_for_capacity(capacity), 256);
-}
 int radix_sort_tiles_wide(uint32_t* keys[2], uint32_t* vals[2], const uint32_t* nPtr, uint32_t capacity,
                           const SortSpace& ws, uint32_t* tileStart, uint32_t* buckets, uint32_t allTiles,
                           hipStream_t s, bool ballot) {
-    if (!buckets || !sort_tiles_wide_fits(capacity, allTiles, ws)) return kSortNoSpace;
-    const uint32_t lo = tiles_wide_bits(allTiles) - 8u;
-    const uint32_t grid = radix_grid_for_capacity(capacity), wgrid = wide_grid_for_capacity(capacity);
-    wide_pass(keys[0], vals[0], keys[1], vals[1], nPtr, wgrid, 0u, 0u, (int)lo, ws.hist, ws.binTotals, s, ballot, true,
-              buckets, 1u << lo, 1u << lo);
-    TileStarts ts{};
-    ts.bucketStart = buckets;
-    ts.lowBits = lo;
-    ts.numTiles = allTiles;
-    ts.tileStart = tileStart;
-    uint32_t* hist = ws.hist + kSuperWords;
-    hipLaunchKernelGGL(k_radix_upsweep<8>, dim3(grid), dim3(kRadixBlock), 0, s, keys[1], nPtr, lo, hist,
-                       (uint32_t*)nullptr, (uint32_t*)nullptr);
-    hipLaunchKernelGGL(k_radix_scan, dim3(256), dim3(256), 0, s, hist, grid, ws.binTotals);
-    if (ballot)
-        hipLaunchKernelGGL((k_radix_downsweep<8, true, true, true>), dim3(grid), dim3(kRadixBlock), 0, s, keys[1], vals[1],
-                           keys[0], vals[0], nPtr, lo, hist, ws.binTotals, ts, (const uint32_t*)nullptr);
-    else
-        hipLaunchKernelGGL((k_radix_downsweep<8, false, true, true>), dim3(grid), dim3(kRadixBlock), 0, s, keys[1], vals[1],
-                           keys[0], vals[0], nPtr, lo, hist, ws.binTotals, ts, (const uint32_t*)nullptr);
-    return 0;
+    return run_sort_plan(plan_sort_tiles_wide(capacity, allTiles), keys, vals, nPtr, ws, tileStart, buckets, s, ballot);
 }
 
 }  // namespace gsm
@@ -1285,17 +1115,10 @@ void tile_depth_sort(uint32_t* keysIn, uint32_t* valsIn, uint32_t* keysOut, uint
                      bool full, int numCUs) {
     if (numTiles == 0) return;
     (void)numCUs;
-#define GSM_TILE_SORT(B, F)                                                                                  \
-    hipLaunchKernelGGL((k_tile_sort<B, F>), dim3(numTiles), dim3(kTsThreads), 0, s, keysIn, valsIn, keysOut, \
-                       valsOut, tileStart, tileBegin, half0, half1, halfCount, tileCount)
-    if (ballot) {
-        if (full) GSM_TILE_SORT(true, true);
-        else GSM_TILE_SORT(true, false);
-    } else {
-        if (full) GSM_TILE_SORT(false, true);
-        else GSM_TILE_SORT(false, false);
-    }
-#undef GSM_TILE_SORT
+    dispatch_flags(ballot, full, [&](auto BAL, auto FULL) {
+        hipLaunchKernelGGL((k_tile_sort<decltype(BAL)::value, decltype(FULL)::value>), dim3(numTiles), dim3(kTsThreads), 0,
+                           s, keysIn, valsIn, keysOut, valsOut, tileStart, tileBegin, half0, half1, halfCount, tileCount);
+    });
 }
 
 // ---------------------------------------------------------------------------

@@ -1,7 +1,7 @@
-// The host checks of gsm_debug_frame_sort_create / _run, the plan a run reports and the guard on the tile starts
+// The host checks of gsm_debug_frame_sort_create / _run and the guard on the tile starts
 // (gsm-renderer_amd/csrc/gsm_frame_sort_check.h) on the CPU: every row of both check tables, the order of the rows by
-// giving two faults at once, the plan for every tile count at a pass boundary, and the guard on real arrays (so the
-// sanitizers see its reads).  A stand-alone program over that header alone (no HIP, no device): the device pointers
+// giving two faults at once, and the guard on real arrays (so the sanitizers see its reads).  The plan a run reports
+// for every tile count at a pass boundary: tests/host/sort_plan_test.cpp, on the planners' output.  A stand-alone program over that header alone (no HIP, no device): the device pointers
 // are made-up addresses that nothing dereferences.  tests/test_frame_sort.py builds it with
 // -fsanitize=address,undefined and runs it.
 #include <cstdio>
@@ -129,19 +129,6 @@ static void test_run_order() {
     EXPECT(c.run() == GSM_ERR_INVALID_BUFFER_SIZE);
 }
 
-static void test_plan() {
-    using gsm::frame_sort_plan;
-    const uint32_t one[] = {1, 2, 16, 17, 33, 65, 129, 256};
-    for (uint32_t t : one) EXPECT(frame_sort_plan(t, 1) == GSM_FRAME_SORT_ONE_NARROW);
-    const uint32_t mid[] = {257, 300, 1000, 2048, 2049, 16200, 65536};
-    for (uint32_t t : mid) {
-        EXPECT(frame_sort_plan(t, 1) == GSM_FRAME_SORT_ONE_WIDE);
-        EXPECT(frame_sort_plan(t, 0) == GSM_FRAME_SORT_TWO_NARROW);
-    }
-    const uint32_t big[] = {65537, 65792, 131072, 262144, 524288};
-    for (uint32_t t : big) EXPECT(frame_sort_plan(t, 0) == GSM_FRAME_SORT_WIDE_THEN_NARROW);
-}
-
 static void test_starts_guard() {
     using gsm::frame_sort_starts_in_range;
     EXPECT(!frame_sort_starts_in_range(nullptr, 1, 0));
@@ -169,7 +156,6 @@ int main() {
     test_create_rows();
     test_run_rows();
     test_run_order();
-    test_plan();
     test_starts_guard();
     if (failures) {
         std::printf("%d checks failed\n", failures);

@@ -302,7 +302,7 @@ def test_entries_are_declared_exported_and_bound(gsm):
     assert callable(gsm.FrameSort.run) and callable(gsm.FrameSort.close)
     assert [int(x) for x in gsm.FrameSortPlan] == [ONE_NARROW, TWO_NARROW, ONE_WIDE, WIDE_THEN_NARROW]
     assert (R.HALF_SKIP_SHIFT, R.CHUNK, R.SUPER_GROUP, R.TILE_SORT_CAP) == (30, 4096, 32, 2048)
-    internal = open(os.path.join(CSRC, "gsm_internal.h")).read() + open(os.path.join(CSRC, "gsm_sort.hip")).read()
+    internal = "".join(open(os.path.join(CSRC, f)).read() for f in ("gsm_internal.h", "gsm_sort.hip", "gsm_sort_plan.h"))
     assert re.search(r"kHalfSkipShift = 30;", internal) and re.search(r"kSuperGroup = 32;", internal)
 
 
