@@ -32,6 +32,16 @@ constexpr int kBlendPerViewExtras = kBlendWide | kBlendPick8 | kBlendOcc8;
 constexpr bool blend_aligned(uintptr_t p, size_t pitch, size_t n, size_t stride = 0) {
     return (((size_t)p | pitch | stride) & (n - 1)) == 0;
 }
+// What that rule grants a frame's targets, for plan_blend and for each view of a batch (gsm_frame_plan.h).  0 stands
+// for a target the frame does not have.  The wide stores: 16-B colour, and depth pairs where there is depth.
+constexpr bool blend_wide(uintptr_t color, size_t colorPitch, uintptr_t depth, size_t depthPitch, size_t colorStride = 0,
+                          size_t depthStride = 0) {
+    return blend_aligned(color, colorPitch, 16, colorStride) && (!depth || blend_aligned(depth, depthPitch, 8, depthStride));
+}
+constexpr int blend_pick8(uintptr_t pick, size_t pitch) { return (pick && blend_aligned(pick, pitch, 8)) ? kBlendPick8 : 0; }
+constexpr int blend_occ8(uintptr_t occluder, size_t pitch) {
+    return (occluder && blend_aligned(occluder, pitch, 8)) ? kBlendOcc8 : 0;
+}
 
 // quadrant units (P = 1) up to this many tiles per CU, half tiles beyond
 constexpr uint32_t kBlendP1TilesPerCu = 8;
@@ -119,14 +129,13 @@ inline BlendPlan plan_blend(const BlendShape& s) {
     const bool strides = s.kind == FrameKind::Views && s.views > 1;
     const size_t colorStride = strides ? s.colorViewStride : 0, depthStride = strides ? s.depthViewStride : 0;
     const bool color16 = blend_aligned(s.color, s.colorPitch, 16, colorStride);
-    const bool wide = color16 && (!s.depth || blend_aligned(s.depth, s.depthPitch, 8, depthStride));
+    const bool wide = blend_wide(s.color, s.colorPitch, s.depth, s.depthPitch, colorStride, depthStride);
     const int shared = kBlendAgePrio | (s.costOrder ? kBlendCostSplit : 0);
     const int format = (s.colorFormat & kBlendFormatMask) << kBlendFormatShift;
     const int flags = (wide ? kBlendWide : 0) | shared | format | ((s.claim & kBlendClaimMask) << kBlendClaimShift) |
                       (s.arrive ? kBlendArrive : 0) |
                       ((s.depth && blend_aligned(s.depth, s.depthPitch, 16)) ? kBlendDepth16 : 0);
-    const int pick8 = (s.pick && blend_aligned(s.pick, s.pickPitch, 8)) ? kBlendPick8 : 0;
-    const int occ8 = (s.occluder && blend_aligned(s.occluder, s.occluderPitch, 8)) ? kBlendOcc8 : 0;
+    const int pick8 = blend_pick8(s.pick, s.pickPitch), occ8 = blend_occ8(s.occluder, s.occluderPitch);
     BlendPlan p;
     p.P = blend_pairs_per_lane(s.numTiles, s.numCUs);
     p.waves = s.waves ? s.waves : blend_waves_per_wg(s.numTiles, s.numCUs);

@@ -11,15 +11,13 @@
 #include <vector>
 
 #include "../../include/gsm_renderer.h"
+#include "gsm_frame_plan.h"
 
 namespace gsm {
 
 // ---- config ----
 // the guards every renderer's init shares (GlobalRenderer.swift:111-113)
 gsm_status check_config(const gsm_renderer_config& cfg);
-inline uint32_t color_bytes_per_pixel(uint32_t format) {
-    return format == GSM_COLOR_FORMAT_RGBA16F ? 8u : (format == GSM_COLOR_FORMAT_RGBA32F ? 16u : 4u);
-}
 // SH_DEGREE selection (GlobalProjectCullEncoder.swift:19-26)
 inline uint32_t sh_degree(uint32_t components) {
     return components <= 1 ? 0u : (components <= 4 ? 1u : (components <= 9 ? 2u : 3u));
@@ -99,25 +97,7 @@ class StageTimer {
 };
 
 // ---- frame ----
-// What a frame call refuses, in this precedence: count, dimensions, missing buffer, buffer size.
-// widthFactor: frames a row of the colour target holds (2: side by side).  depth may be null.
-// pick (nullable): a pick frame's third target (one uint32_t per pixel, required like colour); it joins the
-// missing-buffer row and the buffer-size row.
-struct PickTarget {
-    void* pixels;
-    size_t pitch;
-};
-// occluder (nullable): an occluded frame's depth image (one float per pixel, read only, required like colour); it
-// joins the same two rows.
-struct OccluderSource {
-    const void* pixels;
-    size_t pitch;
-};
-gsm_status validate_frame(const gsm_renderer_config& cfg, uint32_t maxGaussians, uint32_t maxWidth,
-                          uint32_t maxHeight, uint32_t count, bool allowEmpty, bool inputMissing, uint32_t width,
-                          uint32_t height, const void* color, size_t colorPitch, uint32_t widthFactor,
-                          const void* depth, size_t depthPitch, const PickTarget* pick = nullptr,
-                          const OccluderSource* occluder = nullptr);
+// validate_frame, PickTarget, OccluderSource and color_bytes_per_pixel: gsm_frame_plan.h (plain C++, tested on the CPU)
 
 // The per-frame terms of projectCovariance2D (GaussianShared.h:340-355), the same fp32 operations
 // in the same order as the reference repeats per gaussian: part of the numeric contract.

@@ -99,32 +99,6 @@ gsm_status StageTimer::lastGpuTime(double* seconds) {
     return GSM_OK;
 }
 
-gsm_status validate_frame(const gsm_renderer_config& cfg, uint32_t maxGaussians, uint32_t maxWidth,
-                          uint32_t maxHeight, uint32_t count, bool allowEmpty, bool inputMissing, uint32_t width,
-                          uint32_t height, const void* color, size_t colorPitch, uint32_t widthFactor,
-                          const void* depth, size_t depthPitch, const PickTarget* pick,
-                          const OccluderSource* occluder) {
-    // validateLimits (GlobalRenderer.swift:372-376) -- errors instead of a silent skip
-    if (count > maxGaussians || (count == 0 && !allowEmpty)) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
-    if (width == 0 || height == 0 || width > maxWidth || height > maxHeight) return GSM_ERR_INVALID_DIMENSIONS;
-    if (!color || (pick && !pick->pixels) || (occluder && !occluder->pixels) || (count > 0 && inputMissing))
-        return GSM_ERR_MISSING_REQUIRED_BUFFER;
-    if (colorPitch < (size_t)widthFactor * width * color_bytes_per_pixel(cfg.color_format))
-        return GSM_ERR_INVALID_BUFFER_SIZE;
-    // the blend stores at least 4-byte words of colour and 2-byte depth values
-    if ((((uintptr_t)color) & 3u) || (colorPitch & 3u)) return GSM_ERR_INVALID_BUFFER_SIZE;
-    if (depth && (depthPitch < (size_t)width * 2 || (depthPitch & 1u) || (((uintptr_t)depth) & 1u)))
-        return GSM_ERR_INVALID_BUFFER_SIZE;
-    // the blend stores 4-byte words of pick
-    if (pick && (pick->pitch < (size_t)width * 4 || (pick->pitch & 3u) || (((uintptr_t)pick->pixels) & 3u)))
-        return GSM_ERR_INVALID_BUFFER_SIZE;
-    // the blend loads 4-byte words of the occluder
-    if (occluder && (occluder->pitch < (size_t)width * 4 || (occluder->pitch & 3u) ||
-                     (((uintptr_t)occluder->pixels) & 3u)))
-        return GSM_ERR_INVALID_BUFFER_SIZE;
-    return GSM_OK;
-}
-
 ProjectionUniforms projection_uniforms(const float proj[16], float width, float height, float nearPlane,
                                        float farPlane) {
     ProjectionUniforms u;

@@ -6,6 +6,7 @@
 #include <tuple>
 
 #include "gsm_blend_plan.h"
+#include "gsm_frame_plan.h"
 #include "gsm_host.h"
 #include "gsm_sort_plan.h"
 #include "gsm_types.h"
@@ -172,19 +173,11 @@ struct FramePayload {
     const BatchFrame* batch() const { return kind == FrameKind::Batch ? &batchFrame : nullptr; }
     const ComposeFrame* compose() const { return kind == FrameKind::Compose ? &composeFrame : nullptr; }
 };
-// the colour and depth targets of a frame (depth nullable; a Views frame's are view 0's, a Batch's are per view)
-struct FrameTargets {
-    void* color = nullptr;
-    size_t colorPitch = 0;
-    void* depth = nullptr;
-    size_t depthPitch = 0;
-};
-
 // Per-gaussian styles (gsm_global_render_styled): the device table holds 256 packed styles --
 // word x: tint r | g << 8 | b << 16 | tint_amount << 24, word y: opacity_scale | hidden << 8 -- padded with the
 // identity past the caller's style_count, so a state byte indexes it without a bound.  It is filled by kernel
 // arguments (k_fill_styles): the host array is consumed at the call, a captured frame replays its table.
-constexpr uint32_t kStyleEntries = 256;
+// (kStyleEntries: gsm_frame_plan.h)
 constexpr uint32_t kStyleIdentityY = 255u;  // (x: 0 -- tint_amount 0; y: opacity_scale 255, not hidden)
 struct StyleChunk {
     uint2 v[kStyleEntries];
@@ -199,7 +192,7 @@ struct StyleArgs {
 
 // Multi-GPU partition: tile-row boundaries of the slabs, and the 48-byte
 // record a slab owner receives per gaussian (GaussianRenderData + blend record + tile rect).
-constexpr uint32_t kMaxSlabs = 16;
+// (kMaxSlabs: gsm_frame_plan.h)
 struct SlabTable {
     uint32_t rows[kMaxSlabs + 1];  // contiguous: slab s = rows [rows[s], rows[s + 1])
     uint32_t n;
@@ -425,7 +418,7 @@ constexpr uint32_t kHalfSkipShift = 30;
 constexpr uint32_t kGidMask = (1u << kHalfSkipShift) - 1u;
 constexpr float kBlendZeroP = 34.65625f;
 
-constexpr int kProjectBlock = 256;
+// (kProjectBlock: gsm_frame_plan.h)
 // entries of the sincos table (one per quantised angle); the 256 byte-table entries follow (gsm_detmath.h)
 constexpr uint32_t kSincosEntries = 65536;
 inline SortSpace sort_space(const DeviceArena& A) { return SortSpace{A.radixHist, A.radixHistBytes, A.radixBinTotals, kSortTotalsWords}; }

@@ -37,8 +37,8 @@ gsm_status GlobalRenderer::create(const gsm_renderer_config& cfg, int hipDevice,
     r->maxGaussians_ = cfg.max_gaussians ? cfg.max_gaussians : 1u;
     r->maxWidth_ = cfg.max_width ? cfg.max_width : 1u;
     r->maxHeight_ = cfg.max_height ? cfg.max_height : 1u;
-    r->tilesX_ = (r->maxWidth_ + kTileWidth - 1) / kTileWidth;
-    r->tilesY_ = (r->maxHeight_ + kTileHeight - 1) / kTileHeight;
+    r->tilesX_ = tiles_x(r->maxWidth_);
+    r->tilesY_ = tiles_y(r->maxHeight_);
     r->tileCount_ = r->tilesX_ * r->tilesY_;
     if (r->tileCount_ > 65536u) {  // 16-bit tile field of the sort key (GlobalShaders.metal:288)
         delete r;
@@ -52,7 +52,7 @@ gsm_status GlobalRenderer::create(const gsm_renderer_config& cfg, int hipDevice,
 
     const size_t G = r->maxGaussians_;
     const size_t cap = r->maxAssignments_;
-    const size_t nb = (G + kProjectBlock - 1) / kProjectBlock;
+    const size_t nb = blocks_of(r->maxGaussians_);
     DeviceArena& A = r->arena_;
     DeviceAllocations& M = r->allocs_;
     M.alloc(st, A.renderData, G * sizeof(GaussianRenderData));
@@ -194,10 +194,9 @@ ProjectArgs GlobalRenderer::frameArgs(const gsm_camera_params& camp, uint32_t wi
 
 gsm_status GlobalRenderer::validateFrame(uint32_t count, bool inputMissing, uint32_t width, uint32_t height,
                                          const void* color, size_t colorPitch, const void* depth,
-                                         size_t depthPitch, const PickTarget* pick,
-                                         const OccluderSource* occluder) const {
+                                         size_t depthPitch) const {
     const gsm_status st = validate_frame(config_, maxGaussians_, maxWidth_, maxHeight_, count, true, inputMissing,
-                                         width, height, color, colorPitch, 1, depth, depthPitch, pick, occluder);
+                                         width, height, color, colorPitch, 1, depth, depthPitch);
     if (st != GSM_OK) return st;
     if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
     return GSM_OK;
@@ -240,12 +239,9 @@ gsm_status GlobalRenderer::selectPick(hipStream_t s, const void* pick, size_t pi
                                       uint32_t* matched) {
     if (!lastPick_) return GSM_ERR_RENDER_FAILED;  // (the handle's last enqueued frame wrote no pick target)
     if (object >= lastPickObjects_) return GSM_ERR_INVALID_ARGUMENT;
-    if (gaussianCount > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
-    if (!frameSizeOk(width, height) || width != lastWidth_ || height != lastHeight_) return GSM_ERR_INVALID_DIMENSIONS;
-    if (!pick || (gaussianCount > 0 && !state)) return GSM_ERR_MISSING_REQUIRED_BUFFER;
-    if (pickPitch < (size_t)width * 4 || (pickPitch & 3u) || (((uintptr_t)pick) & 3u) || (mask && maskPitch < width) ||
-        (((uintptr_t)matched) & 3u))
-        return GSM_ERR_INVALID_BUFFER_SIZE;
+    const gsm_status st = check_select_pick(limits(), gaussianCount, width, height, lastWidth_, lastHeight_, pick,
+                                            pickPitch, mask, maskPitch, state, matched);
+    if (st != GSM_OK) return st;
     // the object's items of the pick frame's layout: [256 * B_o, 256 * B_o + count_o); an object
     // without gaussians has no entry and no item
     uint32_t base = 0, count = 0;
@@ -268,12 +264,9 @@ gsm_status GlobalRenderer::selectPickIds(hipStream_t s, const void* pick, size_t
                                          uint32_t* matched) {
     // selectPick's rows in its order, without those that read the last pick frame: the image holds gaussian ids
     // (a frame of renderFrames), so the items are [0, gaussianCount) and the handle's pick state is not consulted
-    if (gaussianCount > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
-    if (!frameSizeOk(width, height)) return GSM_ERR_INVALID_DIMENSIONS;
-    if (!pick || (gaussianCount > 0 && !state)) return GSM_ERR_MISSING_REQUIRED_BUFFER;
-    if (pickPitch < (size_t)width * 4 || (pickPitch & 3u) || (((uintptr_t)pick) & 3u) || (mask && maskPitch < width) ||
-        (((uintptr_t)matched) & 3u))
-        return GSM_ERR_INVALID_BUFFER_SIZE;
+    const gsm_status st = check_select_pick(limits(), gaussianCount, width, height, width, height, pick, pickPitch, mask,
+                                            maskPitch, state, matched);
+    if (st != GSM_OK) return st;
     return enqueueSelectPick(s, pick, pickPitch, width, height, mask, maskPitch, 0u, gaussianCount, state, andMask,
                              xorMask, matched);
 }
@@ -303,7 +296,7 @@ gsm_status GlobalRenderer::extract(hipStream_t s, const gsm_gaussian_input* in, 
     if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
     if (!arena_.extractBlocks) {  // (the handle's first extract: one word per block of 256 gaussians it can hold)
         st = allocs_.alloc((void**)&arena_.extractBlocks,
-                           (((size_t)maxGaussians_ + kProjectBlock - 1) / kProjectBlock) * sizeof(uint32_t));
+                           (size_t)blocks_of(maxGaussians_) * sizeof(uint32_t));
         if (st != GSM_OK) return st;
     }
     ExtractArgs a{};
@@ -378,7 +371,7 @@ gsm_status GlobalRenderer::stateBounds(hipStream_t s, const gsm_gaussian_input* 
     if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
     if (!arena_.boundsPartials) {  // (the handle's first state_bounds: 32 bytes per block of 256 gaussians it can hold)
         st = allocs_.alloc((void**)&arena_.boundsPartials,
-                           std::max<size_t>(((size_t)maxGaussians_ + kProjectBlock - 1) / kProjectBlock, 1) *
+                           std::max<size_t>(blocks_of(maxGaussians_), 1) *
                                kBoundsPartialBytes);
         if (st != GSM_OK) return st;
     }
@@ -424,17 +417,9 @@ gsm_status GlobalRenderer::renderFrame(hipStream_t s, const gsm_gaussian_input& 
                                        uint32_t width, uint32_t height, const FrameTargets& t,
                                        const FrameExtras& extras) {
     const StyleSource* style = extras.style;
-    gsm_status st = validateFrame(in.gaussian_count, !in.gaussians || !in.harmonics, width, height, t.color,
-                                  t.colorPitch, t.depth, t.depthPitch, extras.pick, extras.occluder);
+    gsm_status st = check_frame(limits(), in, width, height, t, extras);
     if (st != GSM_OK) return st;
-    if (style && !styleSourceOk(*style, 1)) return GSM_ERR_INVALID_ARGUMENT;
-    // (set_tile_rows: a pick frame, an occluded frame and a styled frame are whole frames)
-    // (an orthographic frame too: the flag joins this row)
-    if ((extras.pick || extras.occluder || style || extras.orthographic) && tileRowsRestricted())
-        return GSM_ERR_UNSUPPORTED;
-    // the projection's tile tests walk contiguous rows; interleaved row sets come from the records
-    // path only (gsm_multigpu)
-    if (rowStride_ != 1) return GSM_ERR_INVALID_ARGUMENT;
+    if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
     const bool ortho = extras.orthographic;
     FrameRequest rq = request(FrameKind::Single,
                               frameArgs(camp, width, height, in.gaussian_count, in.sh_components, ortho), width,
@@ -450,13 +435,6 @@ gsm_status GlobalRenderer::renderFrame(hipStream_t s, const gsm_gaussian_input& 
         rq.style = StyleArgs{arena_.styleTable, style->states[0].state, style->states[0].default_state};
     }
     return runFrame(s, rq);
-}
-
-bool GlobalRenderer::styleSourceOk(const StyleSource& style, uint32_t stateCount) {
-    if (!style.styles || style.styleCount == 0 || style.styleCount > kStyleEntries || !style.states) return false;
-    for (uint32_t o = 0; o < stateCount; ++o)
-        if (style.states[o].default_state > 255u) return false;
-    return true;
 }
 
 gsm_status GlobalRenderer::fillStyleTable(hipStream_t s, const gsm_global_style* styles, uint32_t styleCount) {
@@ -483,13 +461,9 @@ gsm_status GlobalRenderer::selectMask(hipStream_t s, const gsm_gaussian_input* i
                                       uint32_t width, uint32_t height, const void* mask, size_t maskPitch,
                                       uint8_t* state, const gsm_global_style* styles, uint32_t styleCount,
                                       uint32_t andMask, uint32_t xorMask, uint32_t* matched, bool orthographic) {
-    // (the count of a NULL input cannot be read: that is the missing buffer, before every other check)
-    if (!in) return GSM_ERR_MISSING_REQUIRED_BUFFER;
-    if (in->gaussian_count > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
-    if (!frameSizeOk(width, height)) return GSM_ERR_INVALID_DIMENSIONS;
-    if (!camp || !mask || (in->gaussian_count > 0 && (!in->gaussians || !state))) return GSM_ERR_MISSING_REQUIRED_BUFFER;
-    if (maskPitch < width || (((uintptr_t)matched) & 3u)) return GSM_ERR_INVALID_BUFFER_SIZE;
-    if (styles ? (styleCount == 0 || styleCount > kStyleEntries) : styleCount != 0) return GSM_ERR_INVALID_ARGUMENT;
+    const gsm_status cst =
+        check_select_mask(limits(), in, camp, width, height, mask, maskPitch, state, styles, styleCount, matched);
+    if (cst != GSM_OK) return cst;
     if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
     (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's)
     if (styles && in->gaussian_count > 0) {
@@ -502,10 +476,6 @@ gsm_status GlobalRenderer::selectMask(hipStream_t s, const gsm_gaussian_input* i
                        orthographic);
     if (hipGetLastError() != hipSuccess) return GSM_ERR_RENDER_FAILED;
     return GSM_OK;
-}
-
-uint32_t GlobalRenderer::tiles_of(uint32_t width, uint32_t height) {
-    return ((width + kTileWidth - 1) / kTileWidth) * ((height + kTileHeight - 1) / kTileHeight);
 }
 
 // What the two batch entries below share on the host.
@@ -536,18 +506,12 @@ static void fill_chunks(const std::vector<Entry>& host, uint32_t count, Launch&&
     }
 }
 
-bool GlobalRenderer::frameSizeOk(uint32_t width, uint32_t height) const {
-    return width != 0 && height != 0 && width <= maxWidth_ && height <= maxHeight_;
-}
-
-bool GlobalRenderer::batchTilesOk(uint64_t allTiles) const { return allTiles <= tileCount_ && allTiles <= 65535u; }
-
 ProjectArgs GlobalRenderer::batchSharedArgs(const gsm_camera_params& camera0, uint32_t width0, uint32_t height0,
                                             uint32_t count, uint32_t shComponents) const {
     // what a batch shares: view 0's arguments on that view's own tile grid, rows [0, tilesY)
     ProjectArgs a = frameArgs(camera0, width0, height0, count, shComponents);
-    a.bin.tilesX = (width0 + kTileWidth - 1) / kTileWidth;
-    a.bin.tilesY = (height0 + kTileHeight - 1) / kTileHeight;
+    a.bin.tilesX = tiles_x(width0);
+    a.bin.tilesY = tiles_y(height0);
     a.rowBegin = 0;
     a.rowEnd = a.bin.tilesY;
     a.rowStride = 1;
@@ -558,25 +522,13 @@ gsm_status GlobalRenderer::renderViews(hipStream_t s, const gsm_gaussian_input& 
                                        uint32_t viewCount, uint32_t width, uint32_t height, void* color,
                                        size_t colorPitch, size_t colorStride, void* depth, size_t depthPitch,
                                        size_t depthStride) {
-    // validate_frame's precedence: count, dimensions, (tiles,) a missing buffer, sizes -- all before anything
-    // is enqueued.  A view's items start on a projection-block boundary, and the values keep 30 bits of item.
-    const uint64_t padded = ((uint64_t)in.gaussian_count + kProjectBlock - 1) / kProjectBlock * kProjectBlock;
-    if (viewCount == 0 || (uint64_t)viewCount * padded > maxGaussians_ || in.gaussian_count > maxGaussians_)
-        return GSM_ERR_INVALID_GAUSSIAN_COUNT;
-    if (!frameSizeOk(width, height)) return GSM_ERR_INVALID_DIMENSIONS;
-    const uint32_t T = tiles_of(width, height);
-    if (!batchTilesOk((uint64_t)viewCount * T)) return GSM_ERR_INVALID_TILE_COUNT;
-    if (!cameras) return GSM_ERR_MISSING_REQUIRED_BUFFER;
-    gsm_status st = validateFrame(in.gaussian_count, !in.gaussians || !in.harmonics, width, height, color, colorPitch,
-                                  depth, depthPitch);
+    const FrameTargets t{color, colorPitch, depth, depthPitch};
+    gsm_status st = check_views(limits(), in, cameras, viewCount, width, height, t, colorStride, depthStride);
     if (st != GSM_OK) return st;
-    // a view's rows fit in its stride, and every view's first row is as aligned as validate_frame asks of the first
-    if (colorStride < (size_t)height * colorPitch || (colorStride & 3u)) return GSM_ERR_INVALID_BUFFER_SIZE;
-    if (depth && (depthStride < (size_t)height * depthPitch || (depthStride & 1u))) return GSM_ERR_INVALID_BUFFER_SIZE;
-    if (tileRowsRestricted()) return GSM_ERR_UNSUPPORTED;  // (set_tile_rows)
+    if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
     // the per-view array: allocated by the first batch, for the most views the handle's tile space holds
     if (!arena_.viewArgs) {
-        maxViews_ = std::min(tileCount_, 65535u);
+        maxViews_ = max_batch_views(tileCount_);
         st = allocs_.alloc((void**)&arena_.viewArgs, (size_t)maxViews_ * sizeof(ViewArgs));
         if (st != GSM_OK) return st;
     }
@@ -594,11 +546,12 @@ gsm_status GlobalRenderer::renderViews(hipStream_t s, const gsm_gaussian_input& 
     fill_chunks<ViewChunk>(viewHost_, viewCount, [&](const ViewChunk& c, uint32_t v0, uint32_t n) {
         launch_fill_views(c, v0, n, arena_.viewArgs, s);
     });
-    FrameRequest rq = request(FrameKind::Views, a, width, height, FrameTargets{color, colorPitch, depth, depthPitch});
+    FrameRequest rq = request(FrameKind::Views, a, width, height, t);
+    const ViewsLayout layout = views_layout(in.gaussian_count, width, height);
     ViewBatch& vb = rq.payload.viewBatch;
     vb.views = viewCount;
-    vb.blocksPerView = (uint32_t)(padded / kProjectBlock);
-    vb.tilesPerView = T;
+    vb.blocksPerView = layout.blocksPerView;
+    vb.tilesPerView = layout.tilesPerView;
     vb.args = arena_.viewArgs;
     rq.payload.colorViewStride = colorStride;
     rq.payload.depthViewStride = depthStride;
@@ -609,40 +562,24 @@ gsm_status GlobalRenderer::renderViews(hipStream_t s, const gsm_gaussian_input& 
 }
 
 gsm_status GlobalRenderer::renderBatch(hipStream_t s, const gsm_global_view* views, uint32_t viewCount) {
-    return enqueueBatch(s, views, viewCount, nullptr);
+    const gsm_status st = check_batch(limits(), BatchViewArray{views, nullptr}, viewCount);
+    return st != GSM_OK ? st : enqueueBatch(s, views, viewCount, nullptr);
 }
 
 gsm_status GlobalRenderer::renderFrames(hipStream_t s, const gsm_global_frame* frames, uint32_t frameCount) {
-    // The rows of this entry that come before the batch's, each over all frames: the first failing
-    // row decides, within it the lowest frame.  (frame_count == 0 falls through to the batch's first row.)
-    if (frameCount >= 1 && !frames) return GSM_ERR_MISSING_REQUIRED_BUFFER;
-    for (uint32_t v = 0; v < frameCount; ++v)
-        if (frames[v].flags & ~GSM_FRAME_ORTHOGRAPHIC) return GSM_ERR_INVALID_ARGUMENT;
-    for (uint32_t v = 0; v < frameCount; ++v)  // (composites inside a batch: out of scope)
-        if (frames[v].object_count != 1) return GSM_ERR_UNSUPPORTED;
-    for (uint32_t v = 0; v < frameCount; ++v)
-        if (!frames[v].objects) return GSM_ERR_MISSING_REQUIRED_BUFFER;
+    gsm_status st = check_frames_front(frames, frameCount);
+    if (st != GSM_OK) return st;
     // the frames as batch views plus what each adds: host copies only (reserved by the handle's first such call
     // for the most views it can hold, so no later call allocates)
     if (framesViews_.capacity() == 0) {
-        const uint32_t mv = std::min(tileCount_, 65535u);
+        const uint32_t mv = max_batch_views(tileCount_);
         framesViews_.reserve(mv);
         framesOptions_.reserve(mv);
     }
-    if (frameCount > framesViews_.capacity()) {
-        // more frames than the handle's tile space has tiles: the batch's rows up to the tile row, which such a
-        // batch cannot pass (every view takes a tile), read from the frames themselves
-        uint64_t items = 0;
-        for (uint32_t v = 0; v < frameCount; ++v) {
-            const uint32_t n = frames[v].objects[0].input.gaussian_count;
-            if (n > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
-            items += ((uint64_t)n + kProjectBlock - 1) / kProjectBlock * kProjectBlock;
-        }
-        if (items > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
-        for (uint32_t v = 0; v < frameCount; ++v)
-            if (!frameSizeOk(frames[v].width, frames[v].height)) return GSM_ERR_INVALID_DIMENSIONS;
-        return GSM_ERR_INVALID_TILE_COUNT;
-    }
+    // the batch's rows, read from the frames themselves (more frames than the copies hold do not pass the tile row:
+    // every view takes a tile)
+    const BatchFrameArray batch{frames};
+    if ((st = check_batch(limits(), batch, frameCount)) != GSM_OK) return st;
     framesViews_.resize(frameCount);
     framesOptions_.resize(frameCount);
     bool any = false;
@@ -657,13 +594,8 @@ gsm_status GlobalRenderer::renderFrames(hipStream_t s, const gsm_global_frame* f
         V.color_pitch_bytes = F.color_pitch_bytes;
         V.depth = F.depth_r16f;
         V.depth_pitch_bytes = F.depth_pitch_bytes;
-        BatchViewOptions& O = framesOptions_[v];
-        O.pick = PickTarget{F.pick_r32u, F.pick_pitch_bytes};  // (a null pointer: the option is not given)
-        O.occluder = OccluderSource{F.occluder_r32f, F.occluder_pitch_bytes};
-        O.styled = F.states || F.styles;  // (one without the other: the styled row refuses)
-        O.style = StyleSource{F.states, F.styles, F.style_count};
-        O.orthographic = (F.flags & GSM_FRAME_ORTHOGRAPHIC) != 0;
-        any = any || F.pick_r32u || F.occluder_r32f || O.styled || O.orthographic;
+        const BatchViewOptions& O = framesOptions_[v] = batch.optionsAt(v);
+        any = any || O.pick.pixels || O.occluder.pixels || O.styled || O.orthographic;
     }
     // every option NULL and no flag in every frame: the plain batch, its path and its device code
     return enqueueBatch(s, framesViews_.data(), frameCount, any ? framesOptions_.data() : nullptr);
@@ -671,68 +603,13 @@ gsm_status GlobalRenderer::renderFrames(hipStream_t s, const gsm_global_frame* f
 
 gsm_status GlobalRenderer::enqueueBatch(hipStream_t s, const gsm_global_view* views, uint32_t viewCount,
                                         const BatchViewOptions* options) {
-    // Every check before anything is enqueued, one kind of check after another over all views (the first
-    // failing kind decides, within it the lowest view): counts, dimensions, tiles, missing buffers, sizes,
-    // sh_components, tile rows.  (The counts of a NULL array cannot be read: that is the missing buffer.)
-    if (viewCount == 0) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
-    if (!views) return GSM_ERR_MISSING_REQUIRED_BUFFER;
-    uint64_t items = 0, allTiles = 0;
-    for (uint32_t v = 0; v < viewCount; ++v) {  // (gsm_global_render's rule per view: an empty scene is a frame)
-        if (views[v].input.gaussian_count > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
-        items += ((uint64_t)views[v].input.gaussian_count + kProjectBlock - 1) / kProjectBlock * kProjectBlock;
-    }
-    if (items > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;  // (the values keep 30 bits of item)
-    for (uint32_t v = 0; v < viewCount; ++v) {
-        const gsm_global_view& V = views[v];
-        if (!frameSizeOk(V.width, V.height)) return GSM_ERR_INVALID_DIMENSIONS;
-        allTiles += tiles_of(V.width, V.height);
-    }
-    if (!batchTilesOk(allTiles)) return GSM_ERR_INVALID_TILE_COUNT;
-    for (uint32_t v = 0; v < viewCount; ++v) {
-        const gsm_global_view& V = views[v];
-        if (!V.color || (V.input.gaussian_count > 0 && (!V.input.gaussians || !V.input.harmonics)))
-            return GSM_ERR_MISSING_REQUIRED_BUFFER;
-    }
-    for (uint32_t v = 0; v < viewCount; ++v) {  // (everything above passed: what is left of validate_frame is sizes)
-        const gsm_global_view& V = views[v];
-        // (a view's pick target and occluder, where given, join the size row as for gsm_global_render_frame)
-        const PickTarget* pick = options && options[v].pick.pixels ? &options[v].pick : nullptr;
-        const OccluderSource* occluder = options && options[v].occluder.pixels ? &options[v].occluder : nullptr;
-        const gsm_status st = validate_frame(config_, maxGaussians_, maxWidth_, maxHeight_, V.input.gaussian_count,
-                                             true, false, V.width, V.height, V.color, V.color_pitch_bytes, 1, V.depth,
-                                             V.depth_pitch_bytes, pick, occluder);
-        if (st != GSM_OK) return st;
-    }
-    for (uint32_t v = 1; v < viewCount; ++v)
-        if (views[v].input.sh_components != views[0].input.sh_components) return GSM_ERR_INVALID_ARGUMENT;
-    // the styled row, per view; the batch has one style table, so every styled view must give the same one (the
-    // six meaningful bytes of every style; pad is ignored)
-    bool anyPick = false, anyOccluder = false, anyOrtho = false;
-    const StyleSource* table = nullptr;
-    for (uint32_t v = 0; options && v < viewCount; ++v) {
-        const BatchViewOptions& O = options[v];
-        anyOrtho = anyOrtho || O.orthographic;
-        anyPick = anyPick || O.pick.pixels;
-        anyOccluder = anyOccluder || O.occluder.pixels;
-        if (!O.styled) continue;
-        if (!styleSourceOk(O.style, 1)) return GSM_ERR_INVALID_ARGUMENT;
-        if (!table) {
-            table = &O.style;
-            continue;
-        }
-        if (O.style.styleCount != table->styleCount) return GSM_ERR_INVALID_ARGUMENT;
-        for (uint32_t i = 0; i < table->styleCount; ++i)
-            if (std::memcmp(&O.style.styles[i], &table->styles[i], offsetof(gsm_global_style, pad)) != 0)
-                return GSM_ERR_INVALID_ARGUMENT;
-    }
-    if (tileRowsRestricted()) return GSM_ERR_UNSUPPORTED;  // (set_tile_rows)
     if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
     // the per-view array and the two lookup tables: allocated by the handle's first batch, for the most views
     // its tile space and its item space hold (every view takes at least one tile; the host copies are reserved
     // with them, so no later batch allocates)
-    const uint32_t maxBlocks = (uint32_t)(((uint64_t)maxGaussians_ + kProjectBlock - 1) / kProjectBlock);
+    const uint32_t maxBlocks = blocks_of(maxGaussians_);
     if (!arena_.batchArgs) {
-        const uint32_t mv = std::min(tileCount_, 65535u);
+        const uint32_t mv = max_batch_views(tileCount_);
         BatchViewArgs* args = nullptr;
         uint16_t *bv = nullptr, *tv = nullptr;
         gsm_status st = allocs_.alloc((void**)&args, (size_t)mv * sizeof(BatchViewArgs));
@@ -754,96 +631,84 @@ gsm_status GlobalRenderer::enqueueBatch(hipStream_t s, const gsm_global_view* vi
         extrasHost_.reserve(maxBatchViews_);
     }
     (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's)
-    // the host copy of the per-view entries (`views` is consumed before the call returns): each view's own
-    // frameArgs -- the camera terms depend on its width and height -- on its own tile grid, rows [0, tilesY)
+    // the host copies of the per-view entries and, with options, of the per-view options lines (`views` is consumed
+    // before the call returns): each view's own frameArgs -- the camera terms depend on its width and height -- on
+    // its own tile grid, rows [0, tilesY), placed by the layout
+    const BatchViewArray batch{views, options};
     const uint32_t sh = views[0].input.sh_components;
     batchHost_.resize(viewCount);
-    uint32_t blockBase = 0, tileBase = 0, countSum = 0;
+    if (options) extrasHost_.resize(viewCount);
+    BatchLayout layout;
     for (uint32_t v = 0; v < viewCount; ++v) {
         const gsm_global_view& V = views[v];
+        const BatchViewDesc desc = batch.at(v);
+        const BatchViewOptions& O = desc.options;
+        const BatchViewLayout l = layout.place(desc);
         const uint32_t n = V.input.gaussian_count;
-        const bool ortho = options && options[v].orthographic;  // (the kind is per view: a quad view mixes them)
-        const ProjectArgs pv = frameArgs(V.camera, V.width, V.height, n, sh, ortho);
+        // (the kind is per view: a quad view mixes them)
+        const ProjectArgs pv = frameArgs(V.camera, V.width, V.height, n, sh, O.orthographic);
         BatchViewArgs& d = batchHost_[v];
         std::memset(&d, 0, sizeof(d));
         set_view_terms(d, pv);
-        d.ortho = ortho ? 1u : 0u;
+        d.ortho = O.orthographic ? 1u : 0u;
         d.count = n;
         d.bin = pv.bin;
-        d.bin.tilesX = (V.width + kTileWidth - 1) / kTileWidth;
-        d.bin.tilesY = (V.height + kTileHeight - 1) / kTileHeight;
-        d.blockBase = blockBase;
+        d.bin.tilesX = l.tilesX;
+        d.bin.tilesY = l.tilesY;
+        d.blockBase = l.blockBase;
         d.world = V.input.gaussians;
         d.harm = V.input.harmonics;
         d.tg.color = (uint8_t*)V.color;
         d.tg.depth = (uint8_t*)V.depth;
         d.tg.colorPitch = V.color_pitch_bytes;
         d.tg.depthPitch = V.depth ? V.depth_pitch_bytes : 0;
-        d.tg.tileBase = tileBase;
-        d.tg.tilesX = d.bin.tilesX;
-        d.tg.tilesY = d.bin.tilesY;
+        d.tg.tileBase = l.tileBase;
+        d.tg.tilesX = l.tilesX;
+        d.tg.tilesY = l.tilesY;
         d.tg.width = V.width;
         d.tg.height = V.height;
-        // the wide stores (16-B colour, 4-B depth pairs) where this view's targets are aligned for them: plan_blend's
-        // rule for a single frame; the bytes are the same either way
-        d.tg.vec = (blend_aligned((uintptr_t)V.color, V.color_pitch_bytes, 16) &&
-                    (!V.depth || blend_aligned((uintptr_t)V.depth, V.depth_pitch_bytes, 8)))
-                       ? (uint32_t)kBlendWide
-                       : 0u;
-        blockBase += (n + kProjectBlock - 1) / kProjectBlock;
-        tileBase += d.bin.tilesX * d.bin.tilesY;
-        countSum += n;
+        d.tg.vec = l.vec;  // (the wide stores where this view's targets are aligned for them)
+        if (!options) continue;
+        BatchExtras& e = extrasHost_[v];
+        std::memset(&e, 0, sizeof(e));
+        e.pick = (uint8_t*)O.pick.pixels;
+        e.pickPitch = O.pick.pixels ? O.pick.pitch : 0;
+        e.occluder = (const uint8_t*)O.occluder.pixels;
+        e.occluderPitch = O.occluder.pixels ? O.occluder.pitch : 0;
+        if (O.styled) {  // (one object per frame: states[0], as renderFrame)
+            e.styled = 1u;
+            e.state = O.style.states[0].state;
+            e.defaultState = O.style.states[0].default_state;
+        }
+        e.align = l.align;
+        e.itemBase = l.itemBase;
     }
     fill_chunks<BatchChunk>(batchHost_, viewCount, [&](const BatchChunk& c, uint32_t v0, uint32_t n) {
         launch_fill_batch(c, v0, n, arena_.batchArgs, arena_.batchBlockView, maxBlocks, arena_.batchTileView, tileCount_,
                           s);
     });
     // what the batch shares: the thresholds, the capacity and the schedule; count = the batch's gaussians (counters)
-    const ProjectArgs a = batchSharedArgs(views[0].camera, views[0].width, views[0].height, countSum, sh);
-    FrameRequest rq = request(FrameKind::Batch, a, views[0].width, views[0].height,
-                              FrameTargets{views[0].color, views[0].color_pitch_bytes, views[0].depth,
-                                           views[0].depth_pitch_bytes});
+    const ProjectArgs a = batchSharedArgs(views[0].camera, views[0].width, views[0].height, layout.countSum, sh);
+    FrameRequest rq = request(FrameKind::Batch, a, views[0].width, views[0].height, batch.at(0).targets);
     BatchFrame& bf = rq.payload.batchFrame;
     bf.views = viewCount;
-    bf.blocks = blockBase;
-    bf.tiles = tileBase;
+    bf.blocks = layout.blocks;
+    bf.tiles = layout.tiles;
     bf.args = arena_.batchArgs;
     bf.blockView = arena_.batchBlockView;
     bf.tileView = arena_.batchTileView;
     rq.shDegree = sh_degree(sh);
-    if (options) {
-        // the host copy of the per-view options, to the device array in kernel-argument chunks as the entries
-        // above; the alignment bits follow each view's own pointer and pitch, by plan_blend's rule for a single frame
-        extrasHost_.resize(viewCount);
-        for (uint32_t v = 0; v < viewCount; ++v) {
-            const BatchViewOptions& O = options[v];
-            BatchExtras& e = extrasHost_[v];
-            std::memset(&e, 0, sizeof(e));
-            e.pick = (uint8_t*)O.pick.pixels;
-            e.pickPitch = O.pick.pixels ? O.pick.pitch : 0;
-            e.occluder = (const uint8_t*)O.occluder.pixels;
-            e.occluderPitch = O.occluder.pixels ? O.occluder.pitch : 0;
-            if (O.styled) {  // (one object per frame: states[0], as renderFrame)
-                e.styled = 1u;
-                e.state = O.style.states[0].state;
-                e.defaultState = O.style.states[0].default_state;
-            }
-            e.align =
-                ((O.pick.pixels && blend_aligned((uintptr_t)O.pick.pixels, O.pick.pitch, 8)) ? (uint32_t)kBlendPick8 : 0u) |
-                ((O.occluder.pixels && blend_aligned((uintptr_t)O.occluder.pixels, O.occluder.pitch, 8))
-                     ? (uint32_t)kBlendOcc8
-                     : 0u);
-            e.itemBase = batchHost_[v].blockBase * (uint32_t)kProjectBlock;
-        }
+    if (options) {  // the options lines to the device array in kernel-argument chunks, as the entries above
         fill_chunks<ExtrasChunk>(extrasHost_, viewCount, [&](const ExtrasChunk& c, uint32_t v0, uint32_t n) {
             launch_fill_batch_extras(c, v0, n, arena_.batchExtras, s);
         });
         bf.extras = arena_.batchExtras;
-        rq.anyPick = anyPick;
-        rq.anyOccluder = anyOccluder;
-        rq.orthographic = anyOrtho;
-        if (table) {
-            const gsm_status st = fillStyleTable(s, table->styles, table->styleCount);
+        rq.anyPick = layout.anyPick;
+        rq.anyOccluder = layout.anyOccluder;
+        rq.orthographic = layout.anyOrtho;
+        if (layout.tableView != BatchLayout::kNoTable) {
+            const StyleSource& table = options[layout.tableView].style;
+            const gsm_status st = fillStyleTable(s, table.styles, table.styleCount);
             if (st != GSM_OK) return st;
             rq.style.table = arena_.styleTable;  // (the views' state bytes travel in their options lines)
         }
@@ -855,49 +720,16 @@ gsm_status GlobalRenderer::enqueueBatch(hipStream_t s, const gsm_global_view* vi
 gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* objects, uint32_t objectCount,
                                         uint32_t width, uint32_t height, const FrameTargets& t,
                                         const FrameExtras& extras) {
-    const PickTarget* pick = extras.pick;
-    const OccluderSource* occluder = extras.occluder;
     const StyleSource* style = extras.style;
     const bool ortho = extras.orthographic;  // (the flag holds for every object; sigma, J and d0 are per object)
-    void* const color = t.color;
-    void* const depth = t.depth;
-    const size_t colorPitch = t.colorPitch, depthPitch = t.depthPitch;
-    // Every check before anything is enqueued, one kind of check after another over all objects (the first
-    // failing kind decides, within it the lowest object): counts, dimensions, missing buffers, sizes,
-    // sh_components, tile rows.  (The counts of a NULL array cannot be read: that is the missing buffer.)
-    if (objectCount == 0) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
-    if (!objects) return GSM_ERR_MISSING_REQUIRED_BUFFER;
-    if (objectCount > 65535u) return GSM_ERR_INVALID_GAUSSIAN_COUNT;  // (a block's entry is a 16-bit index)
-    uint64_t items = 0;
-    uint32_t countSum = 0, entries = 0;
-    for (uint32_t o = 0; o < objectCount; ++o) {
-        const uint32_t n = objects[o].input.gaussian_count;
-        if (n > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;
-        items += ((uint64_t)n + kProjectBlock - 1) / kProjectBlock * kProjectBlock;
-        entries += n ? 1u : 0u;
-    }
-    if (items > maxGaussians_) return GSM_ERR_INVALID_GAUSSIAN_COUNT;  // (the values keep 30 bits of item)
-    if (!frameSizeOk(width, height)) return GSM_ERR_INVALID_DIMENSIONS;
-    if (!color || (pick && !pick->pixels) || (occluder && !occluder->pixels)) return GSM_ERR_MISSING_REQUIRED_BUFFER;
-    for (uint32_t o = 0; o < objectCount; ++o) {
-        const gsm_gaussian_input& in = objects[o].input;
-        if (in.gaussian_count > 0 && (!in.gaussians || !in.harmonics)) return GSM_ERR_MISSING_REQUIRED_BUFFER;
-        countSum += in.gaussian_count;  // (<= items <= max_gaussians)
-    }
-    // (everything above passed: what is left of validate_frame is the pitches and the alignment)
-    gsm_status st = validate_frame(config_, maxGaussians_, maxWidth_, maxHeight_, countSum, true, false, width, height,
-                                   color, colorPitch, 1, depth, depthPitch, pick, occluder);
+    gsm_status st = check_compose(limits(), objects, objectCount, width, height, t, extras);
     if (st != GSM_OK) return st;
-    for (uint32_t o = 1; o < objectCount; ++o)
-        if (objects[o].input.sh_components != objects[0].input.sh_components) return GSM_ERR_INVALID_ARGUMENT;
-    if (style && !styleSourceOk(*style, objectCount)) return GSM_ERR_INVALID_ARGUMENT;
-    if (tileRowsRestricted()) return GSM_ERR_UNSUPPORTED;  // (set_tile_rows)
     if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
     // the per-object array and the block table: allocated by the handle's first composite, for the most objects
     // with gaussians its item space holds (each takes at least one block; the host copies are reserved with
     // them, so no later composite allocates)
-    const uint32_t maxBlocks = (uint32_t)(((uint64_t)maxGaussians_ + kProjectBlock - 1) / kProjectBlock);
-    const uint32_t maxEntries = std::min(maxBlocks, 65535u);
+    const uint32_t maxBlocks = blocks_of(maxGaussians_);
+    const uint32_t maxEntries = max_compose_entries(maxBlocks);
     if (!arena_.composeArgs) {
         ComposeObjectArgs* args = nullptr;
         uint16_t* bo = nullptr;
@@ -906,8 +738,8 @@ gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* 
         if (st != GSM_OK) return st;
         composeHost_.reserve(maxEntries);
         composeObject_.reserve(maxEntries);
-        key_.reserve(ScheduleKey::kFixedWords + 65535u + 1u);  // (the largest signature: a count per object)
-        schedState_.reserve(ScheduleKey::kFixedWords + 65535u + 1u);
+        key_.reserve(ScheduleKey::kFixedWords + kBatchIndexMax + 1u);  // (the largest signature: a count per object)
+        schedState_.reserve(ScheduleKey::kFixedWords + kBatchIndexMax + 1u);
         arena_.composeArgs = args;
         arena_.composeBlockObject = bo;
     }
@@ -917,11 +749,12 @@ gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* 
     const uint32_t sh = objects[0].input.sh_components;
     composeHost_.clear();
     composeObject_.clear();
-    uint32_t blockBase = 0;
+    ComposeLayout layout;
     for (uint32_t o = 0; o < objectCount; ++o) {
         const gsm_global_object& O = objects[o];
         const uint32_t n = O.input.gaussian_count;
-        if (n == 0) continue;  // (no block, no entry)
+        ComposeEntry entry;
+        if (!layout.place(n, &entry)) continue;  // (no gaussians: no block, no entry)
         const ProjectArgs po = frameArgs(O.camera, width, height, n, sh, ortho);
         ComposeObjectArgs d;
         std::memset(&d, 0, sizeof(d));
@@ -929,32 +762,31 @@ gsm_status GlobalRenderer::composeFrame(hipStream_t s, const gsm_global_object* 
         d.count = n;
         d.world = O.input.gaussians;
         d.harm = O.input.harmonics;
-        d.blockBase = blockBase;
+        d.blockBase = entry.blockBase;
         if (style) {  // (a styled composite: the object's state bytes and default travel with its entry)
             d.state = style->states[o].state;
             d.defaultState = style->states[o].default_state;
         }
         composeHost_.push_back(d);
-        composeObject_.push_back(o);  // (pickOwner: the entry's object index of the call)
-        blockBase += (n + kProjectBlock - 1) / kProjectBlock;
+        composeObject_.push_back(entry.object);  // (pickOwner: the entry's object index of the call)
     }
-    fill_chunks<ComposeChunk>(composeHost_, entries, [&](const ComposeChunk& c, uint32_t e0, uint32_t n) {
+    fill_chunks<ComposeChunk>(composeHost_, layout.entries, [&](const ComposeChunk& c, uint32_t e0, uint32_t n) {
         launch_fill_compose(c, e0, n, arena_.composeArgs, arena_.composeBlockObject, maxBlocks, s);
     });
     // the frame's arguments are the single frame's: the handle's tile grid and rows, the thresholds, the capacity
     // and the schedule; count = the composite's gaussians (counters).  (Not batchSharedArgs: that puts a batch on
     // view 0's own grid, and a composite stays on the handle's, as gsm_global_render does.)
-    const ProjectArgs a = frameArgs(objects[0].camera, width, height, countSum, sh, ortho);
+    const ProjectArgs a = frameArgs(objects[0].camera, width, height, layout.countSum, sh, ortho);
     FrameRequest rq = request(FrameKind::Compose, a, width, height, t);
     rq.orthographic = ortho;
     ComposeFrame& cf = rq.payload.composeFrame;
     cf.objects = objectCount;
-    cf.entries = entries;
-    cf.blocks = blockBase;
+    cf.entries = layout.entries;
+    cf.blocks = layout.blocks;
     cf.args = arena_.composeArgs;
     cf.blockObject = arena_.composeBlockObject;
-    rq.pick = pick;
-    rq.occluder = occluder;
+    rq.pick = extras.pick;
+    rq.occluder = extras.occluder;
     rq.shDegree = sh_degree(sh);
     if (style) {
         if ((st = fillStyleTable(s, style->styles, style->styleCount)) != GSM_OK) return st;
@@ -988,23 +820,15 @@ gsm_status GlobalRenderer::preparePartition(const gsm_gaussian_input& in, const 
                                             const void* send, const uint32_t* sendCounts, PartitionFrame* f,
                                             bool interleave) {
     (void)hipGetLastError();  // (an error left by an earlier call of the process is not this call's: the launches below are checked)
-    if ((uint64_t)first + count > in.gaussian_count || count > maxGaussians_)
-        return GSM_ERR_INVALID_GAUSSIAN_COUNT;
-    if (width == 0 || height == 0 || width > maxWidth_ || height > maxHeight_)
-        return GSM_ERR_INVALID_DIMENSIONS;
-    if (!slabRows || numSlabs == 0 || numSlabs > kMaxSlabs) return GSM_ERR_INVALID_ARGUMENT;
-    if (!sendCounts || (count > 0 && ((needSend && !send) || !in.gaussians || !in.harmonics)))
-        return GSM_ERR_MISSING_REQUIRED_BUFFER;
+    gsm_status st = check_partition(limits(), in, width, height, first, count, slabRows, numSlabs, needSend, send,
+                                    sendCounts, interleave);
+    if (st != GSM_OK) return st;
     std::memset(&f->slabs, 0, sizeof(f->slabs));
     f->slabs.n = numSlabs;
     f->slabs.interleave = interleave ? 1u : 0u;  // slab s = rows s, s + n, ... < slabRows[n]
-    for (uint32_t i = 0; i <= numSlabs; ++i) {
-        if (slabRows[i] > tilesY_ || (!interleave && i > 0 && slabRows[i] < slabRows[i - 1]))
-            return GSM_ERR_INVALID_ARGUMENT;
-        f->slabs.rows[i] = slabRows[i];
-    }
+    for (uint32_t i = 0; i <= numSlabs; ++i) f->slabs.rows[i] = slabRows[i];
     if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
-    gsm_status st = ensurePartitionBuffers(numSlabs);
+    st = ensurePartitionBuffers(numSlabs);
     if (st != GSM_OK) return st;
     f->half = config_.precision == GSM_PRECISION_FLOAT16;
     f->a = frameArgs(camp, width, height, count, in.sh_components);
@@ -1023,7 +847,7 @@ gsm_status GlobalRenderer::ensurePartitionBuffers(uint32_t numSlabs) {
     // lazily: only ranks of a partitioned frame need these (the multi-GPU frame: at prepare)
     if (part_.runs && part_.runSlabs >= numSlabs) return GSM_OK;
     if (hipSetDevice(dev_.id) != hipSuccess) return GSM_ERR_DEVICE_NOT_AVAILABLE;
-    const size_t blocks = ((size_t)maxGaussians_ + kProjectBlock - 1) / kProjectBlock;
+    const size_t blocks = blocks_of(maxGaussians_);
     PartitionBuffers b = part_;
     b.runStride = (uint32_t)(blocks * kProjectBlock);
     b.runSlabs = numSlabs;
@@ -1173,7 +997,7 @@ gsm_status GlobalRenderer::runFrame(hipStream_t s, const FrameRequest& rq) {
     const BatchFrame* batch = rq.payload.batch();
     const ComposeFrame* comp = rq.payload.compose();
     const uint32_t nb = comp ? comp->blocks : batch ? batch->blocks : views ? views->views * views->blocksPerView
-                                                                            : (a.count + kProjectBlock - 1) / kProjectBlock;
+                                                                            : blocks_of(a.count);
     // GaussianRenderData for readback only when profiling (bits 0, 1), gsm_debug.h
     ProjectArgs fa = a;
     fa.keepRenderData = capture ? 1u : 0u;

@@ -16,25 +16,7 @@
 
 namespace gsm {
 
-// What the entries of a family add to the plain frame, all nullable and independent (gsm_global_render_frame
-// passes any combination):
-// pick: a per-pixel pick target, the item of each pixel's heaviest contribution;
-// occluder: the frame cut, pixel by pixel, at the depth of an opaque surface, one float per pixel, read only
-// (DESIGN.md 21); style: the style of every gaussian's state byte applied in the projection --
-// the caller's states, one per object, and its table: host memory, consumed by the call.
-struct StyleSource {
-    const gsm_global_state* states;
-    const gsm_global_style* styles;
-    uint32_t styleCount;
-};
-// orthographic: the frame's flag GSM_FRAME_ORTHOGRAPHIC -- the projection rule of every object.
-struct FrameExtras {
-    const PickTarget* pick = nullptr;
-    const OccluderSource* occluder = nullptr;
-    const StyleSource* style = nullptr;
-    bool orthographic = false;
-};
-
+// (FrameExtras, StyleSource, PickTarget, OccluderSource, BatchViewOptions: gsm_frame_plan.h, with the entries' checks)
 class GlobalRenderer {
    public:
     // GlobalRenderer.init(device:config:) (GlobalRenderer.swift:110-193)
@@ -125,8 +107,7 @@ class GlobalRenderer {
                              const MgArrive* blendArrive = nullptr);
     // what renderRecords / the multi-GPU frame would refuse, checked before anything is enqueued
     gsm_status validateFrame(uint32_t count, bool inputMissing, uint32_t width, uint32_t height,
-                             const void* color, size_t colorPitch, const void* depth, size_t depthPitch,
-                             const PickTarget* pick = nullptr, const OccluderSource* occluder = nullptr) const;
+                             const void* color, size_t colorPitch, const void* depth, size_t depthPitch) const;
     // the partition buffers (allocated lazily by the first partition frame; the multi-GPU frame
     // allocates them at prepare so that no frame can fail on an allocation)
     gsm_status ensurePartitionBuffers(uint32_t numSlabs);
@@ -162,8 +143,6 @@ class GlobalRenderer {
 
    private:
     GlobalRenderer() = default;
-    // a styled entry's own refusals (GSM_ERR_INVALID_ARGUMENT), checked after the plain entry's
-    static bool styleSourceOk(const StyleSource& style, uint32_t stateCount);
     // the handle's style table: allocated by its first use, filled from the caller's styles (identity past them)
     gsm_status fillStyleTable(hipStream_t s, const gsm_global_style* styles, uint32_t styleCount);
     // orthographic: the uniforms of the orthographic rule in place of the perspective terms (ProjectArgs)
@@ -209,26 +188,25 @@ class GlobalRenderer {
     // the blend schedule's unit count for a frame of that key over `tiles` tiles (0 when cost order is off), the
     // cost arrays cleared when the key is not the one they belong to
     uint32_t scheduleUnits(hipStream_t s, const ScheduleKey& key, uint32_t tiles);
-    static uint32_t tiles_of(uint32_t width, uint32_t height);  // tiles of a width x height frame
-    // checks and arguments renderViews and renderBatch share: a view's size within the handle's, a batch's
-    // tiles within its tile space and the key's 16-bit field, no set_tile_rows restriction, and the
-    // ProjectArgs of what a batch shares (view 0's, on that view's own grid)
-    bool frameSizeOk(uint32_t width, uint32_t height) const;
-    bool batchTilesOk(uint64_t allTiles) const;
+    // what the handle contributes to the entries' checks (gsm_frame_plan.h)
+    FrameLimits limits() const {
+        FrameLimits L;
+        L.colorFormat = config_.color_format;
+        L.maxGaussians = maxGaussians_;
+        L.maxWidth = maxWidth_;
+        L.maxHeight = maxHeight_;
+        L.tileCount = tileCount_;
+        L.tilesY = tilesY_;
+        L.rowsRestricted = tileRowsRestricted();
+        L.rowStride = rowStride_;
+        return L;
+    }
     bool tileRowsRestricted() const { return rowBegin_ != 0 || rowEnd_ != tilesY_ || rowStride_ != 1; }
+    // the ProjectArgs of what renderViews and a batch share: view 0's, on that view's own grid
     ProjectArgs batchSharedArgs(const gsm_camera_params& camera0, uint32_t width0, uint32_t height0, uint32_t count,
                                 uint32_t shComponents) const;
-    // What a frame of renderFrames adds to its view (host memory of the caller, consumed by the call); pixels null:
-    // the option is not given; styled: states and styles as gsm_global_render_frame takes them for one object.
-    struct BatchViewOptions {
-        PickTarget pick{nullptr, 0};
-        OccluderSource occluder{nullptr, 0};
-        bool styled = false;
-        StyleSource style{nullptr, nullptr, 0};
-        bool orthographic = false;  // the frame's flag: this view's projection rule
-    };
-    // renderBatch and renderFrames: every check, the per-view entries and tables, the request, the frame.
-    // options (nullable, [viewCount]): null is the plain batch, device code and all.
+    // renderBatch and renderFrames after check_batch: the lazy allocations, the per-view entries and tables from the
+    // layout, the request, the frame.  options (nullable, [viewCount]): null is the plain batch, device code and all.
     gsm_status enqueueBatch(hipStream_t s, const gsm_global_view* views, uint32_t viewCount,
                             const BatchViewOptions* options);
     // the tail selectPick and selectPickIds share: the bitmap (allocated by the first call) and the two launches
